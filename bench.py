@@ -16,6 +16,9 @@ Launch modes
 `value` is weak scaling (--samples-per-gpu samples on every GPU, ONE all-reduce of the packed sums per step); the
 strong-scaling figure on a fixed 24 576-sample ensemble is reported beside it (`strong_scaling`).
 
+A plain run sets up, warms up, times --steps steps and prints the line; everything measured beside it (strong scaling, CPU
+baselines, latency, other sizes and configurations, the issue-bound probe) runs only with --full.
+
 Prints ONE JSON line on rank 0 (see the contract in the repository brief)."""
 import argparse
 import json
@@ -51,8 +54,19 @@ def parse_args():
     ap.add_argument("--dense-only", type=int, default=0, metavar="SAMPLES",
                     help="profiling runs: only the dense_operator block at this batch size (one full-length evaluation), printed as the line")
     ap.add_argument("--quick-extras", action="store_true",
-                    help="tests: keep the strong-scaling points and a one-repetition CPU baseline, skip the other side measurements")
-    return ap.parse_args()
+                    help="with --full, for tests: keep the strong-scaling points and a one-repetition CPU baseline, skip the other side "
+                         "measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements after the timed steps: strong scaling, CPU baselines, the issue-bound probe, "
+                         "latency, other batch sizes and integrators, the dense operator, the other BASELINE configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (infidelity, leakage and their gradients) as DIR/<name>.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.quick_extras and not args.full:
+        ap.error("--quick-extras only trims the side measurements of --full")
+    return args
 
 
 def visible_gpu_count(sysfs_glob="/sys/class/kfd/kfd/topology/nodes/*/properties"):
@@ -518,10 +532,19 @@ def main():
     mfma_bwd = sum(t["mfma_backward"] for t in tms)
     tm = tms[-1]
     infid_weak = params.last_infidelity
+    if args.dump_outputs and rank == 0:
+        # what eval_f_g_grad hands its caller after the last timed step (the side measurements below overwrite params.last_*)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, val in (("infidelity", params.last_infidelity), ("leak", params.last_leak),
+                          ("infidelity_grad", params.last_infidelity_grad), ("leak_grad", params.last_leak_grad)):
+            arr = np.atleast_1d(np.asarray(val, dtype=np.float64))
+            if arr.size:                # (leak_grad is empty for objFuncType 1)
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+    extras = args.full and not args.no_extras
 
     # ---- strong scaling: a FIXED ensemble split over the job's GPUs (outside the timed region of `value`) ------------
     strong = strong_small = None
-    if not args.no_extras:
+    if extras:
         def strong_point(ns, note):
             n2, w2, s2 = jq.cases.cnot3_ensemble(ns)
 
@@ -659,7 +682,7 @@ def main():
                             "traffic": pf.get("hbm_bytes_per_launch"),
                             "frac_incl_coupling_fma": (ach_f + fma_fwd / fwd_launch_s / 1e12) / FP64_MFMA_PEAK_TFLOPS if fwd_launch_s > 0 else None,
                             "products_per_step": 8 + 2 * m}
-        if band == 7 and not args.no_extras and not args.quick_extras:
+        if band == 7 and extras and not args.quick_extras:
             roofline["issue_bound"] = issue_bound(avg_launch_s, nsteps * args.steps / max(nb, 1), 2 * (8 + 2 * m) + 4 * Nc,
                                                   min(3, max(1, round(args.samples_per_gpu * N / 16 / 256))))
         out = {"metric": "traceobjgrad evals/sec (fwd+adjoint), cnot3 Hilbert dim", "value": value,
@@ -689,10 +712,10 @@ def main():
         if strong is not None:
             out["strong_scaling"] = strong
             out["strong_scaling_small"] = strong_small
-        if not args.no_extras and not args.no_cpu_baseline and (ngpus > 1 or args.quick_extras):
+        if extras and not args.no_cpu_baseline and (ngpus > 1 or args.quick_extras):
             # rank 0 of an N-rank job (the line a SCALE run parses) carries the CPU baseline too: bounded sample, one core
             out["cpu_baseline"] = cpu_baseline(params, pcof, nrep=1 if args.quick_extras else 2, all_cores=False)
-        if ngpus == 1 and not args.no_extras and not args.quick_extras:
+        if ngpus == 1 and extras and not args.quick_extras:
             # outside the timed region: the latency of ONE evaluation and of the reference's 9-node ensemble
             # (examples/Risk_Neutral/run_all.jl:134) -- what an Ipopt iteration of the reference waits for -- next to the
             # CPU figures below; not part of `value`

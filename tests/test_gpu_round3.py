@@ -298,7 +298,7 @@ def test_bench_under_torch_distributed_run_one_rank(hip):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", JQ_BENCH_SAMPLES="256")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
-           "--strong-samples", "512", "--quick-extras"]
+           "--strong-samples", "512", "--full", "--quick-extras"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -312,6 +312,36 @@ def test_bench_under_torch_distributed_run_one_rank(hip):
     assert j["per_rank_ms"]["min"] <= j["per_rank_ms"]["max"] and j["allreduce_ms"] >= 0.0
     assert j["cpu_baseline"]["value"] > 0 and j["cpu_baseline"]["cores"] == 1
     assert j["strong_scaling"]["total_samples"] == 512 and "strong_scaling_small" in j
+
+
+def test_plain_bench_run_and_its_dumped_outputs(hip, tmp_path):
+    """`bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR`: the line of a plain run carries no side measurement (those
+    need --full), and DIR holds what the last timed step returned -- the same numbers as one evaluation of the same inputs here."""
+    jq = hip
+    ns = 256
+    env = dict(os.environ, JQ_BENCH_SAMPLES=str(ns))
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["steps"] == 2 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0 and j["dtype"] == "f64"
+    for k in ("strong_scaling", "cpu_baseline", "single_evaluation", "dense_operator", "baseline_configs"):
+        assert k not in j, k
+    assert "issue_bound" not in j["roofline"]
+    dumped = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert set(dumped) == {"infidelity", "leak", "infidelity_grad"}, sorted(dumped)
+    assert all(a.dtype == np.float64 for a in dumped.values())
+    assert dumped["infidelity"][0] == j["ensemble_infidelity"]
+    params, info, pcof, _ = case_inputs("cnot3")
+    nodes, weights, shift = jq.cases.cnot3_ensemble(ns)
+    wa = jq.Working_Arrays_HIP(params, pcof.size)
+    jq.eval_f_g_grad(pcof, params, wa, nodes, weights, True, shift=shift)
+    wa.close()
+    assert rel(dumped["infidelity"], params.last_infidelity) < 1e-12 and rel(dumped["leak"], params.last_leak) < 1e-12
+    assert rel(dumped["infidelity_grad"], params.last_infidelity_grad) < 1e-12
 
 
 # ---- (5) more than four control Hamiltonians, drift updates outside the planned structure -------------------------------------

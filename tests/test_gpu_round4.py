@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 def test_bench_single_process_same_device(K):
     env = dict(os.environ, JQ_OPTIONS="multi_same_device=1", JQ_BENCH_SAMPLES="128")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--single-process", "--gpus", str(K), "--steps", "1", "--warmup", "1",
-           "--strong-samples", "512", "--strong-small-samples", "256", "--quick-extras"]
+           "--strong-samples", "512", "--strong-small-samples", "256", "--full", "--quick-extras"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

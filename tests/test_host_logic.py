@@ -190,6 +190,17 @@ def test_bench_counts_gpus_without_initialising_hip(tmp_path, monkeypatch):
     assert b.visible_gpu_count(pattern) == 0
 
 
+def test_bench_refuses_arguments_without_effect():
+    """--steps below 1 times nothing, and --quick-extras trims only the side measurements of --full: both are refused before
+    anything is imported or started."""
+    import subprocess
+    for extra in (["--steps", "0"], ["--quick-extras"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + extra, capture_output=True, text=True,
+                           timeout=120)
+        assert r.returncode == 2 and "error:" in r.stderr, (extra, r.stderr)
+        assert not any(ln.startswith("{") for ln in r.stdout.splitlines())
+
+
 def test_bench_spawns_its_ranks_through_the_launcher_command_line(tmp_path, monkeypatch):
     """`python bench.py --gpus 4` without a launcher: the command line it starts (stub launcher: prints its arguments) is the
     driver's own form -- one node, 4 ranks, rendezvous on 127.0.0.1 -- followed by bench.py and the caller's arguments."""
