@@ -198,6 +198,18 @@ static long long bwd_lds_tail(int NT, int Nc, int nwaves, long long park_doubles
 {
     return 32LL * NT * 8 + (long long)Nc * 64 * nwaves * 8 + (long long)nwaves * park_doubles * 8 + 2LL * nwaves * 8 * Nc * 8;
 }
+// Dynamic LDS (bytes) of the kernel layouts the planner checks when a handle is created and per batch (plan_batch), and the LDS of a CU:
+#define JQ_LDS_MAX 163840
+// window staging (jq_kernels.h Ring): JQ_WIN_TPS time points (K and S image each) and the constant trace images, images of `stride` doubles
+static size_t win_lds(const jq_handle* h, long long stride) { return (size_t)(2 * JQ_WIN_TPS + 2 * h->NcK) * stride * 8; }
+// backward quad-layout kernel with spw slabs per workgroup: window staging + bwd_lds_tail (a 16-row block per register to park)
+static size_t quad_bwd_lds(const jq_handle* h, int spw) { return win_lds(h, h->mat_elems) + (size_t)bwd_lds_tail(h->NT, h->NcK, 4 * spw, (long long)h->NT * 64); }
+// cooperative-quad kernels (jq_cq_kernels.h) behind the operator staging: tables, x exchange, trace hand-off / wg-sum scratch (one region)
+static size_t cq_lds(const jq_handle* h, size_t lds_stage) { return lds_stage + (size_t)32 * h->NT * 8 + (size_t)6 * (h->NT + 2) * 64 * 8 + (size_t)std::max(2, h->NcK + (h->NcK + 1) / 2) * h->NT * 64 * 8; }
+// k_backward_qsplit (jq_quad_split_kernels.h): ring of JQ_QS_TPS time points + constant images, tables, trace records
+static size_t qsplit_lds(const jq_handle* h, int qw) { return (size_t)(2 * JQ_QS_TPS + 2 * h->NcK) * h->mat_elems * 8 + (size_t)32 * h->NT * 8 + (size_t)2 * qw * 8 * h->NcK * 8; }
+// k_backward_cq_imr2: staging + tables + two exchange images (one per set of waves) + the decisions
+static size_t cq_imr2_lds(const jq_handle* h, size_t lds_stage) { return lds_stage + (size_t)32 * h->NT * 8 + (size_t)12 * (h->NT + 2) * 64 * 8 + 64; }
 
 // Dense column-major copy of a sparse operator in Julia's SparseMatrixCSC form (jq_csc: 1-based Int64 colptr / rowval); repeated
 // entries are summed.  The planner then sees exactly the structure it would see for the dense form of the same operator.
@@ -417,11 +429,11 @@ static int create_dense(const jq_problem* p, jq_handle* h)
             // equal one of the structure codes (NT = 8, 9, 10: 7 = JQ_BW_T4Q, 8 = JQ_BW_T4, 9 = JQ_BW_OD) -- round 2 sent dense
             // problems with Ntot 113 .. 160 to kernel families that do not exist for them (found by the round-3 tests)
             h->BW = -1;
-        } else if (2 * slot + lds_fwd_fixed > 163840)
+        } else if (2 * slot + lds_fwd_fixed > JQ_LDS_MAX)
             return fail(h, JQ_EUNSUPPORTED, "jq_create: operator images do not fit the LDS double buffer");
         h->nslots = 2;
         h->nslots_bwd = 2;
-        h->park_lds = (2 * slot + lds_bwd_fixed + park_bytes <= 163840) ? 1 : 0;
+        h->park_lds = (2 * slot + lds_bwd_fixed + park_bytes <= JQ_LDS_MAX) ? 1 : 0;
         // cooperative (row-split) kernels for small batches: NT waves per slab, needs NT >= 2
         // (NT == 1: only the implicit-midpoint kernels are instantiated -- Ntot <= 16 with more than four columns per evaluation)
         h->mat_elems_c = 0;
@@ -437,7 +449,7 @@ static int create_dense(const jq_problem* p, jq_handle* h)
             h->mat_elems_c = ec;                  // (the images are built whenever the layout exists ...)
             // (... the Stormer-Verlet kernels need two of them in LDS -- or none: NT > 6; the 4 x 4 x 7 / 4 x 4 x 8 structures keep
             //  their JQ_BW_T4 slab kernels as the Stormer-Verlet fallback: the cooperative layout serves their implicit-midpoint path)
-            h->coop_ok = lds_c <= 163840 && (h->NT <= 6 || h->big);
+            h->coop_ok = lds_c <= JQ_LDS_MAX && (h->NT <= 6 || h->big);
             if (h->huge) h->coop_ok = true;      // (static LDS only)
         }
         h->coop_max_slabs = prop.multiProcessorCount;   // one cooperative workgroup per CU = one round
@@ -452,52 +464,35 @@ static int create_dense(const jq_problem* p, jq_handle* h)
         // resident in LDS, one workgroup barrier per time step.  Used whenever it fits next to the backward kernel's carry
         // and parking images (kernels compiled for two workgroups per CU: in half of the LDS); option window=0 disables it.
         {
-            const long long win = (2LL * JQ_WIN_TPS + 2LL * h->NcK) * slot;
-            const long long budget = (h->NT <= JQ_MINW_MAXNT) ? 81920 : 163840;
-            bool w = !h->big && win + lds_bwd_fixed + park_bytes <= budget;
-            if (!h->opt.on(O_WINDOW)) w = false;
-            if (w) {
+            const long long budget = (h->NT <= JQ_MINW_MAXNT) ? JQ_LDS_MAX / 2 : JQ_LDS_MAX;
+            if (!h->big && (long long)win_lds(h, h->mat_elems) + lds_bwd_fixed + park_bytes <= budget && h->opt.on(O_WINDOW)) {
                 h->batch = -1;
                 h->park_lds = 1;
             }
         }
         // Quad-layout kernels (jq_kernels.h JQ_BW_T4Q) for this structure: workgroups of 4, 8 or 12 waves carry 1, 2 or 3 slabs
-        // (1, 2, 3 waves per SIMD; one workgroup per CU because of the LDS).  run_eval picks the variant -- or the slab
-        // kernels -- by the number of rounds the batch needs (quad_plan).  option quad=0 disables them, option quad=<n> limits them to
+        // (1, 2, 3 waves per SIMD; one workgroup per CU because of the LDS).  plan_batch picks the variant -- or the slab
+        // kernels -- by the number of rounds the batch needs (t4_rounds).  option quad=0 disables them, option quad=<n> limits them to
         // batches of at most n slabs.
         // (they always use the window staging and need less LDS next to it than the slab kernels -- a register per 16-row block
         // to park -- so they are also available when the slab kernels have to fall back to the per-operator ring: Ntot > 80, Nc = 4)
-        {
-            const long long win = (2LL * JQ_WIN_TPS + 2LL * h->NcK) * slot;
-            const long long quad_fixed = bwd_lds_tail(h->NT, h->NcK, JQ_WAVES, (long long)h->NT * 64);
-            bool w = h->BW == JQ_BW_T4 && win + quad_fixed <= 163840;
-            if (!h->opt.on(O_WINDOW)) w = false;
-            h->quad_max_slabs = w ? (1 << 30) : 0;
-        }
+        h->quad_max_slabs = (h->BW == JQ_BW_T4 && quad_bwd_lds(h, 1) <= JQ_LDS_MAX && h->opt.on(O_WINDOW)) ? (1 << 30) : 0;
         h->num_cu = prop.multiProcessorCount;
         if (h->opt.has(O_QUAD) && h->quad_max_slabs > 0) h->quad_max_slabs = (int)h->opt.get(O_QUAD);
         // Cooperative-quad kernels (jq_cq_kernels.h): the latency path -- one workgroup of NT waves per column quad while every
         // quad still gets a CU of its own (LDS: the window staging, one workgroup per CU).  NT >= 2 (a single block has no
         // neighbour to split the work with).  option cq=0 disables them, option cq=<n> bounds the number of quads.
-        {
-            const long long win = (2LL * JQ_WIN_TPS + 2LL * h->NcK) * slot;
-            const long long tail = 32LL * h->NT * 8 + 6LL * (h->NT + 2) * 64 * 8 + (long long)std::max(2, h->NcK + (h->NcK + 1) / 2) * h->NT * 64 * 8;      // (run_eval: lds_cq)
-            h->cq_max_quads = (h->BW == JQ_BW_T4 && h->NT >= 2 && h->NT <= 7 && h->quad_max_slabs > 0 && win + tail <= 163840) ? 2 * prop.multiProcessorCount : 0;      // (two rounds of them, 2 x 0.20 s at cnot3, still beat one round of the quad-layout kernels, 0.55 s)
-            if (h->opt.has(O_CQ) && h->cq_max_quads > 0) h->cq_max_quads = (int)h->opt.get(O_CQ);
-        }
+        h->cq_max_quads = (h->BW == JQ_BW_T4 && h->NT >= 2 && h->NT <= 7 && h->quad_max_slabs > 0 && cq_lds(h, win_lds(h, h->mat_elems)) <= JQ_LDS_MAX) ? 2 * prop.multiProcessorCount : 0;      // (two rounds of them, 2 x 0.20 s at cnot3, still beat one round of the quad-layout kernels, 0.55 s)
+        if (h->opt.has(O_CQ) && h->cq_max_quads > 0) h->cq_max_quads = (int)h->opt.get(O_CQ);
         // ... with the DENSE policy (round 6, jq_cq_kernels.h CoopQ<2, true>): two 16-row blocks WITHOUT the structure (17 .. 32 levels: two
         // five-level subsystems, a drift in its eigenbasis, ...), whose small batches otherwise take the cooperative kernels.  Images of
         // JQ_DQ_ELEMS doubles in the window staging; Neumann solver, Diagonal weights.  option dq=0 disables them.
-        {
-            const long long win = (2LL * JQ_WIN_TPS + 2LL * h->NcK) * JQ_DQ_ELEMS * 8;
-            const long long tail = 32LL * h->NT * 8 + 6LL * (h->NT + 2) * 64 * 8 + (long long)std::max(2, h->NcK + (h->NcK + 1) / 2) * h->NT * 64 * 8;      // (run_eval: lds_cq)
-            h->dq_max_quads = (h->NT == 2 && h->BW != JQ_BW_T4 && !h->big && !h->huge && !h->is_emb && win + tail <= 163840 && h->opt.on(O_DQ)) ? 3 * prop.multiProcessorCount : 0;      // (three rounds of them, 3 x 16 ms per 2 000 steps, still beat one round of the cooperative kernels, 52 ms: profiles/r06_midsize_single.txt (g))
-        }
+        h->dq_max_quads = (h->NT == 2 && h->BW != JQ_BW_T4 && !h->big && !h->huge && !h->is_emb && cq_lds(h, win_lds(h, JQ_DQ_ELEMS)) <= JQ_LDS_MAX && h->opt.on(O_DQ)) ? 3 * prop.multiProcessorCount : 0;      // (three rounds of them, 3 x 16 ms per 2 000 steps, still beat one round of the cooperative kernels, 52 ms: profiles/r06_midsize_single.txt (g))
         if (h->opt.has(O_BATCH)) {      // (experiment builds only: jq_options.h)
             const int v = (int)h->opt.get(O_BATCH);
             if (v >= 2 && slot <= 8192) {
                 const long long fixed = lds_bwd_fixed + park_bytes + 2LL * h->NcK * slot;
-                const long long per_buf = (163840 - fixed) / 2;
+                const long long per_buf = (JQ_LDS_MAX - fixed) / 2;
                 long long B = (per_buf / (2 * slot) - 1) / 2;
                 if (B > v) B = v;
                 if (B >= 2) {

@@ -78,7 +78,7 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
     kv("neumann_terms_or_max_iter", num(h->integrator == 2 ? h->imr_max_iter : h->m));
     kv("chunk_steps", num(h->chunk_steps));
     kv("replanned", h->replanned ? "true" : "false");
-    // kernel families in the order run_eval considers them for a Stormer-Verlet / Neumann batch (the embedded twin, if any, serves
+    // kernel families in the order plan_batch considers them for a Stormer-Verlet / Neumann batch (the embedded twin, if any, serves
     // the batches beyond the row-lane / lane range with ITS plan)
     std::string fam = "[";
     auto add = [&](int id, const char* name, const char* unit, long long mx) {

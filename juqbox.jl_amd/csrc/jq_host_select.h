@@ -116,12 +116,12 @@ extern template __global__ void k_backward_cq3<2, true, false, 2, false, true>(P
 // fwd2: the forward kernel with two column quads per workgroup (grid = 2 * nslabs); bwd3: the backward sweep on three workgroups per
 // quad (k_backward_cq3)
 // control q acts on subsystem q only (the usual Juqbox set-up: Hsym_ops = [a + a', b + b', c + c']): its trace products need one part of
-// the product each
-static bool cq_ord(const jq_handle* h)
+// the product each (the callers bound Nc first: at most JQ_MAXNC trace modes)
+static bool ctrl_per_subsystem(const jq_handle* h)
 {
-    bool ord = h->Nc <= 3 && !h->opt.on(O_CQ_GENERIC_TRACES);      // (more than JQ_MAXNC controls: generic traces per control group)
-    for (int q = 0; q < h->Nc && ord; ++q) ord = (h->bw_trace[q] == (1 << q));
-    return ord;
+    for (int q = 0; q < h->Nc; ++q)
+        if (h->bw_trace[q] != (1 << q)) return false;
+    return true;
 }
 static int select_cq_kernels(jq_handle* h, bool fwd2, int bwd_nr, bool wlr, bool dense, prop_kernel_t* fwd, prop_kernel_t* bwd)      // bwd_nr: workgroups per quad in the backward sweep (0 / 1: one); wlr: full (real, low-rank) leakage weights; dense: no structure, NT = 2
 {
@@ -135,7 +135,7 @@ static int select_cq_kernels(jq_handle* h, bool fwd2, int bwd_nr, bool wlr, bool
                     : (modd ? k_backward_cq<2, true, false, false, true> : k_backward_cq<2, false, false, false, true>);
         return JQ_OK;
     }
-    const bool ord = cq_ord(h);
+    const bool ord = h->Nc <= 3 && !h->opt.on(O_CQ_GENERIC_TRACES) && ctrl_per_subsystem(h);      // (more than JQ_MAXNC controls: generic traces per group)
 #define JQ_PICKCQ(nt)                                                              \
     if (h->NT == nt && wlr) {                                                      \
         *fwd = modd ? k_forward_cq<nt, true, 1, true> : k_forward_cq<nt, false, 1, true>;                        \
@@ -195,8 +195,6 @@ JQ_DECLCI(1) JQ_DECLCI(2) JQ_DECLCI(3) JQ_DECLCI(4) JQ_DECLCI(5) JQ_DECLCI(6) JQ
 #define JQ_DECLCI(nt) extern template __global__ void k_backward_cq_imr2<nt>(PropArgs);
 JQ_DECLCI(1) JQ_DECLCI(2) JQ_DECLCI(3) JQ_DECLCI(4) JQ_DECLCI(5) JQ_DECLCI(6)
 #undef JQ_DECLCI
-// dynamic LDS of k_backward_cq_imr2: staging + tables + two exchange images (one per set of waves) + the decisions
-static size_t cq_imr2_lds(const jq_handle* h, size_t lds_stage) { return lds_stage + (size_t)32 * h->NT * 8 + (size_t)12 * (h->NT + 2) * 64 * 8 + 64; }
 // two: the backward sweep with the state and the adjoint chain on two sets of waves (NT <= 6, LDS permitting; option imr_cq2=0: the
 // one-set kernel of round 3)
 extern template __global__ void k_forward_cq_imr<2, true>(PropArgs);      // the dense policy (17 .. 32 levels without the structure)
@@ -245,8 +243,7 @@ static int select_quad_kernels(jq_handle* h, int spw, prop_kernel_t* fwd, prop_k
     // per workgroup + 1.6 ... 3.4 %)
     const bool uni = (h->N % 4 == 0 || h->parts > 1) && !h->opt.on(O_NO_UNI);
     // ... and its ORD variant when control q acts on subsystem q only (like the cooperative-quad kernels, select_cq_kernels)
-    bool ord = uni && h->Nc >= 2 && h->Nc <= 3 && !h->opt.on(O_NO_ORD);
-    for (int q = 0; q < h->Nc && ord; ++q) ord = (h->bw_trace[q] == (1 << q));
+    const bool ord = uni && h->Nc >= 2 && h->Nc <= 3 && !h->opt.on(O_NO_ORD) && ctrl_per_subsystem(h);
 #define JQ_PICKQ(nt)                                                                                                                             \
     if (h->NT == nt) {                                                                                                                           \
         *fwd = spw == 3 ? k_forward<nt, JQ_BW_T4Q, 3, false> : spw == 2 ? k_forward<nt, JQ_BW_T4Q, 2, false> : k_forward<nt, JQ_BW_T4Q, 1, false>;     \
@@ -272,15 +269,10 @@ template <int NT, bool ORD, int QW, bool RIDE = false> __global__ void k_backwar
     extern template __global__ void k_backward_qsplit<nt, true, 2, true>(PropArgs);
 JQ_DECLQS(1) JQ_DECLQS(2) JQ_DECLQS(3) JQ_DECLQS(4) JQ_DECLQS(5) JQ_DECLQS(6)
 #undef JQ_DECLQS
-static size_t qsplit_lds(const jq_handle* h, int qw)      // ring of JQ_QS_TPS time points + constant images, tables, trace records
-{
-    return (size_t)(2 * JQ_QS_TPS + 2 * h->NcK) * h->mat_elems * 8 + (size_t)32 * h->NT * 8 + (size_t)2 * qw * 8 * h->NcK * 8;
-}
 static int select_qsplit_kernel(jq_handle* h, int qw, prop_kernel_t* bwd)
 {
     // control q acts on subsystem q only (like select_quad_kernels / select_cq_kernels): compile-time trace modes
-    bool ord = h->Nc >= 2 && h->Nc <= 3 && !h->opt.on(O_NO_ORD);
-    for (int q = 0; q < h->Nc && ord; ++q) ord = (h->bw_trace[q] == (1 << q));
+    const bool ord = h->Nc >= 2 && h->Nc <= 3 && !h->opt.on(O_NO_ORD) && ctrl_per_subsystem(h);
     // ... and with exactly three of them every trace product rides along in a pass of the adjoint step (RIDE; option qs_ride=0: separate passes)
     // -- where the adjoint wave is alone on its SIMD (qw = 2: - 6 %); with two waves per SIMD and the adjoint wave first in the issue
     // arbitration the rides buy nothing (248.9 ms without, 250.0 with): qw = 4 keeps the separate passes (bit-identical to the one-wave

@@ -207,7 +207,8 @@ struct DeviceGuard {
 #include "jq_host_create.h"      // device buffers, uploads, jq_create* (planning from the operators' nonzero structure), structure embedding
 #include "jq_host_update.h"      // the mutations scripts apply to params after construction: solver / integrator, target, drift (re-planning), leakage weights
 #include "jq_host_select.h"      // the kernel instantiations (compiled in their own translation units) and the tables that pick one
-#include "jq_host_eval.h"      // run_eval: how a batch is routed to a kernel family and propagated chunk by chunk
+#include "jq_host_plan.h"      // plan_batch: how a batch is routed to a kernel family, its geometry and LDS layout
+#include "jq_host_eval.h"      // run_eval: a batch evaluated by its plan, chunk by chunk
 extern "C" int jq_traceobjgrad(jq_handle* h, const double* pcof, int32_t ncoeff, int32_t evaladjoint, double* out4,
                                double* totalgrad, double* infidelgrad, double* leakgrad)
 {
