@@ -40,8 +40,9 @@ extern "C" {
  *     complex leakage weights);
  * 5 = per-handle options instead of environment variables (jq_create_opts, jq_create_multi_opts, jq_set_option, jq_get_option),
  *     jq_timing.reserved renamed kernel_variant, jq_rccl_world_size; no size limits on Ntot, the number of control Hamiltonians or
- *     the rank of a full weight matrix; full leakage weights with the Jacobi solver. */
-#define JQ_ABI_VERSION 5
+ *     the rank of a full weight matrix; full leakage weights with the Jacobi solver;
+ * 6 = continuation adjoints: jq_update_dvds, jq_set_sv_type, jq_get_sv_type (params.dVds_r / dVds_i / sv_type). */
+#define JQ_ABI_VERSION 6
 
 #define JQ_MAX_CONTROLS 16 /* control Hamiltonians the fast kernels hold in registers; more: cooperative kernels (no limit)    */
 #define JQ_MAX_WRANK 16    /* rank of a full leakage-weight matrix every kernel family takes; beyond: slab / cooperative kernels */
@@ -72,7 +73,7 @@ typedef struct jq_csc {
 /*
  * Problem description = the objparams fields the device needs (src/evalobjgrad.jl:53-148;
  * SURVEY.md section 8 row a13).  Hard-wired in the reference and therefore not passed:
- * use_bcarrier=true (:208), pFidType=2 (:164), sv_type=1 (:314), order=2/stages=1 (:507,:644).
+ * use_bcarrier=true (:208), pFidType=2 (:164), order=2/stages=1 (:507,:644).  (sv_type and dVds: jq_set_sv_type, jq_update_dvds.)
  */
 typedef struct jq_problem {
     int32_t Ntot;          /* prod(Ne+Ng): Hilbert dimension incl. guard levels                   */
@@ -241,6 +242,31 @@ int jq_set_linear_solver(jq_handle *h, int32_t solver_id, int32_t max_iter, doub
 int jq_set_integrator(jq_handle *h, int32_t integrator_id, int32_t max_iter, double tol);
 /* change_target!(params, new_Utarget) (src/evalobjgrad.jl:1492) */
 int jq_update_target(jq_handle *h, const double *Utarget_r, const double *Utarget_i);
+/*
+ * Continuation adjoints (ABI 6).  objparams(...; dVds = D) sets params.sv_type = 2 (src/evalobjgrad.jl:312-319), set_adjoint_Sv_type!
+ * (:1516-1520) sets 1, 2 or 3, and the Stormer-Verlet adjoint then starts differently (:815-844).  With T the target, D = dVds and
+ * s_X = tr(X' V(T))/N:
+ *   JQ_SV_TARGET 1: lambda(T) = s_T conj(T)/N  (the default)
+ *   JQ_SV_TERM1  2: lambda(T) = s_T conj(D)/N  ("term 1 of d/ds grad G")
+ *   JQ_SV_TERM2  3: lambda(T) = s_D conj(T)/N  ("term 2 of d/ds grad G")
+ *   JQ_SV_BOTH   4: lambda(T) = (s_T conj(D) + s_D conj(T))/N -- not in the reference: the gradient is affine in lambda(T), so ONE backward
+ *                   sweep returns (total gradient of type 2) + (total gradient of type 3) - (leakage-forcing part, which both contain),
+ *                   and for objFuncType != 1 the sum of the two infidelity gradients; the leakage gradient is that of every type.
+ * The objective values are taken against the target in every type; only gradients change.  Forward-only evaluations ignore the type.
+ * jq_update_dvds: dVds_r / dVds_i are Ntot x N, column major, like jq_update_target's arguments.  A new handle holds a copy of its
+ * target (:312-314).  jq_update_target does NOT touch dVds: "dVds follows the target while sv_type == 1" is change_target!'s rule
+ * (:1492-1506), which the bindings apply.  With type 1 dVds is kept on the host only -- type-1 callers pay nothing.
+ * jq_set_sv_type: JQ_EINVAL outside 1 .. 4.  The reference's implicit-midpoint traceobjgrad (:1042-1481) never reads sv_type or dVds,
+ * so a type other than 1 together with integrator 2 is JQ_EUNSUPPORTED from whichever of jq_set_sv_type / jq_set_integrator comes
+ * second (the refused call changes nothing).  jq_get_sv_type: the type in force (JQ_EINVAL for NULL).
+ */
+#define JQ_SV_TARGET 1
+#define JQ_SV_TERM1 2
+#define JQ_SV_TERM2 3
+#define JQ_SV_BOTH 4
+int jq_update_dvds(jq_handle *h, const double *dVds_r, const double *dVds_i);
+int jq_set_sv_type(jq_handle *h, int32_t sv_type);
+int jq_get_sv_type(const jq_handle *h);
 /* params.Hconst is mutated freely (src/ipopt_interface.jl:41-44, run_all.jl:13-15).  Kernels, operator images and LDS plan are
  * chosen from the operators' nonzero structure at jq_create; a new drift with entries outside that structure re-plans the handle
  * in place (same pointer, settings kept) -- slower kernels may result, never an error for a valid Hconst. */

@@ -70,8 +70,8 @@ struct JQTiming                           # == jq_timing
     ms_shard_max::Float64
 end
 
-# the struct layouts above are those of JQ_ABI_VERSION 5 of include/juqbox_hip.h: refuse a library built for another one
-const JQ_ABI_VERSION = 5
+# the struct layouts above are those of JQ_ABI_VERSION 6 of include/juqbox_hip.h: refuse a library built for another one
+const JQ_ABI_VERSION = 6
 function jq_check_abi()
     v = ccall((:jq_abi_version, libjq), Cint, ())
     v == JQ_ABI_VERSION || error("libjuqbox_hip has ABI version $v, hip_backend.jl was written for $JQ_ABI_VERSION")
@@ -216,6 +216,8 @@ end
 # only, so a script that switches (full weights, Neumann) <-> (Diagonal, Jacobi) in one step is valid in either direction
 # (jq_update_wmat returns at once when the matrices are the ones it has: no eigen-decomposition per call).
 function sync!(wa::AbstractWorkingArraysHIP, params::objparams)
+    # the kernels implement the trace fidelity the constructor sets (src/evalobjgrad.jl:164); the struct is mutable
+    params.pFidType == 2 || error("JQ_EUNSUPPORTED: pFidType = $(params.pFidType) -- only pFidType = 2 is implemented by the HIP backend")
     ls = params.linear_solver            # solver_id 1 = NEUMANN_SOLVER, 2 = JACOBI_SOLVER (src/linear_solvers.jl:5-8)
     max_iter, tol = solver_in_effect(ls)
     fullw = wa isa Working_Arrays_HIP && full_weights(params)
@@ -239,7 +241,19 @@ function sync!(wa::AbstractWorkingArraysHIP, params::objparams)
     end
     jqcheck(wa, ccall((:jq_update_target, libjq), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}),
                       wa.handle, params.Utarget_r, params.Utarget_i))
+    # continuation adjoints (objparams(...; dVds), set_adjoint_Sv_type!, change_target!: src/evalobjgrad.jl:312-319, :1492-1520): dVds is
+    # needed on the device only while sv_type != 1; with Working_Arrays_M_HIP a type other than 1 is refused by the library (the
+    # reference's implicit-midpoint traceobjgrad never reads it)
+    if params.sv_type != 1
+        jqcheck(wa, ccall((:jq_update_dvds, libjq), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}),
+                          wa.handle, Matrix{Float64}(params.dVds_r), Matrix{Float64}(params.dVds_i)))
+    end
+    if params.sv_type != sv_type(wa)
+        jqcheck(wa, ccall((:jq_set_sv_type, libjq), Cint, (Ptr{Cvoid}, Int32), wa.handle, params.sv_type))
+    end
 end
+# the type in force on the handle (1, 2, 3 as set_adjoint_Sv_type! sets them; 4 = both terms in one backward sweep, JQ_SV_BOTH)
+sv_type(wa::AbstractWorkingArraysHIP) = Int(ccall((:jq_get_sv_type, libjq), Cint, (Ptr{Cvoid},), wa.handle))
 
 # the new method: same signature and return tuples as src/evalobjgrad.jl:504 / :1027-1036
 function traceobjgrad(pcof0::Array{Float64,1}, params::objparams, wa::AbstractWorkingArraysHIP,

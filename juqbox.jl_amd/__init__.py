@@ -10,4 +10,4 @@ from .ipopt_interface import (eval_f_g_grad, eval_f_par, eval_g_par, eval_grad_f
                               eval_jac_g_par, intermediate_par, run_optimizer, setup_ipopt_problem,
                               traceobj_sweep)
 from .objparams import (JACOBI_SOLVER, JACOBI_SOLVER_M, NEUMANN_SOLVER, Implicit_Midpoint,  # noqa: F401
-                        Stormer_Verlet, lsolver_object, objparams)
+                        Stormer_Verlet, change_target, lsolver_object, objparams, set_adjoint_Sv_type)

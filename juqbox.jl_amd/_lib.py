@@ -15,6 +15,7 @@ c_dp = ctypes.POINTER(ctypes.c_double)
 c_i32 = ctypes.c_int32
 
 JQ_OK, JQ_EINVAL, JQ_EDIM, JQ_EUNSUPPORTED, JQ_EHIP, JQ_ENOMEM = 0, -1, -2, -3, -4, -5
+JQ_SV_TARGET, JQ_SV_TERM1, JQ_SV_TERM2, JQ_SV_BOTH = 1, 2, 3, 4      # jq_set_sv_type
 JQ_OPTION_DEFAULT = -2 ** 63      # jq_set_option: back to "not set"
 
 
@@ -41,7 +42,7 @@ class jq_timing(ctypes.Structure):
                 ("ms_allreduce", ctypes.c_double), ("ms_shard_min", ctypes.c_double), ("ms_shard_max", ctypes.c_double)]
 
 
-JQ_ABI_VERSION = 5      # the struct layouts above (include/juqbox_hip.h JQ_ABI_VERSION); load() refuses any other library
+JQ_ABI_VERSION = 6      # the struct layouts above (include/juqbox_hip.h JQ_ABI_VERSION); load() refuses any other library
 
 
 # every symbol include/juqbox_hip.h declares: name -> (restype, argtypes)
@@ -58,6 +59,9 @@ SYMBOLS = {
     "jq_set_linear_solver": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, ctypes.c_double]),
     "jq_set_integrator": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, ctypes.c_double]),
     "jq_update_target": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp]),
+    "jq_update_dvds": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp]),
+    "jq_set_sv_type": (ctypes.c_int, [ctypes.c_void_p, c_i32]),
+    "jq_get_sv_type": (ctypes.c_int, [ctypes.c_void_p]),
     "jq_update_hconst": (ctypes.c_int, [ctypes.c_void_p, c_dp]),
     "jq_update_hconst_csc": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(jq_csc)]),
     "jq_update_wmat_diag": (ctypes.c_int, [ctypes.c_void_p, c_dp]),

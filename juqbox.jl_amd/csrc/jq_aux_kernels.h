@@ -128,11 +128,16 @@ __global__ void k_init_state(double* state, long long stride, const double* __re
 //   primaryobjf = 1 - |s|^2 (:759) ; secondaryobjf = dt/2 * tinv * sum(leak partials) (:716-718)
 //   lambda(T) (init_adjoint!, :2029-2042)
 // res[sample][4] = { primaryobjf, secondaryobjf, Re s, Im s }.   grid = nslabs, block = 64
+// mode (wave-uniform; JQ_SV_*, include/juqbox_hip.h): which of the target T (vtr_img, vti_img) and dVds D (dvr_img, dvi_img: the same
+// layout; read only when mode != 1) the adjoint starts from (src/evalobjgrad.jl:815-844), with s_X = tr(X' V)/N:
+//   1: lambda(T) = s_T conj(T)/N    2: s_T conj(D)/N    3: s_D conj(T)/N    4: (s_T conj(D) + s_D conj(T))/N
+// res[] is taken against the target in every mode.  Mode 1 executes the instructions it always did, on the same data; the second trace of
+// modes 3, 4 goes through the same fixed-order sums as the first (part[3], part[4]).
 __global__ void k_terminal(double* state, long long stride, const double* __restrict__ vtr_img,
                            const double* __restrict__ vti_img, int KT, int N, int sps, int nsamples, double leak_scale,
-                           double* res)
+                           double* res, const double* __restrict__ dvr_img, const double* __restrict__ dvi_img, int mode)
 {
-    __shared__ double part[3][64];
+    __shared__ double part[5][64];
     double* st = state + (size_t)blockIdx.x * stride;
     const int lane = threadIdx.x;
     const int col = lane & 15;
@@ -141,12 +146,23 @@ __global__ void k_terminal(double* state, long long stride, const double* __rest
     for (int kk = 0; kk < KT; ++kk) {
         const double u = st[kk * 64 + lane], v = st[(KT + kk) * 64 + lane];
         const double tr = vtr_img[kk * 64 + lane], ti = vti_img[kk * 64 + lane];
-        re += u * tr - v * ti;
-        im += u * ti + v * tr;
+        re += jq_det2(u, tr, v, ti);
+        im += jq_dot2(u, ti, v, tr);
     }
     part[0][lane] = re;
     part[1][lane] = im;
     part[2][lane] = st[(JQ_STATE_ARRAYS * KT + JQ_MAXNC) * 64 + lane];
+    if (mode >= 3) {      // s_D: the same sums against the dVds image
+        double dre = 0.0, dim = 0.0;
+        for (int kk = 0; kk < KT; ++kk) {
+            const double u = st[kk * 64 + lane], v = st[(KT + kk) * 64 + lane];
+            const double tr = dvr_img[kk * 64 + lane], ti = dvi_img[kk * 64 + lane];
+            dre += jq_det2(u, tr, v, ti);
+            dim += jq_dot2(u, ti, v, tr);
+        }
+        part[3][lane] = dre;
+        part[4][lane] = dim;
+    }
     __syncthreads();
     double sre = 0.0, sim = 0.0, slk = 0.0;
     for (int l = 0; l < 64; ++l) {
@@ -160,14 +176,37 @@ __global__ void k_terminal(double* state, long long stride, const double* __rest
     }
     sre /= N;
     sim /= N;
+    double dre = 0.0, dim = 0.0;
+    if (mode >= 3) {
+        for (int l = 0; l < 64; ++l) {
+            const int c2 = l & 15;
+            const int s2 = (c2 < sps * N) ? c2 / N : -1;
+            if (s2 == sl && sl >= 0) {
+                dre += part[3][l];
+                dim += part[4][l];
+            }
+        }
+        dre /= N;
+        dim /= N;
+    }
+    // lambda(T) = a conj(X)/N  (+ s_D conj(T)/N in mode 4): a = s_D in mode 3, X = D in modes 2 and 4
+    const double are = (mode == 3) ? dre : sre, aim = (mode == 3) ? dim : sim;
+    const bool from_d = (mode == 2 || mode == 4);
+    const double *xr_img = from_d ? dvr_img : vtr_img, *xi_img = from_d ? dvi_img : vti_img;
     for (int kk = 0; kk < KT; ++kk) {
-        const double tr = vtr_img[kk * 64 + lane], ti = vti_img[kk * 64 + lane];
-        st[(2 * KT + kk) * 64 + lane] = (sl >= 0) ? (sre * tr + sim * ti) / N : 0.0;  // lambdar
-        st[(3 * KT + kk) * 64 + lane] = (sl >= 0) ? -((sim * tr - sre * ti) / N) : 0.0;  // nb = -lambdai
+        const double tr = xr_img[kk * 64 + lane], ti = xi_img[kk * 64 + lane];
+        double lr = jq_dot2(are, tr, aim, ti) / N, nb = -(jq_det2(aim, tr, are, ti) / N);
+        if (mode == 4) {
+            const double yr = vtr_img[kk * 64 + lane], yi = vti_img[kk * 64 + lane];
+            lr += jq_dot2(dre, yr, dim, yi) / N;
+            nb += -(jq_det2(dim, yr, dre, yi) / N);
+        }
+        st[(2 * KT + kk) * 64 + lane] = (sl >= 0) ? lr : 0.0;  // lambdar
+        st[(3 * KT + kk) * 64 + lane] = (sl >= 0) ? nb : 0.0;  // nb = -lambdai
     }
     const int sample = blockIdx.x * sps + sl;
     if (sl >= 0 && (col % N) == 0 && (lane >> 4) == 0 && sample < nsamples) {
-        res[(size_t)sample * 4 + 0] = 1.0 - (sre * sre + sim * sim);
+        res[(size_t)sample * 4 + 0] = 1.0 - jq_dot2(sre, sre, sim, sim);
         res[(size_t)sample * 4 + 1] = leak_scale * slk;
         res[(size_t)sample * 4 + 2] = sre;
         res[(size_t)sample * 4 + 3] = sim;
@@ -178,10 +217,13 @@ __global__ void k_terminal(double* state, long long stride, const double* __rest
 // fidelity couples them (the only cross-column coupling of an evaluation, src/evalobjgrad.jl:818, :2029-2041).
 // grid = nsamples, block = 64; sums over lanes and parts in a fixed order.
 // imr != 0: the implicit-midpoint convention of k_terminal_imr (lambda(T) = -2/N (...), the true lambda_i in slot NU)
-__global__ void k_terminal_parts(double* state, long long stride, const double* __restrict__ vtr_img,
-                                 const double* __restrict__ vti_img, int KT, int N, int parts, double leak_scale, double* res, int imr)
+// mode, dvr_img, dvi_img: see k_terminal (Stormer-Verlet only: imr != 0 is launched with mode 1)
+// (one wave per block, declared: under the default bound of 1024 threads the unrolled 64-term sums spilled to scratch)
+__global__ void __launch_bounds__(64) k_terminal_parts(double* state, long long stride, const double* __restrict__ vtr_img,
+                                 const double* __restrict__ vti_img, int KT, int N, int parts, double leak_scale, double* res, int imr,
+                                 const double* __restrict__ dvr_img, const double* __restrict__ dvi_img, int mode)
 {
-    __shared__ double part[3][64];
+    __shared__ double part[5][64];
     const int lane = threadIdx.x;
     double re = 0.0, im = 0.0, lk = 0.0;
     for (int p = 0; p < parts; ++p) {
@@ -189,14 +231,28 @@ __global__ void k_terminal_parts(double* state, long long stride, const double* 
         const double *tr = vtr_img + (size_t)p * KT * 64, *ti = vti_img + (size_t)p * KT * 64;
         for (int kk = 0; kk < KT; ++kk) {           // (columns beyond N hold zeros in state and target images)
             const double u = st[kk * 64 + lane], v = st[(KT + kk) * 64 + lane];
-            re += u * tr[kk * 64 + lane] - v * ti[kk * 64 + lane];
-            im += u * ti[kk * 64 + lane] + v * tr[kk * 64 + lane];
+            re += jq_det2(u, tr[kk * 64 + lane], v, ti[kk * 64 + lane]);
+            im += jq_dot2(u, ti[kk * 64 + lane], v, tr[kk * 64 + lane]);
         }
         lk += st[(JQ_STATE_ARRAYS * KT + JQ_MAXNC) * 64 + lane];
     }
     part[0][lane] = re;
     part[1][lane] = im;
     part[2][lane] = lk;
+    if (mode >= 3) {      // s_D: the same sums against the dVds image
+        double dre = 0.0, dim = 0.0;
+        for (int p = 0; p < parts; ++p) {
+            const double* st = state + ((size_t)blockIdx.x * parts + p) * stride;
+            const double *tr = dvr_img + (size_t)p * KT * 64, *ti = dvi_img + (size_t)p * KT * 64;
+            for (int kk = 0; kk < KT; ++kk) {
+                const double u = st[kk * 64 + lane], v = st[(KT + kk) * 64 + lane];
+                dre += jq_det2(u, tr[kk * 64 + lane], v, ti[kk * 64 + lane]);
+                dim += jq_dot2(u, ti[kk * 64 + lane], v, tr[kk * 64 + lane]);
+            }
+        }
+        part[3][lane] = dre;
+        part[4][lane] = dim;
+    }
     __syncthreads();
     double sre = 0.0, sim = 0.0, slk = 0.0;
     for (int l = 0; l < 64; ++l) {
@@ -206,21 +262,39 @@ __global__ void k_terminal_parts(double* state, long long stride, const double* 
     }
     sre /= N;
     sim /= N;
+    double dre = 0.0, dim = 0.0;
+    if (mode >= 3) {
+        for (int l = 0; l < 64; ++l) {
+            dre += part[3][l];
+            dim += part[4][l];
+        }
+        dre /= N;
+        dim /= N;
+    }
+    const double are = (mode == 3) ? dre : sre, aim = (mode == 3) ? dim : sim;
+    const bool from_d = (mode == 2 || mode == 4);
     for (int p = 0; p < parts; ++p) {
         double* st = state + ((size_t)blockIdx.x * parts + p) * stride;
-        const double *tr = vtr_img + (size_t)p * KT * 64, *ti = vti_img + (size_t)p * KT * 64;
+        const double *tr = (from_d ? dvr_img : vtr_img) + (size_t)p * KT * 64, *ti = (from_d ? dvi_img : vti_img) + (size_t)p * KT * 64;
         for (int kk = 0; kk < KT; ++kk) {
             if (imr) {
-                st[(2 * KT + kk) * 64 + lane] = -2.0 / N * (sre * tr[kk * 64 + lane] + sim * ti[kk * 64 + lane]);    // lambdar
-                st[(3 * KT + kk) * 64 + lane] = -2.0 / N * (-sre * ti[kk * 64 + lane] + sim * tr[kk * 64 + lane]);   // lambdai
+                st[(2 * KT + kk) * 64 + lane] = -2.0 / N * jq_dot2(sim, ti[kk * 64 + lane], sre, tr[kk * 64 + lane]);    // lambdar
+                st[(3 * KT + kk) * 64 + lane] = -2.0 / N * jq_det2(sim, tr[kk * 64 + lane], sre, ti[kk * 64 + lane]);   // lambdai
             } else {
-                st[(2 * KT + kk) * 64 + lane] = (sre * tr[kk * 64 + lane] + sim * ti[kk * 64 + lane]) / N;        // lambdar
-                st[(3 * KT + kk) * 64 + lane] = -((sim * tr[kk * 64 + lane] - sre * ti[kk * 64 + lane]) / N);   // nb = -lambdai
+                double lr = jq_dot2(aim, ti[kk * 64 + lane], are, tr[kk * 64 + lane]) / N;        // lambdar
+                double nb = -(jq_det2(aim, tr[kk * 64 + lane], are, ti[kk * 64 + lane]) / N);   // nb = -lambdai
+                if (mode == 4) {
+                    const double yr = vtr_img[(size_t)p * KT * 64 + kk * 64 + lane], yi = vti_img[(size_t)p * KT * 64 + kk * 64 + lane];
+                    lr += jq_dot2(dim, yi, dre, yr) / N;
+                    nb += -(jq_det2(dim, yr, dre, yi) / N);
+                }
+                st[(2 * KT + kk) * 64 + lane] = lr;
+                st[(3 * KT + kk) * 64 + lane] = nb;
             }
         }
     }
     if (lane == 0) {
-        res[(size_t)blockIdx.x * 4 + 0] = 1.0 - (sre * sre + sim * sim);
+        res[(size_t)blockIdx.x * 4 + 0] = 1.0 - jq_dot2(sre, sre, sim, sim);
         res[(size_t)blockIdx.x * 4 + 1] = leak_scale * slk;
         res[(size_t)blockIdx.x * 4 + 2] = sre;
         res[(size_t)blockIdx.x * 4 + 3] = sim;
@@ -471,8 +545,10 @@ __global__ void k_init_state_rowlane(double* state, long long nw, const double* 
 }
 
 // fidelity, leak and adjoint terminal condition per sample (thread per sample; see k_terminal)
+// (mode, dvr, dvi: see k_terminal; the dVds image has the layout of vtr / vti)
 __global__ void k_terminal_rowlane(double* state, long long nw, const double* __restrict__ vtr, const double* __restrict__ vti,
-                                   int N, int nsamples, double leak_scale, double* res)
+                                   int N, int nsamples, double leak_scale, double* res, const double* __restrict__ dvr,
+                                   const double* __restrict__ dvi, int mode)
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nsamples) return;
@@ -483,23 +559,47 @@ __global__ void k_terminal_rowlane(double* state, long long nw, const double* __
         for (int r = 0; r < 16; ++r) {
             const double u = state[base + r], v = state[(size_t)nw * 64 + base + r];
             const double tr = vtr[ic * 16 + r], ti = vti[ic * 16 + r];
-            re += u * tr - v * ti;
-            im += u * ti + v * tr;
+            re += jq_det2(u, tr, v, ti);
+            im += jq_dot2(u, ti, v, tr);
             lk += state[(size_t)(JQ_ROWLANE_ARRAYS + JQ_MAXNC) * nw * 64 + base + r];
         }
     }
     re /= N;
     im /= N;
+    double dre = 0.0, dim = 0.0;
+    if (mode >= 3) {      // s_D: the same sums against the dVds image
+        for (int ic = 0; ic < N; ++ic) {
+            const long long col = (long long)s * N + ic;
+            const size_t base = (size_t)(col >> 2) * 64 + (size_t)(col & 3) * 16;
+            for (int r = 0; r < 16; ++r) {
+                const double u = state[base + r], v = state[(size_t)nw * 64 + base + r];
+                const double tr = dvr[ic * 16 + r], ti = dvi[ic * 16 + r];
+                dre += jq_det2(u, tr, v, ti);
+                dim += jq_dot2(u, ti, v, tr);
+            }
+        }
+        dre /= N;
+        dim /= N;
+    }
+    const double are = (mode == 3) ? dre : re, aim = (mode == 3) ? dim : im;
+    const bool from_d = (mode == 2 || mode == 4);
+    const double *xr = from_d ? dvr : vtr, *xi = from_d ? dvi : vti;
     for (int ic = 0; ic < N; ++ic) {
         const long long col = (long long)s * N + ic;
         const size_t base = (size_t)(col >> 2) * 64 + (size_t)(col & 3) * 16;
         for (int r = 0; r < 16; ++r) {
-            const double tr = vtr[ic * 16 + r], ti = vti[ic * 16 + r];
-            state[(size_t)2 * nw * 64 + base + r] = (re * tr + im * ti) / N;       // lambda_r
-            state[(size_t)3 * nw * 64 + base + r] = -((im * tr - re * ti) / N);    // nb = -lambda_i
+            const double tr = xr[ic * 16 + r], ti = xi[ic * 16 + r];
+            double lr = jq_dot2(aim, ti, are, tr) / N, nb = -(jq_det2(aim, tr, are, ti) / N);
+            if (mode == 4) {
+                const double yr = vtr[ic * 16 + r], yi = vti[ic * 16 + r];
+                lr += jq_dot2(dim, yi, dre, yr) / N;
+                nb += -(jq_det2(dim, yr, dre, yi) / N);
+            }
+            state[(size_t)2 * nw * 64 + base + r] = lr;      // lambda_r
+            state[(size_t)3 * nw * 64 + base + r] = nb;      // nb = -lambda_i
         }
     }
-    res[(size_t)s * 4 + 0] = 1.0 - (re * re + im * im);
+    res[(size_t)s * 4 + 0] = 1.0 - jq_dot2(re, re, im, im);
     res[(size_t)s * 4 + 1] = leak_scale * lk;
     res[(size_t)s * 4 + 2] = re;
     res[(size_t)s * 4 + 3] = im;

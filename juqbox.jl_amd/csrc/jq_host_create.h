@@ -122,29 +122,62 @@ static int upload_operators(jq_handle* h)
     return JQ_OK;
 }
 
-static int upload_targets(jq_handle* h)
+// the images of an Ntot x N matrix pair the terminal kernels read: slab layout, lane and row-lane column layouts (where those families exist)
+static int upload_terminal_images(jq_handle* h, const double* re, const double* im, double* d_r, double* d_i, double* d_r_l, double* d_i_l,
+                                  double* d_r_r, double* d_i_r)
 {
     std::vector<double> img((size_t)h->parts * h->KT * 64);
-    slab_image(h->Utr.data(), h->Ntot, h->N, h->sps, h->KT, img.data(), h->parts);
-    HIPCHK(h, hipMemcpy(h->d_vtr, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
-    slab_image(h->Uti.data(), h->Ntot, h->N, h->sps, h->KT, img.data(), h->parts);
-    HIPCHK(h, hipMemcpy(h->d_vti, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
+    slab_image(re, h->Ntot, h->N, h->sps, h->KT, img.data(), h->parts);
+    HIPCHK(h, hipMemcpy(d_r, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
+    slab_image(im, h->Ntot, h->N, h->sps, h->KT, img.data(), h->parts);
+    HIPCHK(h, hipMemcpy(d_i, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
     if (h->lane_np > 0) {
         std::vector<double> cl((size_t)h->N * h->lane_np, 0.0);
-        column_image(h->Utr.data(), h->Ntot, h->N, h->lane_np, cl.data());
-        HIPCHK(h, hipMemcpy(h->d_vtr_l, cl.data(), cl.size() * sizeof(double), hipMemcpyHostToDevice));
+        column_image(re, h->Ntot, h->N, h->lane_np, cl.data());
+        HIPCHK(h, hipMemcpy(d_r_l, cl.data(), cl.size() * sizeof(double), hipMemcpyHostToDevice));
         std::fill(cl.begin(), cl.end(), 0.0);
-        column_image(h->Uti.data(), h->Ntot, h->N, h->lane_np, cl.data());
-        HIPCHK(h, hipMemcpy(h->d_vti_l, cl.data(), cl.size() * sizeof(double), hipMemcpyHostToDevice));
+        column_image(im, h->Ntot, h->N, h->lane_np, cl.data());
+        HIPCHK(h, hipMemcpy(d_i_l, cl.data(), cl.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     if (h->rl_npj > 0) {
         std::vector<double> cl((size_t)h->N * 16, 0.0);
-        column_image(h->Utr.data(), h->Ntot, h->N, 16, cl.data());
-        HIPCHK(h, hipMemcpy(h->d_vtr_r, cl.data(), cl.size() * sizeof(double), hipMemcpyHostToDevice));
+        column_image(re, h->Ntot, h->N, 16, cl.data());
+        HIPCHK(h, hipMemcpy(d_r_r, cl.data(), cl.size() * sizeof(double), hipMemcpyHostToDevice));
         std::fill(cl.begin(), cl.end(), 0.0);
-        column_image(h->Uti.data(), h->Ntot, h->N, 16, cl.data());
-        HIPCHK(h, hipMemcpy(h->d_vti_r, cl.data(), cl.size() * sizeof(double), hipMemcpyHostToDevice));
+        column_image(im, h->Ntot, h->N, 16, cl.data());
+        HIPCHK(h, hipMemcpy(d_i_r, cl.data(), cl.size() * sizeof(double), hipMemcpyHostToDevice));
     }
+    return JQ_OK;
+}
+
+static int upload_targets(jq_handle* h)
+{
+    return upload_terminal_images(h, h->Utr.data(), h->Uti.data(), h->d_vtr, h->d_vti, h->d_vtr_l, h->d_vti_l, h->d_vtr_r, h->d_vti_r);
+}
+
+// dVds images of ONE handle (not its embedded twin): allocated at first use, uploaded when the host copy is newer.  Handles that stay with
+// sv_type 1 never get here.
+static int upload_dvds(jq_handle* h)
+{
+    if (!h->dv_stale) return JQ_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    if (!h->dv_alloc) {      // (dev_alloc releases what an earlier, failed attempt left)
+        if ((rc = dev_alloc(h, &h->d_dvr, (size_t)h->parts * h->KT * 64))) return rc;
+        if ((rc = dev_alloc(h, &h->d_dvi, (size_t)h->parts * h->KT * 64))) return rc;
+        if (h->lane_np > 0) {
+            if ((rc = dev_alloc(h, &h->d_dvr_l, (size_t)h->N * h->lane_np))) return rc;
+            if ((rc = dev_alloc(h, &h->d_dvi_l, (size_t)h->N * h->lane_np))) return rc;
+        }
+        if (h->rl_npj > 0) {
+            if ((rc = dev_alloc(h, &h->d_dvr_r, (size_t)h->N * 16))) return rc;
+            if ((rc = dev_alloc(h, &h->d_dvi_r, (size_t)h->N * 16))) return rc;
+        }
+        h->dv_alloc = true;
+    }
+    if ((rc = upload_terminal_images(h, h->dVr.data(), h->dVi.data(), h->d_dvr, h->d_dvi, h->d_dvr_l, h->d_dvi_l, h->d_dvr_r, h->d_dvi_r)))
+        return rc;
+    h->dv_stale = false;
     return JQ_OK;
 }
 
@@ -181,7 +214,7 @@ extern "C" void jq_destroy(jq_handle* h)
     }
     (void)hipSetDevice(h->device);
     if (h->emb) jq_destroy(h->emb);
-    double** bufs[] = {&h->d_himg_dq, &h->d_cimg_dq, &h->d_cq3, &h->d_qsplit, &h->d_wlr, &h->d_cimg_l, &h->d_cimg_r, &h->d_rfreq, &h->d_wq, &h->d_pk2, &h->d_pack, &h->d_himg_r, &h->d_uinit_r, &h->d_vtr_r, &h->d_vti_r, &h->d_himg_l, &h->d_uinit_l, &h->d_vtr_l, &h->d_vti_l, &h->d_himg_c, &h->d_cimg_c, &h->d_park, &h->d_cimg, &h->d_himg,  &h->d_uimg,       &h->d_vtr,     &h->d_vti,    &h->d_tabs, &h->d_tf,   &h->d_tb,
+    double** bufs[] = {&h->d_dvr, &h->d_dvi, &h->d_dvr_l, &h->d_dvi_l, &h->d_dvr_r, &h->d_dvi_r, &h->d_himg_dq, &h->d_cimg_dq, &h->d_cq3, &h->d_qsplit, &h->d_wlr, &h->d_cimg_l, &h->d_cimg_r, &h->d_rfreq, &h->d_wq, &h->d_pk2, &h->d_pack, &h->d_himg_r, &h->d_uinit_r, &h->d_vtr_r, &h->d_vti_r, &h->d_himg_l, &h->d_uinit_l, &h->d_vtr_l, &h->d_vti_l, &h->d_himg_c, &h->d_cimg_c, &h->d_park, &h->d_cimg, &h->d_himg,  &h->d_uimg,       &h->d_vtr,     &h->d_vti,    &h->d_tabs, &h->d_tf,   &h->d_tb,
                        &h->d_cfreq, &h->d_pcof,       &h->d_stream,  &h->d_pq,     &h->d_state, &h->d_state_save,
                        &h->d_colinfo, &h->d_traces,   &h->d_R,       &h->d_grad,   &h->d_res};
     for (auto b : bufs)
@@ -361,6 +394,8 @@ static int create_dense(const jq_problem* p, jq_handle* h)
     h->Uinit.assign(p->Uinit, p->Uinit + nc);
     h->Utr.assign(p->Utarget_r, p->Utarget_r + nc);
     h->Uti.assign(p->Utarget_i, p->Utarget_i + nc);
+    h->dVr = h->Utr;      // default dVds: a copy of the target (src/evalobjgrad.jl:312-314)
+    h->dVi = h->Uti;
     h->wd.assign(p->wmat_real_diag, p->wmat_real_diag + p->Ntot);
     h->cfreq.assign(p->Cfreq, p->Cfreq + (size_t)nctrl * p->Nfreq);
 

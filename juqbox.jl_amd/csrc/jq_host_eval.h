@@ -262,9 +262,13 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
     HIPCHK(h, hipGetLastError());
     mfma_fwd = mfma;
     const double leak_scale = imr ? 0.25 * dt * (1.0 / h->T) : 0.5 * dt * (1.0 / h->T);
+    // continuation adjoints (jq_set_sv_type): only the adjoint's terminal condition knows the type -- forward-only evaluations run as type 1,
+    // the implicit-midpoint kernels have no other (plan_batch refused)
+    const int sv_mode = (adjoint && !imr) ? h->sv_type : 1;
+    if (sv_mode != 1 && (h->dv_stale || !h->dv_alloc)) return fail(h, JQ_EHIP, "internal error: sv_type != 1 without the dVds images on the device");
     if (p.term == TK_PARTS || p.term == TK_IMR_PARTS)
         hipLaunchKernelGGL(k_terminal_parts, dim3(nsamples), dim3(64), 0, s, h->d_state, h->state_stride, h->d_vtr, h->d_vti, h->KT,
-                           h->N, h->parts, leak_scale, h->d_res, p.term == TK_IMR_PARTS);
+                           h->N, h->parts, leak_scale, h->d_res, p.term == TK_IMR_PARTS, h->d_dvr, h->d_dvi, sv_mode);
     else if (p.term == TK_IMR)
         hipLaunchKernelGGL(k_terminal_imr, dim3(p.nslabs), dim3(64), 0, s, h->d_state, h->state_stride, h->d_vtr, h->d_vti, h->KT,
                            h->N, h->sps, nsamples, leak_scale, h->d_res);
@@ -273,13 +277,13 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
                            h->d_vti_r, h->N, nsamples, leak_scale, h->d_res, p.cpw);
     else if (p.term == TK_ROWLANE)
         hipLaunchKernelGGL(k_terminal_rowlane, dim3((nsamples + 63) / 64), dim3(64), 0, s, h->d_state, p.nwaves_rl, h->d_vtr_r,
-                           h->d_vti_r, h->N, nsamples, leak_scale, h->d_res);
+                           h->d_vti_r, h->N, nsamples, leak_scale, h->d_res, h->d_dvr_r, h->d_dvi_r, sv_mode);
     else if (p.term == TK_LANE)
         hipLaunchKernelGGL(p.klterm, dim3((nsamples + 63) / 64), dim3(64), 0, s, h->d_state, p.ncols, h->d_vtr_l, h->d_vti_l, h->N,
-                           nsamples, leak_scale, h->d_res);
+                           nsamples, leak_scale, h->d_res, h->d_dvr_l, h->d_dvi_l, sv_mode);
     else
         hipLaunchKernelGGL(k_terminal, dim3(p.nslabs), dim3(64), 0, s, h->d_state, h->state_stride, h->d_vtr, h->d_vti, h->KT,
-                           h->N, h->sps, nsamples, leak_scale, h->d_res);
+                           h->N, h->sps, nsamples, leak_scale, h->d_res, h->d_dvr, h->d_dvi, sv_mode);
 
     // ---- backward sweep(s) ---------------------------------------------------------------------
     // one sweep per (control group, forcing): the forced adjoint gives the total gradient, the unforced one (objFuncType != 1)

@@ -75,6 +75,7 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
     kv("embedded_twin_Ntot", num(h->emb ? h->emb->Ntot : 0));
     kv("integrator", h->integrator == 2 ? "implicit_midpoint" : "stormer_verlet", true);
     kv("linear_solver", h->solver_id == 2 ? "jacobi" : "neumann", true);
+    kv("sv_type", num(h->sv_type));
     kv("neumann_terms_or_max_iter", num(h->integrator == 2 ? h->imr_max_iter : h->m));
     kv("chunk_steps", num(h->chunk_steps));
     kv("replanned", h->replanned ? "true" : "false");

@@ -163,6 +163,8 @@ static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateH
         return fail(h, JQ_EUNSUPPORTED, "uncoupled controls (Hunc_ops): gradients with the Stormer-Verlet integrator only (the reference's "
                                         "implicit-midpoint adjoint has no term for them, src/evalobjgrad.jl:1347)");
 
+    if (adjoint && h->sv_type != 1 && h->integrator != 1) return fail(h, JQ_EUNSUPPORTED, JQ_SV_IMR_REFUSAL);
+
     p->nslabs = h->parts > 1 ? nsamples * h->parts : (nsamples + h->sps - 1) / h->sps;
     const long long ncols_used = (long long)nsamples * h->N;
     // implicit midpoint: row-lane kernels for Ntot <= 16 with N <= 4 (an evaluation's columns share one wave: the solver's convergence test)

@@ -346,13 +346,13 @@ static int select_coop_kernels(jq_handle* h, prop_kernel_t* fwd, prop_kernel_t* 
 
 // lane kernels (one lane per column), NP = padded Hilbert dimension
 typedef void (*lane_init_t)(double*, long long, const double*, int, long long);
-typedef void (*lane_term_t)(double*, long long, const double*, const double*, int, int, double, double*);
+typedef void (*lane_term_t)(double*, long long, const double*, const double*, int, int, double, double*, const double*, const double*, int);
 #define JQ_FOR_EACH_LANE(X) X(2) X(4) X(6) X(8)
 #define JQ_DECLL(np)                                                                                  \
     extern template __global__ void k_forward_lane<np>(PropArgs);                                     \
     extern template __global__ void k_backward_lane<np>(PropArgs);                                    \
     extern template __global__ void k_init_state_lane<np>(double*, long long, const double*, int, long long); \
-    extern template __global__ void k_terminal_lane<np>(double*, long long, const double*, const double*, int, int, double, double*);
+    extern template __global__ void k_terminal_lane<np>(double*, long long, const double*, const double*, int, int, double, double*, const double*, const double*, int);
 JQ_FOR_EACH_LANE(JQ_DECLL)
 #undef JQ_DECLL
 

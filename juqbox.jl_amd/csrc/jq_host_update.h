@@ -17,6 +17,11 @@ static int multi_traceobj_sweep(jq_handle* h, const double* pcof, int ncoeff, co
         return rc_;                                  \
     }
 
+// The one refusal of the continuation adjoints (jq_set_sv_type / jq_set_integrator, whichever comes second; plan_batch as the last line)
+#define JQ_SV_IMR_REFUSAL                                                                                                          \
+    "sv_type != 1 with the implicit-midpoint integrator: the reference's implicit-midpoint traceobjgrad (src/evalobjgrad.jl:1042-1481) " \
+    "never reads sv_type or dVds, so there is nothing to reproduce; set sv_type 1 or use the Stormer-Verlet integrator"
+
 extern "C" int jq_set_neumann_terms(jq_handle* h, int32_t m)
 {
     if (!h) return JQ_EINVAL;
@@ -72,6 +77,7 @@ extern "C" int jq_set_integrator(jq_handle* h, int32_t integrator_id, int32_t ma
     }
     if (integrator_id != 2) return fail(h, JQ_EUNSUPPORTED, "jq_set_integrator: 1 = Stormer-Verlet, 2 = implicit midpoint");
     if (max_iter < 1 || !(tol > 0.0)) return fail(h, JQ_EINVAL, "jq_set_integrator: implicit midpoint needs max_iter >= 1 and tol > 0");
+    if (h->sv_type != 1) return fail(h, JQ_EUNSUPPORTED, "jq_set_integrator: " JQ_SV_IMR_REFUSAL);
     if (h->huge)
         return fail(h, JQ_EUNSUPPORTED, "jq_set_integrator: the implicit-midpoint path is implemented up to Ntot = 256 (the Stormer-Verlet path has no size limit)");
     if (h->wrank > 0)
@@ -111,6 +117,82 @@ extern "C" int jq_update_target(jq_handle* h, const double* Utr, const double* U
     return upload_targets(h);
 }
 
+// every entry point added with ABI 6 keeps C++ exceptions (std::bad_alloc of the host copies ...) inside the library
+template <typename F>
+static int abi_guard(jq_handle* h, const char* name, F f)
+{
+    try {
+        return f();
+    } catch (const std::bad_alloc&) {
+        try { h->err = std::string(name) + ": out of host memory"; } catch (...) {}
+        return JQ_ENOMEM;
+    } catch (const std::exception& e) {
+        try { h->err = std::string(name) + ": " + e.what(); } catch (...) {}
+        return JQ_EHIP;
+    } catch (...) {
+        return JQ_EHIP;
+    }
+}
+
+// dVds of the handle and of its embedded twin on the device (only while a type other than 1 is in force)
+static int sync_dvds(jq_handle* h)
+{
+    if (h->sv_type == 1) return JQ_OK;
+    int rc = upload_dvds(h);
+    if (rc == JQ_OK && h->emb && (rc = upload_dvds(h->emb)) != JQ_OK) h->err = h->emb->err;
+    return rc;
+}
+
+// dVds (Ntot x N, column major).  jq_update_target leaves it alone: "dVds follows the target while sv_type == 1" is change_target!'s rule
+// (src/evalobjgrad.jl:1492-1506), i.e. the bindings'.
+extern "C" int jq_update_dvds(jq_handle* h, const double* dVds_r, const double* dVds_i)
+{
+    if (!h) return JQ_EINVAL;
+    return abi_guard(h, "jq_update_dvds", [&]() -> int {
+        if (!dVds_r || !dVds_i) return fail(h, JQ_EINVAL, "jq_update_dvds: NULL pointer");
+        if (!h->subs.empty()) return multi_forall(h, [&](jq_handle* sub) { return jq_update_dvds(sub, dVds_r, dVds_i); });
+        const size_t nc = (size_t)h->Ntot * h->N;
+        h->dVr.assign(dVds_r, dVds_r + nc);
+        h->dVi.assign(dVds_i, dVds_i + nc);
+        h->dv_stale = true;
+        if (h->emb) {
+            jq_handle* e = h->emb;
+            e->dVr.assign((size_t)e->Ntot * e->N, 0.0);
+            e->dVi.assign((size_t)e->Ntot * e->N, 0.0);
+            embed_rows(dVds_r, h->Ntot, h->N, h->emb_row, e->Ntot, e->dVr.data());
+            embed_rows(dVds_i, h->Ntot, h->N, h->emb_row, e->Ntot, e->dVi.data());
+            e->dv_stale = true;
+        }
+        return sync_dvds(h);
+    });
+}
+
+extern "C" int jq_set_sv_type(jq_handle* h, int32_t sv_type)
+{
+    if (!h) return JQ_EINVAL;
+    return abi_guard(h, "jq_set_sv_type", [&]() -> int {
+        if (sv_type < 1 || sv_type > JQ_SV_BOTH)
+            return fail(h, JQ_EINVAL, "jq_set_sv_type: 1, 2, 3 (set_adjoint_Sv_type!, src/evalobjgrad.jl:1516-1520) or 4 (JQ_SV_BOTH)");
+        if (!h->subs.empty()) {
+            const int rc = multi_forall(h, [&](jq_handle* sub) { return jq_set_sv_type(sub, sv_type); });
+            if (rc == JQ_OK) h->sv_type = sv_type;
+            return rc;
+        }
+        if (sv_type != 1 && h->integrator == 2) return fail(h, JQ_EUNSUPPORTED, "jq_set_sv_type: " JQ_SV_IMR_REFUSAL);
+        const int before = h->sv_type;
+        h->sv_type = sv_type;
+        if (h->emb) h->emb->sv_type = sv_type;
+        const int rc = sync_dvds(h);
+        if (rc != JQ_OK) {      // nothing half-applied
+            h->sv_type = before;
+            if (h->emb) h->emb->sv_type = before;
+        }
+        return rc;
+    });
+}
+
+extern "C" int jq_get_sv_type(const jq_handle* h) { return h ? h->sv_type : JQ_EINVAL; }
+
 // Re-plan a single-device handle for a new drift Hamiltonian: a fresh plan (create_impl + try_embed) from the handle's own copy
 // of the problem, the settings applied since jq_create carried over, then swapped into the caller's handle.
 static int replan(jq_handle* h, const double* Hconst)
@@ -142,6 +224,8 @@ static int replan(jq_handle* h, const double* Hconst)
         }
     }
     if (rc == JQ_OK && h->integrator == 2) rc = jq_set_integrator(n, 2, h->imr_max_iter, h->imr_tol);
+    if (rc == JQ_OK) rc = jq_update_dvds(n, h->dVr.data(), h->dVi.data());      // continuation adjoints: dVds and the type
+    if (rc == JQ_OK && h->sv_type != 1) rc = jq_set_sv_type(n, h->sv_type);
     if (rc == JQ_OK && h->wrank > 0) rc = jq_update_wmat(n, h->Wr.data(), h->Wi.data());      // full leakage weights
     if (rc != JQ_OK) {
         h->err = "jq_update_hconst: re-planning for the new Hconst failed: " + n->err;

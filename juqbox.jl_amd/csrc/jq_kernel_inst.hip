@@ -117,7 +117,7 @@ template __global__ void k_backward_rowlane<JQ_NT, true>(PropArgs);
 template __global__ void k_forward_lane<JQ_NT>(PropArgs);
 template __global__ void k_backward_lane<JQ_NT>(PropArgs);
 template __global__ void k_init_state_lane<JQ_NT>(double*, long long, const double*, int, long long);
-template __global__ void k_terminal_lane<JQ_NT>(double*, long long, const double*, const double*, int, int, double, double*);
+template __global__ void k_terminal_lane<JQ_NT>(double*, long long, const double*, const double*, int, int, double, double*, const double*, const double*, int);
 #elif JQ_VARIANT == 2
 #include "jq_coop_kernels.h"
 template __global__ void k_forward_coop<JQ_NT, JQ_BW>(PropArgs);

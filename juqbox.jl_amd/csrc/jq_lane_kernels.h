@@ -32,6 +32,14 @@
 #include "jq_kernels.h"
 #include <utility>
 
+// a b + c d and a b - c d of the terminal kernels (complex products of the trace fidelity and of lambda(T)) with their fused multiply-add
+// written out: jq_dot2 rounds a b and fuses c d, jq_det2 fuses a b and rounds c d.  Left to the compiler, which product of the sum is
+// fused depends on the surrounding code (it differed between k_terminal and the other terminal kernels, and flipped when the operands
+// became selects on the sv_type mode), and results would differ in the last bit between modes and between builds: every call below
+// passes its arguments in the order that reproduces what its kernel has always computed.
+__device__ __forceinline__ double jq_dot2(double a, double b, double c, double d) { return fma(c, d, a * b); }
+__device__ __forceinline__ double jq_det2(double a, double b, double c, double d) { return fma(a, b, -(c * d)); }
+
 // Operator images are written by earlier kernels (k_stream), never by the propagators: reading them through
 // the constant address space lets the loads move freely across the kernels' own global stores.
 typedef const __attribute__((address_space(4))) double* cmat_t;
@@ -378,9 +386,11 @@ __global__ void k_init_state_lane(double* state, long long ncols, const double* 
 }
 
 // fidelity, leak and adjoint terminal condition per sample (thread per sample; see k_terminal)
+// (mode, dvr, dvi: see k_terminal; the dVds image has the layout of vtr / vti)
 template <int NP>
 __global__ void k_terminal_lane(double* state, long long ncols, const double* __restrict__ vtr, const double* __restrict__ vti,
-                                int N, int nsamples, double leak_scale, double* res)
+                                int N, int nsamples, double leak_scale, double* res, const double* __restrict__ dvr,
+                                const double* __restrict__ dvi, int mode)
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nsamples) return;
@@ -390,22 +400,45 @@ __global__ void k_terminal_lane(double* state, long long ncols, const double* __
         for (int r = 0; r < NP; ++r) {
             const double u = state[(size_t)r * ncols + col], v = state[((size_t)NP + r) * ncols + col];
             const double tr = vtr[ic * NP + r], ti = vti[ic * NP + r];
-            re += u * tr - v * ti;
-            im += u * ti + v * tr;
+            re += jq_det2(u, tr, v, ti);
+            im += jq_dot2(u, ti, v, tr);
         }
         lk += state[((size_t)JQ_LANE_ARRAYS * NP + JQ_MAXNC) * ncols + col];
     }
     re /= N;
     im /= N;
+    double dre = 0.0, dim = 0.0;
+    if (mode >= 3) {      // s_D: the same sums against the dVds image
+        for (int ic = 0; ic < N; ++ic) {
+            const long long col = (long long)s * N + ic;
+            for (int r = 0; r < NP; ++r) {
+                const double u = state[(size_t)r * ncols + col], v = state[((size_t)NP + r) * ncols + col];
+                const double tr = dvr[ic * NP + r], ti = dvi[ic * NP + r];
+                dre += jq_det2(u, tr, v, ti);
+                dim += jq_dot2(u, ti, v, tr);
+            }
+        }
+        dre /= N;
+        dim /= N;
+    }
+    const double are = (mode == 3) ? dre : re, aim = (mode == 3) ? dim : im;
+    const bool from_d = (mode == 2 || mode == 4);
+    const double *xr = from_d ? dvr : vtr, *xi = from_d ? dvi : vti;
     for (int ic = 0; ic < N; ++ic) {
         const long long col = (long long)s * N + ic;
         for (int r = 0; r < NP; ++r) {
-            const double tr = vtr[ic * NP + r], ti = vti[ic * NP + r];
-            state[((size_t)2 * NP + r) * ncols + col] = (re * tr + im * ti) / N;      // lambda_r
-            state[((size_t)3 * NP + r) * ncols + col] = -((im * tr - re * ti) / N);   // nb = -lambda_i
+            const double tr = xr[ic * NP + r], ti = xi[ic * NP + r];
+            double lr = jq_dot2(aim, ti, are, tr) / N, nb = -(jq_det2(aim, tr, are, ti) / N);
+            if (mode == 4) {
+                const double yr = vtr[ic * NP + r], yi = vti[ic * NP + r];
+                lr += jq_dot2(dim, yi, dre, yr) / N;
+                nb += -(jq_det2(dim, yr, dre, yi) / N);
+            }
+            state[((size_t)2 * NP + r) * ncols + col] = lr;      // lambda_r
+            state[((size_t)3 * NP + r) * ncols + col] = nb;      // nb = -lambda_i
         }
     }
-    res[(size_t)s * 4 + 0] = 1.0 - (re * re + im * im);
+    res[(size_t)s * 4 + 0] = 1.0 - jq_dot2(re, re, im, im);
     res[(size_t)s * 4 + 1] = leak_scale * lk;
     res[(size_t)s * 4 + 2] = re;
     res[(size_t)s * 4 + 3] = im;

@@ -108,6 +108,13 @@ struct jq_handle {
     long long rl_stride = 0;    // doubles per [16][NPJ] operator image
     int rl_max_cols = 0;        // batches of at most this many columns use the row-lane kernels (latency regime)
     std::vector<double> Hconst, Hsym, Hanti, Uinit, Utr, Uti, wd, cfreq;
+    // Continuation adjoints (jq_set_sv_type / jq_update_dvds; src/evalobjgrad.jl:312-319, :815-844): which of the target and dVds the terminal
+    // kernels trace against and build lambda(T) from (JQ_SV_*).  dVr / dVi start as a copy of the target; their device images (the three
+    // layouts of the target's) exist only once a type other than 1 has been asked for -- dv_stale: the host copy is newer than they are.
+    int sv_type = 1;
+    std::vector<double> dVr, dVi;
+    bool dv_stale = true, dv_alloc = false;
+    double *d_dvr = nullptr, *d_dvi = nullptr, *d_dvr_l = nullptr, *d_dvi_l = nullptr, *d_dvr_r = nullptr, *d_dvi_r = nullptr;
     std::vector<double> rfreq;  // uncoupled controls (Nunc > 0): params.Rfreq; empty otherwise
     double* d_rfreq = nullptr;
     // Full leakage weights (jq_update_wmat): W = wmat_real + i wmat_imag = sum_{k < wrank} lam_k f_k f_k^H.  wrank > 0: `wd` is all

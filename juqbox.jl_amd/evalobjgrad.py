@@ -84,6 +84,15 @@ def options(**opts):
         _defaults.opts = prev
 
 
+def check_supported(params):
+    """What the reference's objparams can hold and this path does not evaluate is refused, never served by something else: the kernels
+    implement the trace fidelity pFidType == 2 (the constructor's value, src/evalobjgrad.jl:164; the struct is mutable).  Called before
+    any library call."""
+    if getattr(params, "pFidType", 2) != 2:
+        raise ValueError("JQ_EUNSUPPORTED: pFidType = %r -- only pFidType = 2 (the trace fidelity objparams sets, "
+                         "src/evalobjgrad.jl:164) is implemented" % (params.pFidType,))
+
+
 class Working_Arrays_HIP:
     """Owns the device handle for one `objparams`.  Mutable fields of `params` that scripts change
     after construction (Hconst, wmat_real, Utarget_r/i, linear_solver.max_iter) are re-synchronised
@@ -124,6 +133,7 @@ class Working_Arrays_HIP:
         csc: hand the operators over in sparse (SparseMatrixCSC) storage like the Julia binding does for use_sparse = true
         problems (default: params.use_sparse); the results are bit-identical to the dense form.
         options: {name: value} for jq_create_opts (on top of the defaults of an enclosing `with options(...)` block)."""
+        check_supported(params)
         L = _lib.load()
         if params.linear_solver.solver_id not in self.SOLVERS:
             raise ValueError("Please specify a supported linear solver")
@@ -138,6 +148,7 @@ class Working_Arrays_HIP:
         self._wd = w0 if w0.size == p.Ntot else np.zeros(p.Ntot)      # (full weights follow the creation: jq_update_wmat)
         self._utr = _f64(p.Utarget_r).copy()
         self._uti = _f64(p.Utarget_i).copy()
+        self._dvr, self._dvi, self._sv_type = self._utr, self._uti, 1      # (a new handle: dVds = target, sv_type 1)
         self._m = int(p.linear_solver.max_iter) if self.INTEGRATOR == Stormer_Verlet else 0
         self._solver = None
         nunc = getattr(p, "Nunc", 0)
@@ -197,6 +208,7 @@ class Working_Arrays_HIP:
 
     def sync_params(self):
         """Push post-construction mutations of `params` to the device (only what changed)."""
+        check_supported(self.params)
         L, p, h = _lib.load(), self.params, self.handle
         ls = p.linear_solver
         if ls.solver_id not in self.SOLVERS:
@@ -230,6 +242,16 @@ class Working_Arrays_HIP:
         if not (np.array_equal(utr, self._utr) and np.array_equal(uti, self._uti)):
             _lib.check(L.jq_update_target(h, _ptr(utr), _ptr(uti)), h)
             self._utr, self._uti = utr.copy(), uti.copy()
+        # continuation adjoints: dVds (needed on the device only while sv_type != 1), then the type
+        sv = int(getattr(p, "sv_type", 1))
+        if sv != 1:
+            dvr, dvi = _f64(p.dVds_r), _f64(p.dVds_i)
+            if not (np.array_equal(dvr, self._dvr) and np.array_equal(dvi, self._dvi)):
+                _lib.check(L.jq_update_dvds(h, _ptr(dvr), _ptr(dvi)), h)
+                self._dvr, self._dvi = dvr.copy(), dvi.copy()
+        if sv != self._sv_type:
+            _lib.check(L.jq_set_sv_type(h, sv), h)
+            self._sv_type = sv
 
     def set_option(self, name, value=None):
         """jq_set_option: change one option of this handle (value None: back to "not set"); plan-shaping options re-plan it"""

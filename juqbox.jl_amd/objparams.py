@@ -46,7 +46,7 @@ class objparams:
     def __init__(self, Ne, Ng, T, nsteps, *, Uinit, Utarget, Cfreq, Rfreq, Hconst,
                  Hsym_ops=(), Hanti_ops=(), Hunc_ops=(), objFuncType=1, leak_ubound=1.0e-3,
                  wmatScale=1.0, use_sparse=False, linear_solver=None, Integrator=Stormer_Verlet,
-                 use_custom_forbidden=False, forb_states=None, forb_weights=None):
+                 use_custom_forbidden=False, forb_states=None, forb_weights=None, dVds=None):
         self.Ne = [int(x) for x in Ne]
         self.Ng = [int(x) for x in Ng]
         self.Nt = [a + b for a, b in zip(self.Ne, self.Ng)]
@@ -93,6 +93,14 @@ class objparams:
         self.Uinit = np.asfortranarray(Uinit)
         self.Utarget_r = np.asfortranarray(Utarget.real.copy())
         self.Utarget_i = np.asfortranarray(Utarget.imag.copy())
+        # continuation adjoints (:312-319): without dVds a copy of the target and sv_type 1, with it sv_type 2
+        if dVds is None or np.size(dVds) == 0:
+            dV, sv_type = Utarget, 1
+        else:
+            dV, sv_type = np.asarray(dVds, dtype=np.complex128), 2
+            assert dV.shape == Utarget.shape, "size(dVds) == size(Utarget)"        # :316
+        self.dVds_r = np.asfortranarray(dV.real.copy())
+        self.dVds_i = np.asfortranarray(dV.imag.copy())
         self.use_bcarrier = True      # :208
         self.kpar = 1                 # :205
         self.tik0 = 0.01              # :202
@@ -151,7 +159,7 @@ class objparams:
         self.quiet = False
         self.save_pcof_hist = False
         self.pcof_hist = []
-        self.sv_type = 1
+        self.sv_type = sv_type        # 1, 2, 3: set_adjoint_Sv_type; 4 (both terms in one backward sweep, JQ_SV_BOTH): by assignment only
         if Integrator not in (Stormer_Verlet, Implicit_Midpoint):
             raise NotImplementedError("Integrator must be Stormer_Verlet (1) or Implicit_Midpoint (2)")
         self.Integrator_id = Integrator
@@ -175,3 +183,20 @@ class objparams:
         for j in range(2, self.Ntot + 1):
             s[j - 1] = 0.01 * (10.0 ** (j - 2))
         return s
+
+
+def change_target(params, new_Utarget):
+    """change_target!(params, new_Utarget): src/evalobjgrad.jl:1492-1506.  dVds follows the target only while sv_type == 1."""
+    U = np.asarray(new_Utarget, dtype=np.complex128)
+    assert U.shape == (params.N + params.Nguard, params.N), "size(new_Utarget) must be (Ntot, N)"      # :1496
+    params.Utarget_r = np.asfortranarray(U.real.copy())
+    params.Utarget_i = np.asfortranarray(U.imag.copy())
+    if params.sv_type == 1:
+        params.dVds_r = np.asfortranarray(U.real.copy())
+        params.dVds_i = np.asfortranarray(U.imag.copy())
+
+
+def set_adjoint_Sv_type(params, new_sv_type=1):
+    """set_adjoint_Sv_type!(params, new_sv_type = 1): src/evalobjgrad.jl:1516-1520 ("for continuation only")."""
+    assert new_sv_type in (1, 2, 3), "new_sv_type must be 1, 2, or 3"      # :1517
+    params.sv_type = int(new_sv_type)
