@@ -41,7 +41,8 @@ extern "C" {
  * 5 = per-handle options instead of environment variables (jq_create_opts, jq_create_multi_opts, jq_set_option, jq_get_option),
  *     jq_timing.reserved renamed kernel_variant, jq_rccl_world_size; no size limits on Ntot, the number of control Hamiltonians or
  *     the rank of a full weight matrix; full leakage weights with the Jacobi solver;
- * 6 = continuation adjoints: jq_update_dvds, jq_set_sv_type, jq_get_sv_type (params.dVds_r / dVds_i / sv_type). */
+ * 6 = continuation adjoints: jq_update_dvds, jq_set_sv_type, jq_get_sv_type (params.dVds_r / dVds_i / sv_type); later, with no
+ *     change of a layout or of an existing entry point: jq_s_uniform (host-only structure test). */
 #define JQ_ABI_VERSION 6
 
 #define JQ_MAX_CONTROLS 16 /* control Hamiltonians the fast kernels hold in registers; more: cooperative kernels (no limit)    */
@@ -384,6 +385,15 @@ int jq_traceobj_sweep(jq_handle *h, const double *pcof, int32_t ncoeff, const do
  * current settings.  jq_last_timing() reports which one actually ran.
  */
 int jq_plan_info(const jq_handle *h, char *buf, int32_t buflen);
+
+/*
+ * The test behind "s_uniform" of jq_plan_info, on its own (host only; no handle, no device): 1 if the S image of every time point,
+ * sum_k q_k(t) Hanti_k, repeats its first 16-row block on a 4 x 4 x n space -- every Hanti_k (Ntot x Ntot, column-major, one after the
+ * other) has the same 4 x 4 diagonal blocks and the same (i, i +- 4) couplings in every 16-row block and one (i, i +- 16) coupling per
+ * pair of neighbouring blocks, as Hanti_k = a_k - a_k' has -- 0 if not (or if an operator lacks the 4 x 4 x n structure), JQ_EINVAL for
+ * Ntot that is not a multiple of 16 up to 128.  The three-slab quad-layout kernels then read a compact S operand (option s_compact).
+ */
+int jq_s_uniform(const double *Hanti_ops, int32_t Ntot, int32_t Ncoupled);
 
 /* ---- measurement -----------------------------------------------------------------------------*/
 int jq_last_timing(const jq_handle *h, jq_timing *t);

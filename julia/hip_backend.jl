@@ -195,6 +195,12 @@ function plan_info(wa::AbstractWorkingArraysHIP)      # JSON text: structure, co
     ccall((:jq_plan_info, libjq), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Int32), wa.handle, buf, n + 1)
     return String(buf[1:n])
 end
+# the structure test behind "s_uniform" of plan_info (host only): do the S images of these Hanti_ops repeat their first 16-row block?
+function s_uniform(Hanti_ops)
+    Ntot = size(Hanti_ops[1], 1)
+    Ha = reduce(hcat, [vec(Matrix{Float64}(h)) for h in Hanti_ops])
+    return ccall((:jq_s_uniform, libjq), Cint, (Ptr{Float64}, Int32, Int32), Ha, Ntot, length(Hanti_ops)) == 1
+end
 handle_device(wa::AbstractWorkingArraysHIP) = ccall((:jq_handle_device, libjq), Cint, (Ptr{Cvoid},), wa.handle)
 
 # What the reference's solver WOULD use.  lsolver_object's `solve` closure captures max_iter (and tol) when it is constructed

@@ -28,6 +28,7 @@ static int dev_grow(jq_handle* h, T** p, size_t* cap, size_t need)
     return rc;
 }
 
+static bool hanti_s_uniform(const double* Hanti, int Ntot, int NT, int Nc);      // (jq_host_select.h)
 static int upload_operators(jq_handle* h)
 {
     const size_t nn = (size_t)h->Ntot * h->Ntot;
@@ -445,6 +446,7 @@ static int create_dense(const jq_problem* p, jq_handle* h)
         // trace image layout per control: 0 block diagonal, 1 band BW, 2 band BW without the diagonal blocks
         for (int q = 0; q < h->Nc && h->BW == JQ_BW_T4; ++q)
             h->bw_trace[q] = t4_mode(h->Hsym.data() + q * nn, h->Ntot) | t4_mode(h->Hanti.data() + q * nn, h->Ntot);
+        h->s_uniform = h->BW == JQ_BW_T4 && hanti_s_uniform(h->Hanti.data(), h->Ntot, h->NT, h->Nc);
         for (int q = 0; q < h->Nc && h->BW != JQ_BW_T4; ++q) {
             if (h->bw_trace[q] == 0 || h->BW == 0)
                 h->bw_trace[q] = (h->BW == 0) ? 1 : 0;

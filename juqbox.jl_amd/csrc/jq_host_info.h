@@ -79,6 +79,10 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
     kv("neumann_terms_or_max_iter", num(h->integrator == 2 ? h->imr_max_iter : h->m));
     kv("chunk_steps", num(h->chunk_steps));
     kv("replanned", h->replanned ? "true" : "false");
+    // uniform S images (4 x 4 x n plans; the embedded twin's where it serves the batches) and the option that lets the three-slab quad-layout
+    // kernels use the compact S operand then
+    kv("s_uniform", (h->emb ? h->emb : h)->s_uniform ? "true" : "false");
+    kv("s_compact", num(hh->opt.get(O_S_COMPACT)));
     // kernel families in the order plan_batch considers them for a Stormer-Verlet / Neumann batch (the embedded twin, if any, serves
     // the batches beyond the row-lane / lane range with ITS plan)
     std::string fam = "[";
@@ -153,6 +157,16 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
         buf[n] = 0;
     }
     return (int)o.size();
+}
+
+// the structure test behind "s_uniform" on its own (host only, no device): Hanti_ops as jq_problem passes them
+extern "C" int jq_s_uniform(const double* Hanti_ops, int32_t Ntot, int32_t Ncoupled)
+{
+    if (!Hanti_ops || Ntot < 1 || Ntot > 128 || Ntot % 16 != 0 || Ncoupled < 1) return JQ_EINVAL;
+    const size_t nn = (size_t)Ntot * Ntot;
+    for (int q = 0; q < Ncoupled; ++q)
+        if (block_band(Hanti_ops + q * nn, Ntot) > 1 || !t4_structure(Hanti_ops + q * nn, Ntot)) return 0;
+    return hanti_s_uniform(Hanti_ops, Ntot, Ntot / 16, Ncoupled) ? 1 : 0;
 }
 
 extern "C" int jq_last_timing(const jq_handle* h, jq_timing* t)

@@ -65,7 +65,9 @@ static int select_kernels(jq_handle* h, prop_kernel_t* fwd, prop_kernel_t* bwd)
     extern template __global__ void k_forward<nt, JQ_BW_T4Q, 3, false>(PropArgs);    \
     extern template __global__ void k_backward<nt, JQ_BW_T4Q, 3, false>(PropArgs);   \
     extern template __global__ void k_backward<nt, JQ_BW_T4Q, 3, false, false, true>(PropArgs);   \
-    extern template __global__ void k_backward<nt, JQ_BW_T4Q, 3, false, false, true, true>(PropArgs);
+    extern template __global__ void k_backward<nt, JQ_BW_T4Q, 3, false, false, true, true>(PropArgs);   \
+    extern template __global__ void k_forward<nt, JQ_BW_T4Q, 3, false, false, false, true>(PropArgs);   \
+    extern template __global__ void k_backward<nt, JQ_BW_T4Q, 3, false, false, true, true, true>(PropArgs);
 JQ_DECLQ(1) JQ_DECLQ(2) JQ_DECLQ(3) JQ_DECLQ(4) JQ_DECLQ(5) JQ_DECLQ(6) JQ_DECLQ(7) JQ_DECLQ(8)
 #undef JQ_DECLQ
 template <int NT, bool MODD, int NS, bool WLR = false, bool DN = false> __global__ void k_forward_cq(PropArgs);    // jq_cq_kernels.h (own translation units); NS: column quads per workgroup; WLR: full (real, low-rank) leakage weights
@@ -121,6 +123,42 @@ static bool ctrl_per_subsystem(const jq_handle* h)
 {
     for (int q = 0; q < h->Nc; ++q)
         if (h->bw_trace[q] != (1 << q)) return false;
+    return true;
+}
+// Uniform S: the S image of every time point, c sum_k q_k(t) Hanti_k, repeats its block 0 -- what Juqbox's usual set-up Hanti_k = a_k - a_k'
+// gives on a 4 x 4 x n space (row = 16 mt + 4 b + i): the 4 x 4 diagonal blocks are those of the fastest subsystem in every row group, the
+// +-4 couplings those of the middle one in every 16-row block, the +-16 couplings one number per pair of neighbouring blocks.  Tested on
+// the JQ_BW_T4 image of each Hanti_k, entry by entry and BIT by bit (k_stream forms every entry of S with the same operations from the
+// same entries of the Hanti images: equal inputs give equal entries), in exactly the form the compact operand of the kernels relies on
+// (jq_kernels.h OpS):
+//   (1) the A operand (64 doubles) of every 16-row block equals that of block 0;
+//   (2) the lane-shift coefficients (c0, c1) of every row of a block equal those of the same row of block 0;
+//   (3) the neighbour-block coefficients c2 (blocks mt > 0) and c3 (blocks mt < NT - 1) are the same in all 16 rows of a block.
+static bool s_image_uniform(const double* img, int NT)
+{
+    auto same = [](double x, double y) { return memcmp(&x, &y, sizeof x) == 0; };
+    const double* cf = img + (size_t)4 * NT * JQ_T4_TILE;
+    for (int mt = 0; mt < NT; ++mt) {
+        for (int e = 0; e < 64; ++e)
+            if (!same(img[mt * 64 + e], img[e])) return false;
+        for (int g = 0; g < 4; ++g)
+            for (int r = 0; r < 4; ++r) {
+                const double* rec = cf + mt * 64 + JQ_T4_CIDX(g, r, 0);
+                if (!same(rec[0], cf[JQ_T4_CIDX(g, r, 0)]) || !same(rec[1], cf[JQ_T4_CIDX(g, r, 1)])) return false;
+                if (mt > 0 && !same(rec[2], cf[mt * 64 + 2])) return false;
+                if (mt + 1 < NT && !same(rec[3], cf[mt * 64 + 3])) return false;
+            }
+    }
+    return true;
+}
+// ... of all Nc antisymmetric control operators (column-major Ntot x Ntot each) of a 4 x 4 x n plan with NT 16-row blocks
+static bool hanti_s_uniform(const double* Hanti, int Ntot, int NT, int Nc)
+{
+    std::vector<double> img((size_t)JQ_T4_ELEMS(NT));
+    for (int q = 0; q < Nc; ++q) {
+        tile_image(Hanti + (size_t)q * Ntot * Ntot, Ntot, NT, JQ_BW_T4, img.data());
+        if (!s_image_uniform(img.data(), NT)) return false;
+    }
     return true;
 }
 static int select_cq_kernels(jq_handle* h, bool fwd2, int bwd_nr, bool wlr, bool dense, prop_kernel_t* fwd, prop_kernel_t* bwd)      // bwd_nr: workgroups per quad in the backward sweep (0 / 1: one); wlr: full (real, low-rank) leakage weights; dense: no structure, NT = 2
@@ -244,10 +282,13 @@ static int select_quad_kernels(jq_handle* h, int spw, prop_kernel_t* fwd, prop_k
     const bool uni = (h->N % 4 == 0 || h->parts > 1) && !h->opt.on(O_NO_UNI);
     // ... and its ORD variant when control q acts on subsystem q only (like the cooperative-quad kernels, select_cq_kernels)
     const bool ord = uni && h->Nc >= 2 && h->Nc <= 3 && !h->opt.on(O_NO_ORD) && ctrl_per_subsystem(h);
+    // ... and, three slabs per workgroup, the SC variants when the plan's S images are uniform (s_image_uniform; option s_compact=0: the kernels
+    // with the full operand, bit-identical): the forward kernel, and the ORD backward kernel
+    const bool sc = spw == 3 && h->s_uniform && h->opt.on(O_S_COMPACT);
 #define JQ_PICKQ(nt)                                                                                                                             \
     if (h->NT == nt) {                                                                                                                           \
-        *fwd = spw == 3 ? k_forward<nt, JQ_BW_T4Q, 3, false> : spw == 2 ? k_forward<nt, JQ_BW_T4Q, 2, false> : k_forward<nt, JQ_BW_T4Q, 1, false>;     \
-        *bwd = spw == 3 ? (ord ? k_backward<nt, JQ_BW_T4Q, 3, false, false, true, true>                                                       \
+        *fwd = spw == 3 ? (sc ? k_forward<nt, JQ_BW_T4Q, 3, false, false, false, true> : k_forward<nt, JQ_BW_T4Q, 3, false>) : spw == 2 ? k_forward<nt, JQ_BW_T4Q, 2, false> : k_forward<nt, JQ_BW_T4Q, 1, false>;     \
+        *bwd = spw == 3 ? (ord ? (sc ? k_backward<nt, JQ_BW_T4Q, 3, false, false, true, true, true> : k_backward<nt, JQ_BW_T4Q, 3, false, false, true, true>) \
                                 : uni ? k_backward<nt, JQ_BW_T4Q, 3, false, false, true> : k_backward<nt, JQ_BW_T4Q, 3, false>)                 \
                         : spw == 2 ? k_backward<nt, JQ_BW_T4Q, 2, false> : k_backward<nt, JQ_BW_T4Q, 1, false>;  \
         return JQ_OK;                                                                                                                            \

@@ -567,6 +567,10 @@ __device__ __forceinline__ const d4* t4q_c(const double* mat, int lane)
     return (const d4*)(mat - lane + 4 * NT * JQ_T4_TILE + JQ_T4_CIDX(lane >> 4, (lane >> 2) & 3, 0));
 }
 __device__ __forceinline__ d4 t4q_cload(const d4* cf, int mt) { return cf[mt * 16]; }
+// Uniform S (s_image_uniform): the halves of a row's record -- (c0, c1) is the same in every block, (c2, c3) the same on every lane
+__device__ __forceinline__ d2 t4s_c01(const d4* cf) { return ((const d2*)cf)[0]; }
+__device__ __forceinline__ d2 t4s_c23(const d4* cf, int mt) { return ((const d2*)(cf + mt * 16))[1]; }
+__device__ __forceinline__ d4 t4s_c(const d2& c01, const d2& c23) { return (d4){c01[0], c01[1], c23[0], c23[1]}; }
 // one 16-row block
 template <int NT, bool ZEROC, int MODE>
 __device__ __forceinline__ void t4q_block(Arr<NT>& D, const Arr<NT>& C, const Arr<NT>& x, int mt, double a, const d4& c, double& xold)
@@ -648,7 +652,9 @@ struct T4qNoHook {
 };
 // (HOOK: called once per 16-row block with the block's two lane-shifted copies of x -- products with single-subsystem operators
 //  that only need those, e.g. the trace products of a control of the middle subsystem, ride along without shifts of their own)
-template <int NT, int NP, bool Z0, bool Z1, bool Z2, int SH = 0, typename HOOK = T4qNoHook>      // SH: bit k = operator k is a K image and takes the folded shift
+// SCM: bit k = operator k is an S image of a plan with a UNIFORM S (jq_host_select.h s_image_uniform): its A operand and its lane-shift
+// coefficients (c0, c1) are those of block 0 for every block, fetched once in front of the pass; a block reads its (c2, c3) only
+template <int NT, int NP, bool Z0, bool Z1, bool Z2, int SH = 0, typename HOOK = T4qNoHook, int SCM = 0>      // SH: bit k = operator k is a K image and takes the folded shift
 __device__ __forceinline__ void mm_t4q_multi(Arr<NT>& D0, const Arr<NT>& C0, const double* m0, Arr<NT>& D1, const Arr<NT>& C1,
                                              const double* m1, Arr<NT>& D2, const Arr<NT>& C2, const double* m2, const Arr<NT>& x,
                                              double sh0 = 0.0, double sh1 = 0.0, double sh2 = 0.0, const double* wsr = nullptr,
@@ -658,6 +664,14 @@ __device__ __forceinline__ void mm_t4q_multi(Arr<NT>& D0, const Arr<NT>& C0, con
     const double* ma[3] = {t4q_a(m0, lane), t4q_a(m1, lane), t4q_a(NP > 2 ? m2 : m1, lane)};
     const d4* cf[3] = {t4q_c<NT>(m0, lane), t4q_c<NT>(m1, lane), t4q_c<NT>(NP > 2 ? m2 : m1, lane)};
     double xold = 0.0;
+    double as[3];
+    d2 cs[3];
+#pragma unroll
+    for (int k = 0; k < NP; ++k)
+        if ((SCM >> k) & 1) {
+            as[k] = ma[k][0];
+            cs[k] = t4s_c01(cf[k]);
+        }
 #pragma unroll
     for (int mt = 0; mt < NT; ++mt) {
         // (operands of THIS block only: a one-block-ahead prefetch like mm_t4q's costs 10 NP registers, which the twelve-wave
@@ -666,8 +680,13 @@ __device__ __forceinline__ void mm_t4q_multi(Arr<NT>& D0, const Arr<NT>& C0, con
         d4 c[3];
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
-            a[k] = ma[k][mt * 64];
-            c[k] = t4q_cload(cf[k], mt);
+            if ((SCM >> k) & 1) {
+                a[k] = as[k];
+                c[k] = t4s_c(cs[k], t4s_c23(cf[k], mt));
+            } else {
+                a[k] = ma[k][mt * 64];
+                c[k] = t4q_cload(cf[k], mt);
+            }
         }
         if constexpr (SH != 0) {      // (shift folded into the A operands of the K images, see mm_t4q)
             const double w = wsr[16 * mt];
@@ -708,18 +727,18 @@ __device__ __forceinline__ void mm_t4q_multi(Arr<NT>& D0, const Arr<NT>& C0, con
         __builtin_amdgcn_sched_barrier(0);
     }
 }
-template <int NT, bool Z0, bool Z1, int SH = 0>
+template <int NT, bool Z0, bool Z1, int SH = 0, int SCM = 0>
 __device__ __forceinline__ void mm_t4q2(Arr<NT>& D0, const Arr<NT>& C0, const double* m0, Arr<NT>& D1, const Arr<NT>& C1,
                                         const double* m1, const Arr<NT>& x, double sh0 = 0.0, double sh1 = 0.0, const double* wsr = nullptr)
 {
-    mm_t4q_multi<NT, 2, Z0, Z1, true, SH>(D0, C0, m0, D1, C1, m1, D1, C1, m1, x, sh0, sh1, 0.0, wsr);
+    mm_t4q_multi<NT, 2, Z0, Z1, true, SH, T4qNoHook, SCM>(D0, C0, m0, D1, C1, m1, D1, C1, m1, x, sh0, sh1, 0.0, wsr);
 }
-template <int NT, bool Z0, bool Z1, bool Z2, int SH = 0>
+template <int NT, bool Z0, bool Z1, bool Z2, int SH = 0, int SCM = 0>
 __device__ __forceinline__ void mm_t4q3(Arr<NT>& D0, const Arr<NT>& C0, const double* m0, Arr<NT>& D1, const Arr<NT>& C1,
                                         const double* m1, Arr<NT>& D2, const Arr<NT>& C2, const double* m2, const Arr<NT>& x,
                                         double sh0 = 0.0, double sh1 = 0.0, double sh2 = 0.0, const double* wsr = nullptr)
 {
-    mm_t4q_multi<NT, 3, Z0, Z1, Z2, SH>(D0, C0, m0, D1, C1, m1, D2, C2, m2, x, sh0, sh1, sh2, wsr);
+    mm_t4q_multi<NT, 3, Z0, Z1, Z2, SH, T4qNoHook, SCM>(D0, C0, m0, D1, C1, m1, D2, C2, m2, x, sh0, sh1, sh2, wsr);
 }
 // the same with the operator in registers (the m + 1 products of a Horner chain share it: no LDS latency at their heads)
 template <int NT>
@@ -749,6 +768,52 @@ __device__ __forceinline__ void mm_t4q_regs(Arr<NT>& D, const Arr<NT>& C, const 
     double xold = 0.0;
 #pragma unroll
     for (int mt = 0; mt < NT; ++mt) t4q_block<NT, false, JQ_T4_DIAG | JQ_T4_RTERMS | JQ_T4_MTERMS>(D, C, x, mt, op.a[mt], op.c[mt], xold);
+}
+
+// Uniform S (the usual Juqbox set-up Hanti_k = a_k - a_k': s_image_uniform, jq_host_select.h): every 16-row block of an S image has the
+// SAME A operand and the same (c0, c1) per row, and a block's (c2, c3) are the same on every lane.  The operand of a product is then
+// 3 + 2 NT doubles instead of 5 NT: one A register, one (c0, c1) pair, (c2, c3) per block -- every value IS the image entry the full
+// operand would have read, the FMAs and MFMAs and their order are those of mm_t4q / mm_t4q_regs: bit-identical results.
+template <int NT>
+struct OpS {
+    double a;
+    d2 c;
+    d2 m[NT];      // lane-uniform
+};
+template <int NT>
+__device__ __forceinline__ void t4s_load(OpS<NT>& op, const double* mat)
+{
+    const int lane = threadIdx.x & 63;
+    const d4* cf = t4q_c<NT>(mat, lane);
+    op.a = t4q_a(mat, lane)[0];
+    op.c = t4s_c01(cf);
+#pragma unroll
+    for (int mt = 0; mt < NT; ++mt) op.m[mt] = t4s_c23(cf, mt);
+}
+template <int NT>
+__device__ __forceinline__ void mm_t4s_regs(Arr<NT>& D, const Arr<NT>& C, const OpS<NT>& op, const Arr<NT>& x)
+{
+    double xold = 0.0;
+#pragma unroll
+    for (int mt = 0; mt < NT; ++mt)
+        t4q_block<NT, false, JQ_T4_DIAG | JQ_T4_RTERMS | JQ_T4_MTERMS>(D, C, x, mt, op.a, t4s_c(op.c, op.m[mt]), xold);
+}
+// one product with the operand from LDS (mm_t4q's one-block-ahead prefetch of what still differs per block)
+template <int NT, bool ZEROC>
+__device__ __forceinline__ void mm_t4s(Arr<NT>& D, const Arr<NT>& C, const double* mat, const Arr<NT>& x)
+{
+    const int lane = threadIdx.x & 63;
+    const d4* cf = t4q_c<NT>(mat, lane);
+    const double a = t4q_a(mat, lane)[0];
+    const d2 c01 = t4s_c01(cf);
+    d2 m_cur = t4s_c23(cf, 0);
+    double xold = 0.0;
+#pragma unroll
+    for (int mt = 0; mt < NT; ++mt) {
+        const d2 m = m_cur;
+        if (mt + 1 < NT) m_cur = t4s_c23(cf, mt + 1);
+        t4q_block<NT, ZEROC, JQ_T4_DIAG | JQ_T4_RTERMS | JQ_T4_MTERMS>(D, C, x, mt, a, t4s_c(c01, m), xold);
+    }
 }
 
 template <int NT, int BW, bool ZEROC, bool SD = false>
@@ -1586,7 +1651,8 @@ __device__ __forceinline__ void jacobi_add(Arr<NT>& out, const Arr<NT>& bpa, con
 
 // REGOP (quad layout): the operator of the chain's m + 1 products is held in 10 NT registers (OpQ); false: every product reads it from
 // LDS again (mm_t4q) -- 60 registers less inside the recurrence at NT = 6
-template <int NT, int BW, bool JAC, bool REGOP = true>
+// SC (quad layout, Neumann): S is uniform -- the operand is an OpS (3 + 2 NT doubles)
+template <int NT, int BW, bool JAC, bool REGOP = true, bool SC = false>
 __device__ __forceinline__ void horner_add(Arr<NT>& out, const Arr<NT>& bpa, const Arr<NT>& A, const double* S, int m,
                                            Arr<NT>& Ya, Arr<NT>& Yb, double jacobi_tol2, int ncol, int jac_wg = -1)
 {
@@ -1599,6 +1665,23 @@ __device__ __forceinline__ void horner_add(Arr<NT>& out, const Arr<NT>& bpa, con
         return;
     }
     int rem = m - 1;  // Horner updates before the final product
+    if constexpr (SC) {
+        static_assert(!SC || (BW == JQ_BW_T4Q && !JAC), "SC: quad layout, Neumann solver");
+        if (rem == 0) {
+            mm_t4s<NT, false>(out, bpa, S, A);
+            return;
+        }
+        OpS<NT> op;
+        t4s_load(op, S);
+        mm_t4s_regs(Ya, A, op, A);
+        for (--rem; rem >= 2; rem -= 2) {      // (two products per iteration: see below)
+            mm_t4s_regs(Ya, A, op, Ya);
+            mm_t4s_regs(Ya, A, op, Ya);
+        }
+        if (rem > 0) mm_t4s_regs(Ya, A, op, Ya);
+        mm_t4s_regs(out, bpa, op, Ya);
+        return;
+    }
     if (rem == 0) {
         mm_c<NT, BW>(out, bpa, S, A);
         return;
@@ -1729,11 +1812,13 @@ __device__ __forceinline__ void a_unpark(Arr<NT>& a, const double* park)
 // FUSE (quad layout only): bit 0 = K05 u with S0 u in one pass, bit 1 = S05 v05 with K0 v05 and K1 v05 in one pass
 // FOLD (quad layout, one sample per wave): `ceps` is the per-lane MASKED shift (+c eps on the lanes that hold the diagonal of the MFMA's
 // A operand, 0 elsewhere; 0 everywhere without a shift) and every product with a K image folds it into its operand (mm_t4q SH)
-template <int NT, int BW, bool JAC, int FUSE = 0, bool FOLD = false, bool REGOP = true, bool TERMS = false, typename RING = RingT<BW == JQ_BW_T4Q>>
+// SC (quad layout, fused passes): the S images are uniform (s_image_uniform) -- their products take the compact operand (OpS, mm_t4s)
+template <int NT, int BW, bool JAC, int FUSE = 0, bool FOLD = false, bool REGOP = true, bool TERMS = false, typename RING = RingT<BW == JQ_BW_T4Q>, bool SC = false>
 __device__ __forceinline__ void sv_state(RING& p, const PropArgs& a, bool active, double ceps, const double* ws, int g,
                                          const Arr<NT>& u, Arr<NT>& v, Arr<NT>& unew, Arr<NT>& vN, Arr<NT>& A, Arr<NT>& Ya,
                                          Arr<NT>& Yb)
 {
+    static_assert(!SC || (BW == JQ_BW_T4Q && !JAC && FUSE == 3 && REGOP), "SC: the fused quad-layout step");
     if constexpr (BW == JQ_BW_T4Q && !JAC && FUSE != 0) {
         // Quad layout (always window staging: every image of the step is resident, the order of the uses is free): the products
         // that share a right-hand side are made in ONE pass over the blocks so that they share its lane shifts -- K05 u with
@@ -1745,10 +1830,10 @@ __device__ __forceinline__ void sv_state(RING& p, const PropArgs& a, bool active
         if (active) {
             if constexpr (FOLD) {
                 static_assert(!FOLD || (FUSE & 3) == 3 || FUSE == 0, "FOLD: fused or generic path");
-                mm_t4q2<NT, true, false, 1>(A, A, M0, unew, u, M1, u, ceps, 0.0, ws + g);
+                mm_t4q2<NT, true, false, 1, SC ? 2 : 0>(A, A, M0, unew, u, M1, u, ceps, 0.0, ws + g);
             } else {
             if constexpr (FUSE & 1) {
-                mm_t4q2<NT, true, false>(A, A, M0, unew, u, M1, u);        // A = c K05 u ;  unew = u + c S0 u
+                mm_t4q2<NT, true, false, 0, SC ? 2 : 0>(A, A, M0, unew, u, M1, u);        // A = c K05 u ;  unew = u + c S0 u
             } else {
                 mm_z<NT, BW>(A, M0, u);
                 mm_c<NT, BW>(unew, u, M1, u);
@@ -1758,18 +1843,19 @@ __device__ __forceinline__ void sv_state(RING& p, const PropArgs& a, bool active
         }
         M0 = p.template next_ks<1, 1>();                    // S05
         if (active) {
-            mm_c<NT, BW>(A, A, M0, v);                                 // A = c (K05 u + S05 v)
+            if constexpr (SC) mm_t4s<NT, false>(A, A, M0, v);
+            else mm_c<NT, BW>(A, A, M0, v);                            // A = c (K05 u + S05 v)
             a_add(v, A);
-            horner_add<NT, BW, JAC, REGOP>(v, v, A, M0, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);       // v = v05
+            horner_add<NT, BW, JAC, REGOP, SC>(v, v, A, M0, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);       // v = v05
         }
         M1 = p.template next_ks<0, 0>();                    // Kn0
         const double* M2 = p.template next_ks<0, 2>();      // Kn1
         if (active) {
             if constexpr (FOLD) {
-                mm_t4q3<NT, false, false, true, 6>(vN, v, M0, unew, unew, M1, A, A, M2, v, 0.0, -ceps, -ceps, ws + g);
+                mm_t4q3<NT, false, false, true, 6, SC ? 1 : 0>(vN, v, M0, unew, unew, M1, A, A, M2, v, 0.0, -ceps, -ceps, ws + g);
             } else {
             if constexpr (FUSE & 2) {
-                mm_t4q3<NT, false, false, true>(vN, v, M0, unew, unew, M1, A, A, M2, v);     // vN = v05 + S05 v05 ; unew -= c K0 v05 ; A = -c K1 v05
+                mm_t4q3<NT, false, false, true, 0, SC ? 1 : 0>(vN, v, M0, unew, unew, M1, A, A, M2, v);     // vN = v05 + S05 v05 ; unew -= c K0 v05 ; A = -c K1 v05
             } else {
                 mm_c<NT, BW>(vN, v, M0, v);
                 mm_c<NT, BW>(unew, unew, M1, v);
@@ -1783,9 +1869,10 @@ __device__ __forceinline__ void sv_state(RING& p, const PropArgs& a, bool active
         }
         M0 = p.template next_ks<1, 2>();                    // S1
         if (active) {
-            mm_c<NT, BW>(A, A, M0, unew);                              // A = c (S1 (u + c kappa1) - K1 v05)
+            if constexpr (SC) mm_t4s<NT, false>(A, A, M0, unew);
+            else mm_c<NT, BW>(A, A, M0, unew);                         // A = c (S1 (u + c kappa1) - K1 v05)
             a_add(unew, A);
-            horner_add<NT, BW, JAC, REGOP>(unew, unew, A, M0, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);
+            horner_add<NT, BW, JAC, REGOP, SC>(unew, unew, A, M0, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);
         }
         return;
     }
@@ -1851,9 +1938,10 @@ __device__ __forceinline__ void sv_state(RING& p, const PropArgs& a, bool active
 //  their register allocation 17 - 23 % -- cnot3 on <6, 9> 342 -> 402 ms, on <6, 1> 564 -> 692 ms per 4 000 steps.)
 template <int BW, bool JAC, bool WLRT>
 constexpr bool jq_wlr_on() { return WLRT; }
-template <int NT, int BW, int MINW, bool JAC, bool WLRT = false, bool UNI = false>      // (UNI: see k_backward)
+template <int NT, int BW, int MINW, bool JAC, bool WLRT = false, bool UNI = false, bool SC = false>      // (UNI, SC: see k_backward)
 __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_T4Q) ? 1 : MINW) void k_forward(PropArgs a)
 {
+    static_assert(!SC || (BW == JQ_BW_T4Q && MINW == 3 && !JAC && !WLRT), "SC: a variant of the three-slab quad-layout kernel");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int KT = 4 * NT;
     const int lane_ = threadIdx.x & 63;
@@ -1904,7 +1992,7 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
     {                                                                                                            \
         p.begin_step(NSTEP);                                                                                     \
         if (active) leak += a_wsq(wd, g, U); /* trapezoidal part: tr(vr' W vr) at t_n (:700) */                  \
-        sv_state<NT, BW, JAC, JQ_FWD_FUSE, UNI>(p, a, active, ceps, ws, g, U, V, UN, VN, A, Ya, Yb);                  \
+        sv_state<NT, BW, JAC, JQ_FWD_FUSE, UNI, true, false, RingT<QUAD>, SC>(p, a, active, ceps, ws, g, U, V, UN, VN, A, Ya, Yb); \
         /* use 6: Kp05 again -- v(t+h) = v05 + c (K05 u_new + S05 v05) */                                        \
         const double* M6 = p.template next_ks<0, 1>();                                                                             \
         if (active) {                                                                                            \
@@ -1984,10 +2072,15 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
 // compile time (no mode dispatch), and Hsym_1 lambda_i_new of the MIDDLE subsystem's control (lane-shift couplings only) rides along
 // in the pass that shifts lambda_i_new anyway (K05 lambda_i_new, use 11): backward sweep 755 -> 737 ms (round 4).  Letting Hanti_1 X and
 // Hsym_1 X ride along with K0 X / K1 X as well keeps vr(t_n+1) alive through that pass: 464 B of scratch, 1 327 ms -- rejected.
-template <int NT, int BW, int MINW, bool JAC, bool WLRT = false, bool UNI = false, bool ORD = false>
+// SC (with UNI + ORD, three slabs per workgroup; also k_forward): the plan's S images are UNIFORM (host: s_image_uniform -- Hanti_k = a_k - a_k',
+// the usual Juqbox set-up): the products with S0, S05, S1 -- 16 of the 20 full products of a Stormer-Verlet chain -- take the compact
+// operand (OpS: one A register and one (c0, c1) pair for all blocks, (c2, c3) per block) from block 0 of the same image.  Same FMAs and
+// MFMAs on the same values in the same order: bit-identical to the kernels without it (tests/test_gpu_s_compact.py).
+template <int NT, int BW, int MINW, bool JAC, bool WLRT = false, bool UNI = false, bool ORD = false, bool SC = false>
 __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_T4Q) ? 1 : MINW) void k_backward(PropArgs a)
 {
     static_assert(!ORD || (UNI && BW == JQ_BW_T4Q && !JAC), "ORD: a variant of the UNI quad-layout kernel");
+    static_assert(!SC || (ORD && MINW == 3 && !WLRT && !JQ_BWD3_NOOPQ && !JQ_BWD3_NOOPQ_STATE), "SC: a variant of the ORD three-slab kernel");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int KT = 4 * NT;
     const int lane_ = threadIdx.x & 63;
@@ -2123,7 +2216,7 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
         // mu's registers serve as the scratch array A of the state step
         // (UNI: the fused stages -- shared lane shifts of u and of v05 -- also in the twelve-wave kernel: round 3 measured them slower there,
         //  104 -> 144 ... 172 B of scratch; with the registers the UNI variant frees they pay: backward sweep 772 -> 757 ms, round 4)
-        sv_state<NT, BW, JAC, (MINW >= 3 ? (UNI ? 3 : JQ_BWD_FUSE3) : JQ_BWD_FUSE), UNI, !(QUAD && MINW >= 3 && JQ_BWD3_NOOPQ_STATE), jq_bwd_terms(NT, BW, JAC)>(p, a, active, ceps, ws, g, u, v, un, vN, mu, Ya, Yb);
+        sv_state<NT, BW, JAC, (MINW >= 3 ? (UNI ? 3 : JQ_BWD_FUSE3) : JQ_BWD_FUSE), UNI, !(QUAD && MINW >= 3 && JQ_BWD3_NOOPQ_STATE), jq_bwd_terms(NT, BW, JAC), RingT<QUAD>, SC>(p, a, active, ceps, ws, g, u, v, un, vN, mu, Ya, Yb);
         // (every wave has passed a workgroup barrier since it finished step n-1: begin_step in window mode, the operator
         // switches of sv_state otherwise)
         if (n > 0) flush_traces(n - 1);
@@ -2147,7 +2240,8 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
         // use 7: S0 -- L = c (S0 mu - K05 li + hr0) ; X = mu + sum_j S^j L   (in place: mu becomes X)
         M = p.template next_ks<1, 0>();
         if (active) {
-            mm_c<NT, BW>(L, L, M, mu);
+            if constexpr (SC) mm_t4s<NT, false>(L, L, M, mu);
+            else mm_c<NT, BW>(L, L, M, mu);
             a_axpy_rows1<NT, false>(L, wd, g, u);  // u holds vr before the state step (:862)
             if constexpr (WLR)
                 if (wforce)
@@ -2160,7 +2254,7 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
                     }
             a_add(mu, L);
             if constexpr (jq_bwd_terms(NT, BW, JAC)) neumann_terms_add<NT, BW>(mu, L, M, a.m, Ya);      // (L is scratch from here on)
-            else horner_add<NT, BW, JAC, BREG>(mu, mu, L, M, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);
+            else horner_add<NT, BW, JAC, BREG, SC>(mu, mu, L, M, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);
         }
         // early traces with X (lets vr0 = u die here): tr1 = tr(vr0' Hanti_q X), tr3 = tr(vr' Hanti_q X)
         double o_p4 = 0.0;      // ORD: the new part of tr4 of control 1, formed in the pass of use 11
@@ -2213,7 +2307,8 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
         //               nb_new = nb + L + sum_j S^j Q          (li_new = li + c (l2 + l1))
         M = p.template next_ks<1, 1>();
         if (active) {
-            mm_z<NT, BW>(Ya, M, nb);
+            if constexpr (SC) mm_t4s<NT, true>(Ya, Ya, M, nb);
+            else mm_z<NT, BW>(Ya, M, nb);
             a_axpy_rows1<NT, true>(Ya, wd, g, v);  // v holds vi05;  Ya = c (-S05 li - hi0)
             if constexpr (WLR)
                 if (wforce)
@@ -2228,11 +2323,12 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
                     }
             a_add(L, Ya);
             a_add(vN, Ya);
-            mm_c<NT, BW>(vN, vN, M, L);       // vN = Q
+            if constexpr (SC) mm_t4s<NT, false>(vN, vN, M, L);
+            else mm_c<NT, BW>(vN, vN, M, L);  // vN = Q
             a_add(L, nb);
             a_add(L, vN);                     // L = nb + L + Q
             if constexpr (jq_bwd_terms(NT, BW, JAC)) neumann_terms_add<NT, BW>(L, vN, M, a.m, Ya);      // (vN = Q is scratch from here on)
-            else horner_add<NT, BW, JAC, BREG>(L, L, vN, M, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);  // L = nb_new
+            else horner_add<NT, BW, JAC, BREG, SC>(L, L, vN, M, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);  // L = nb_new
             a_add(nb, L);                     // nb = nb_old + nb_new = -(li0 + li)
         }
         // use 11: Kp05 -- vN(scratch G) = X + c K05 nb_new (= lambda_r^{1/2} - c K05 li_new)
@@ -2256,7 +2352,8 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
         // use 12: S1 -- lambda_r_new = X + c (S1 X - K05 li_new + hr1)
         M = p.template next_ks<1, 2>();
         if (active) {
-            mm_c<NT, BW>(vN, vN, M, mu);
+            if constexpr (SC) mm_t4s<NT, false>(vN, vN, M, mu);
+            else mm_c<NT, BW>(vN, vN, M, mu);
             a_axpy_rows1<NT, false>(vN, wd, g, un);
             if constexpr (WLR)
                 if (wforce)

@@ -18,7 +18,7 @@ enum JqOpt {
     O_T4, O_OD, O_T4BIG, O_FORCE_DENSE, O_WINDOW, O_LANE, O_LANE_MIN, O_LANE_MAX, O_ROWLANE_MAX, O_COOP_MAX, O_QUAD, O_CQ, O_EMBED,
     O_STREAM_BYTES, O_CHUNK_STEPS, O_BATCH,
     // ---- per evaluation -------------------------------------------------------------------------------------------------
-    O_DQ, O_NOSPLIT, O_QUAD8, O_CQ_W, O_IMR_CQ, O_IMR_CQ2, O_CQ_FWD2, O_CQ3, O_QSPLIT, O_RL_SPLIT, O_JAC_WG, O_TRACE_BYTES, O_NO_UNI, O_NO_ORD,
+    O_DQ, O_NOSPLIT, O_QUAD8, O_CQ_W, O_IMR_CQ, O_IMR_CQ2, O_CQ_FWD2, O_CQ3, O_QSPLIT, O_RL_SPLIT, O_JAC_WG, O_TRACE_BYTES, O_NO_UNI, O_NO_ORD, O_S_COMPACT,
     O_QS_RIDE, O_CQ_GENERIC_TRACES, O_WLR_SC, O_RCCL_SELFCHECK, O_MULTI_SAME_DEVICE, O_CQ3_RDV_US, O_CQ3_WAIT_MS,
     // ---- test hooks (results unchanged) ---------------------------------------------------------------------------------
     O_DEBUG, O_CQ3_FAULT,
@@ -69,6 +69,7 @@ static const JqOptDesc g_jq_opt[O_COUNT] = {
     {"trace_bytes", JQ_OPT_UNSET, 0, "bytes of the per-step trace records of one backward chunk (default 4 GiB): smaller = more, shorter chunks"},
     {"no_uni", 0, 0, "1: three-slab quad-layout backward sweep on the generic kernel (tests compare)"},
     {"no_ord", 0, 0, "1: no single-subsystem-control specialisation of the quad-layout backward kernels (tests compare)"},
+    {"s_compact", 1, 0, "0: three-slab quad-layout kernels read the full S operand of every block even when the S images are uniform (plan info s_uniform; bit-identical)"},
     {"qs_ride", JQ_OPT_UNSET, 0, "split quad-layout backward kernel: trace products as separate passes (0) / riding along also at four quads per workgroup (1)"},
     {"cq_generic_traces", 0, 0, "1: cooperative-quad backward sweep with full trace products even when every control acts on one subsystem"},
     {"wlr_sc", 0, JQ_OPT_EXP, "1: full weights, quad layout: carry the column dots of a step in LDS (measured slower)"},

@@ -76,6 +76,7 @@ struct jq_handle {
     // per GROUP of at most JQ_MAXNC controls (ctrl_groups(); 5 .. 8 controls: two sweeps), each with its own trace images.
     int NcK = 0;                // controls per backward sweep the LDS plan is made for: min(Nc, JQ_MAXNC)
     std::vector<int> bw_trace;  // [Nc]
+    bool s_uniform = false;     // 4 x 4 x n plan: every 16-row block of an S image repeats block 0 (hanti_s_uniform, jq_host_select.h)
     long long mat_elems = 0;    // doubles per operator image slot ("stride"): band tiles, padded to 1 KiB
     long long mat_elems_c = 0;  // ... in the row-window layout of the cooperative kernels (0: not available)
     bool coop_ok = false;       // the cooperative Stormer-Verlet kernels fit the LDS (dense 96 x 96: only the implicit-midpoint variant that reads its images from HBM)
