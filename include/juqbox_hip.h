@@ -42,7 +42,8 @@ extern "C" {
  *     jq_timing.reserved renamed kernel_variant, jq_rccl_world_size; no size limits on Ntot, the number of control Hamiltonians or
  *     the rank of a full weight matrix; full leakage weights with the Jacobi solver;
  * 6 = continuation adjoints: jq_update_dvds, jq_set_sv_type, jq_get_sv_type (params.dVds_r / dVds_i / sv_type); later, with no
- *     change of a layout or of an existing entry point: jq_s_uniform (host-only structure test). */
+ *     change of a layout or of an existing entry point: jq_s_uniform (host-only structure test), jq_traceobjgrad_batch (many control
+ *     vectors of one problem in one call). */
 #define JQ_ABI_VERSION 6
 
 #define JQ_MAX_CONTROLS 16 /* control Hamiltonians the fast kernels hold in registers; more: cooperative kernels (no limit)    */
@@ -311,6 +312,24 @@ int jq_update_wmat(jq_handle *h, const double *wmat_real, const double *wmat_ima
  */
 int jq_traceobjgrad(jq_handle *h, const double *pcof, int32_t ncoeff, int32_t evaladjoint, double *out4,
                     double *totalgrad, double *infidelgrad, double *leakgrad);
+/*
+ * npcof independent evaluations traceobjgrad(pcofs[:, i], params, wa, false, evaladjoint) of ONE problem: multi-start optimisation,
+ * batched line searches, finite-difference checks, population optimisers, parameter scans of a pulse.
+ * pcofs: [ncoeff x npcof] column-major; out4: [4 x npcof]; totalgrad / infidelgrad / leakgrad: [ncoeff x npcof]
+ * (conventions per column exactly those of jq_traceobjgrad; NULL allowed when evaladjoint == 0).
+ * Column i of every output equals what jq_traceobjgrad returns for pcofs[:, i] under the handle's current settings (sv_type, weights,
+ * solver, target, objFuncType) -- bit for bit on the same kernel variant.
+ * Grouped batches: with the Stormer-Verlet integrator and the Neumann solver on the latency kernels -- row-lane (family 3) and
+ * cooperative quad (family 8, its dense policy included) -- the vectors SHARE launches: every workgroup belongs to one vector and
+ * reads the operator tile stream of that vector.  At most one vector's workgroups per compute unit go into a launch (option
+ * pcof_batch_max: fewer), larger batches run in rounds.  Column counts that would put two vectors into one wave / column quad
+ * (N = 3, 5, 6, 7 ...; cooperative quad: N not dividing 16 and not beyond it), every other kernel family and the implicit-midpoint
+ * integrator evaluate the vectors one after the other inside the call.  jq_plan_info reports what the last call did ("pcof_batch").
+ * Errors: those of the single call (JQ_EINVAL / JQ_EDIM for the coefficient count, JQ_EINVAL for NULL arguments), JQ_EINVAL for
+ * npcof < 1; a refused call writes nothing.  Multi-device handles shard the vectors like jq_traceobj_sweep (jq_shard_bounds).
+ */
+int jq_traceobjgrad_batch(jq_handle *h, const double *pcofs, int32_t ncoeff, int32_t npcof, int32_t evaladjoint,
+                          double *out4, double *totalgrad, double *infidelgrad, double *leakgrad);
 
 /*
  * Replaces the verbose branch's state history (src/evalobjgrad.jl:677-680, :748-752, returned at

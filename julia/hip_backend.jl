@@ -285,6 +285,25 @@ function traceobjgrad(pcof0::Array{Float64,1}, params::objparams, wa::AbstractWo
     return out4[1], tg, out4[2], out4[3], out4[4], ig, (params.objFuncType == 1 ? zeros(0) : lg)
 end
 
+# Many control vectors of ONE problem in one call (jq_traceobjgrad_batch): column i of every result is what
+# traceobjgrad(pcofs[:, i], params, wa, false, evaladjoint) returns.  On the latency kernels (row-lane, cooperative quad; Stormer-Verlet)
+# the vectors share launches, elsewhere they run one after the other inside the call.
+# evaladjoint: (objfv[n], totalgrad[ncoeff, n], primaryobjf[n], secondaryobjf[n], traceInfidelity[n], infidelgrad[ncoeff, n],
+#               leakgrad[ncoeff, n] -- 0 x n for objFuncType == 1); else (objfv[n], primaryobjf[n], secondaryobjf[n])
+function traceobjgrad_batch(pcofs::Matrix{Float64}, params::objparams, wa::AbstractWorkingArraysHIP, evaladjoint::Bool = true)
+    ncoeff, n = size(pcofs)
+    n >= 1 || throw(ArgumentError("traceobjgrad_batch: need at least one control vector"))
+    sync!(wa, params)
+    out4 = zeros(4, n)
+    tg = zeros(ncoeff, evaladjoint ? n : 0); ig = similar(tg); lg = similar(tg)
+    jqcheck(wa, ccall((:jq_traceobjgrad_batch, libjq), Cint,
+                      (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                      wa.handle, pcofs, ncoeff, n, evaladjoint ? 1 : 0, out4,
+                      evaladjoint ? pointer(tg) : C_NULL, evaladjoint ? pointer(ig) : C_NULL, evaladjoint ? pointer(lg) : C_NULL))
+    evaladjoint || return out4[1, :], out4[2, :], out4[3, :]
+    return out4[1, :], tg, out4[2, :], out4[3, :], out4[4, :], ig, (params.objFuncType == 1 ? zeros(0, n) : lg)
+end
+
 # the state history alone (usaver, usavei of src/evalobjgrad.jl:677-680, :748-752)
 function state_history(pcof::Vector{Float64}, params::objparams, wa::AbstractWorkingArraysHIP)
     sync!(wa, params)

@@ -69,10 +69,14 @@ __device__ __forceinline__ double stream_time(const double* tt, int n0, int j, d
 }
 
 // pq[j][2*Ncoupled] = (p_1, q_1, p_2, q_2, ...)(t_j)   -- KS!'s controlfunc calls (src/evalobjgrad.jl:2366-2367)
+// grid.y = control vectors of a grouped batch (jq_traceobjgrad_batch): vector g reads the coefficient block g of s.pcof and writes the
+// pq block g ([g][ntp][2 Ncoupled]); one vector is the launch it always was
 __global__ void k_ctrl(SplineArgs s, const double* tt, int n0, int ntp, double h, double* pq)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= ntp) return;
+    s.pcof += (size_t)blockIdx.y * s.nCoeff;
+    pq += (size_t)blockIdx.y * ntp * 2 * s.Ncoupled;
     const double t = stream_time(tt, n0, j, h);
     if (s.rfreq) {
         // uncoupled controls (src/evalobjgrad.jl:2373-2387): ft = 2 (p cos(2 pi Rfreq t) - q sin(2 pi Rfreq t)) multiplies
@@ -91,14 +95,16 @@ __global__ void k_ctrl(SplineArgs s, const double* tt, int n0, int ntp, double h
 // KS!: K = Hconst + sum_q p_q Hsym_q ; S = sum_q q_q Hanti_q  (src/evalobjgrad.jl:2354-2370), evaluated
 // on the MFMA tile images and stored pre-scaled for the accumulate-in-place step formulation
 // (jq_kernels.h): with c = h/2, K -> +c K at the half time points (odd j), -c K at the integer
-// time points (even j); S -> c S.   grid = (mat_elems/256, ntp)
+// time points (even j); S -> c S.   grid = (mat_elems/256, ntp, control vectors)
+// (grouped batch: vector g = blockIdx.z reads the pq block g and writes its own stream, gstride doubles behind the one before)
 __global__ void k_stream(const double* __restrict__ himg, const double* __restrict__ pq, int Ncoupled, long long mat_elems,
-                         double c, double* __restrict__ stream)
+                         double c, double* __restrict__ stream, long long gstride)
 {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int j = blockIdx.y;
     if (e >= mat_elems) return;
-    const double* ctl = pq + (size_t)j * 2 * Ncoupled;
+    stream += (size_t)blockIdx.z * (size_t)gstride;
+    const double* ctl = pq + ((size_t)blockIdx.z * gridDim.y + j) * 2 * Ncoupled;
     double K = himg[e], S = 0.0;
     for (int q = 0; q < Ncoupled; ++q) {
         K += ctl[2 * q] * himg[(size_t)(1 + q) * mat_elems + e];
@@ -355,11 +361,15 @@ __global__ void k_terminal_imr(double* state, long long stride, const double* __
 }
 
 // R[m][k] = sum_slab traces[slab][m][k] in slab order (deterministic).  thread per (m,k)
+// Grouped batch: grid.y = control vectors, `nslabs` = trace rows of ONE vector; R[g][m][k] sums the rows g nslabs .. (g + 1) nslabs - 1 in
+// row order -- the order a single evaluation of that vector sums them in.
 __global__ void k_trace_reduce(const double* __restrict__ traces, int nslabs, int nsteps_chunk, int ntr, double* R)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long tot = (long long)nsteps_chunk * ntr;
     if (i >= tot) return;
+    traces += (size_t)blockIdx.y * nslabs * tot;
+    R += (size_t)blockIdx.y * tot;
     double s = 0.0;
     for (int sl = 0; sl < nslabs; ++sl) s += traces[(size_t)sl * tot + i];
     R[i] = s;
@@ -374,11 +384,15 @@ __global__ void k_trace_reduce(const double* __restrict__ traces, int nslabs, in
 #define JQ_GRADACC_THREADS 256
 __global__ __launch_bounds__(JQ_GRADACC_THREADS) void k_gradacc(SplineArgs s, const double* __restrict__ R,
                                                                 const double* __restrict__ tb, int n0, int nsteps_chunk,
-                                                                double h, double* grad, int q0, int ng)
+                                                                double h, double* grad, int q0, int ng, long long grad_gstride)
 {
     // (q0, ng): the control group [q0, q0 + ng) this backward sweep computed the traces of (R rows: [ng][JQ_NTR] per step);
     // the grid covers the coefficients of those controls only
+    // grid.y = control vectors of a grouped batch: vector g assembles R[g] into its own gradient, grad_gstride doubles behind the one
+    // before (gradbcarrier2! does not depend on the coefficient values: the same code per vector)
     __shared__ double red[JQ_GRADACC_THREADS];
+    R += (size_t)blockIdx.y * nsteps_chunk * (ng * JQ_NTR);
+    grad += (size_t)blockIdx.y * (size_t)grad_gstride;
     const int per_osc = 2 * s.Nfreq * s.D1;
     const int idx = blockIdx.x + q0 * per_osc;
     const int q = idx / per_osc;
@@ -546,16 +560,17 @@ __global__ void k_init_state_rowlane(double* state, long long nw, const double* 
 
 // fidelity, leak and adjoint terminal condition per sample (thread per sample; see k_terminal)
 // (mode, dvr, dvi: see k_terminal; the dVds image has the layout of vtr / vti)
+// cpw: columns per wave (4; grouped batches with N < 4: N, so that every wave holds the columns of one control vector)
 __global__ void k_terminal_rowlane(double* state, long long nw, const double* __restrict__ vtr, const double* __restrict__ vti,
                                    int N, int nsamples, double leak_scale, double* res, const double* __restrict__ dvr,
-                                   const double* __restrict__ dvi, int mode)
+                                   const double* __restrict__ dvi, int mode, int cpw)
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nsamples) return;
     double re = 0.0, im = 0.0, lk = 0.0;
     for (int ic = 0; ic < N; ++ic) {
         const long long col = (long long)s * N + ic;
-        const size_t base = (size_t)(col >> 2) * 64 + (size_t)(col & 3) * 16;
+        const size_t base = (size_t)(col / cpw) * 64 + (size_t)(col % cpw) * 16;
         for (int r = 0; r < 16; ++r) {
             const double u = state[base + r], v = state[(size_t)nw * 64 + base + r];
             const double tr = vtr[ic * 16 + r], ti = vti[ic * 16 + r];
@@ -570,7 +585,7 @@ __global__ void k_terminal_rowlane(double* state, long long nw, const double* __
     if (mode >= 3) {      // s_D: the same sums against the dVds image
         for (int ic = 0; ic < N; ++ic) {
             const long long col = (long long)s * N + ic;
-            const size_t base = (size_t)(col >> 2) * 64 + (size_t)(col & 3) * 16;
+            const size_t base = (size_t)(col / cpw) * 64 + (size_t)(col % cpw) * 16;
             for (int r = 0; r < 16; ++r) {
                 const double u = state[base + r], v = state[(size_t)nw * 64 + base + r];
                 const double tr = dvr[ic * 16 + r], ti = dvi[ic * 16 + r];
@@ -586,7 +601,7 @@ __global__ void k_terminal_rowlane(double* state, long long nw, const double* __
     const double *xr = from_d ? dvr : vtr, *xi = from_d ? dvi : vti;
     for (int ic = 0; ic < N; ++ic) {
         const long long col = (long long)s * N + ic;
-        const size_t base = (size_t)(col >> 2) * 64 + (size_t)(col & 3) * 16;
+        const size_t base = (size_t)(col / cpw) * 64 + (size_t)(col % cpw) * 16;
         for (int r = 0; r < 16; ++r) {
             const double tr = xr[ic * 16 + r], ti = xi[ic * 16 + r];
             double lr = jq_dot2(aim, ti, are, tr) / N, nb = -(jq_det2(aim, tr, are, ti) / N);

@@ -66,14 +66,15 @@ struct WinRing {
     }
     // time points 0 .. 4 and the constants; wb1, wb2 = time points 1, 2 (step 0); time point 0 is at offset 0
     // (all JQ_WIN_TPS time points are fetched before the first step)
-    __device__ __forceinline__ void init(char* smem_, const PropArgs& a, int wave_, int lane_, int nwaves_)
+    // (strm: the chunk's tile stream -- a.stream, or the workgroup's own of a grouped batch, cq_group_stream)
+    __device__ __forceinline__ void init(char* smem_, const PropArgs& a, int wave_, int lane_, int nwaves_, const double* strm)
     {
         smem = smem_, wave = wave_, lane = lane_, nwaves = nwaves_;
         stride_b = (unsigned)(a.stride * 8);
         slot_bytes = 2 * stride_b;
         cbase = JQ_WIN_TPS * slot_bytes;
         pieces2 = 2 * a.pieces;
-        gnext = (const char*)a.stream;
+        gnext = (const char*)strm;
         jnext = 0, jlast = 2 * a.nsteps_chunk, snext = 0;
         dma((const char*)a.cimg, smem + cbase, 2 * a.Ncoupled * a.pieces);
         for (int j = 0; j < JQ_WIN_TPS; ++j) issue_next();
@@ -82,6 +83,7 @@ struct WinRing {
         asm volatile("" ::: "memory");
         wb0 = 0, wb1 = slot_bytes, wb2 = 2 * slot_bytes;
     }
+    __device__ __forceinline__ void init(char* smem_, const PropArgs& a, int wave_, int lane_, int nwaves_) { init(smem_, a, wave_, lane_, nwaves_, a.stream); }
     // the window of the next step (call once its operators are about to be loaded)
     __device__ __forceinline__ void advance()
     {
@@ -601,6 +603,11 @@ __device__ __forceinline__ CqSetup<NT> cq_setup(const PropArgs& a)
 {
     return cq_setup<NT>(a, (int)blockIdx.x >> 2, (int)blockIdx.x & 3);
 }
+// Grouped batch (one column quad per workgroup): a control vector owns max(1, N / 4) consecutive quads, N > 16: those of its `parts` slabs
+__device__ __forceinline__ const double* cq_group_stream(const PropArgs& a)
+{
+    return jq_group_stream(a, (int)blockIdx.x, a.parts > 1 ? 4 * a.parts : a.N > 4 ? a.N >> 2 : 1);
+}
 
 // ---------------------------------------------------------------------------------------------
 // grid = 4 * nslabs (workgroup = quad qd of slab blockIdx.x / 4), block = 64 * (NT + 2); 5 + 2 m barriers per time step.
@@ -636,7 +643,7 @@ __global__ __launch_bounds__(64 * NT + 128) void k_forward_cq(PropArgs a)
     CoopQ<NT, DN> c;
     double* scratch = tab + 32 * NT + 2 * CoopQ<NT, DN>::PAR;
     c.setup(tab + 32 * NT, s.chain ? 0 : wave, lane_);
-    c.ring.init(smem, a, wave + NT * s.chain, lane_, NT + 2);      // (barrier inside)
+    c.ring.init(smem, a, wave + NT * s.chain, lane_, NT + 2, NS == 1 ? cq_group_stream(a) : a.stream);      // (barrier inside)
     if (s.chain) {      // staging waves
         c.ring.wave = wave, c.ring.nwaves = 2;
         const int mm = a.m > 0 ? a.m : 0;
@@ -869,7 +876,7 @@ __global__ __launch_bounds__(128 * NT) void k_backward_cq(PropArgs a)
     const int ntr = Nc * JQ_NTR, ngroups = Nc + (Nc + 1) / 2;
     double* red = scratch;                                      // [ngroups][NT][64]: trace hand-off (dead by then: same LDS)
     c.setup(tab + 32 * NT, wave, lane_);
-    c.ring.init(smem, a, wave_all, lane_, 2 * NT);
+    c.ring.init(smem, a, wave_all, lane_, 2 * NT, cq_group_stream(a));
     c.ring.wave = wave, c.ring.nwaves = NT;      // (from here on the state waves stage)
     const double wdr = tab[16 * wave + s.g], wsr = tab[16 * NT + 16 * wave + s.g];
     double* st = a.state + (size_t)s.slab * a.state_stride;

@@ -651,9 +651,11 @@ static int create_dense(const jq_problem* p, jq_handle* h)
     // k_ctrl / k_stream put the 2 cs + 1 time points of a chunk into gridDim.y (limit 65535)
     cs = std::min<long long>(cs, 32767);
     h->chunk_steps = (int)cs;
+    h->cap_stream = h->cap_pq = h->cap_R = 0;
     if ((rc = dev_alloc(h, &h->d_stream, (size_t)(2 * cs + 1) * 2 * img_elems))) return rc;
     if ((rc = dev_alloc(h, &h->d_pq, (size_t)(2 * cs + 1) * 2 * h->Nc))) return rc;
     if ((rc = dev_alloc(h, &h->d_R, (size_t)cs * h->Nc * JQ_NTR))) return rc;
+    h->cap_stream = (size_t)(2 * cs + 1) * 2 * img_elems, h->cap_pq = (size_t)(2 * cs + 1) * 2 * h->Nc, h->cap_R = (size_t)cs * h->Nc * JQ_NTR;
     return JQ_OK;
 }
 

@@ -12,6 +12,36 @@ __global__ void k_add_to(double* __restrict__ y, const double* __restrict__ x, i
     if (i < n) y[i] += x[i];
 }
 
+// the coefficient count of a control vector (src/evalobjgrad.jl:604-608, src/bsplines.jl:177-181): the codes of every evaluation entry point
+static int check_ncoeff(jq_handle* h, int ncoeff)
+{
+    const int Nsig = 2 * h->Nc;
+    // src/evalobjgrad.jl:604-606
+    if (ncoeff % Nsig != 0 || ncoeff < 3 * Nsig) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "pcof must have an even number of elements >= %d, not %d", 3 * Nsig, ncoeff);
+        return fail(h, JQ_EINVAL, buf);
+    }
+    const int D1 = ncoeff / (Nsig * h->Nfreq);  // :608
+    // bcparams: nCoeff = Nfreq*D1*2*Ncoupled must equal length(pcof) (src/bsplines.jl:177-181)
+    if (h->Nfreq * D1 * Nsig != ncoeff)
+        return fail(h, JQ_EDIM, "DimensionMismatch: Inconsistent number of coefficients and size of parameter vector (nCoeff != length(pcof))");
+    if (D1 < 3) return fail(h, JQ_EINVAL, "need at least 3 B-spline coefficients per control function");
+    return JQ_OK;
+}
+// The handle that evaluates a Stormer-Verlet batch of `nsamples` samples without a state history: h, or its embedded twin (structure
+// embedding, try_embed: batches that would run on the dense / band MFMA families go to the twin, whose operators have the JQ_BW_T4 structure)
+static jq_handle* eval_target(jq_handle* h, int nsamples, bool hist)
+{
+    if (h->emb && !hist && h->integrator == 1) {
+        const long long nc_used = (long long)nsamples * h->N;
+        // (full leakage weights: the row-lane kernels take every batch of an Ntot <= 16 problem -- the lane kernels have no low-rank terms)
+        const bool small_family = h->solver_id == 1 && ((h->rl_npj > 0 && (nc_used <= h->rl_max_cols || h->wrank > 0)) ||
+                                                        (h->lane_np > 0 && nc_used >= h->lane_min_cols && nc_used <= h->lane_max_cols));
+        if (h->emb_mode == 2 || !small_family) return h->emb;
+    }
+    return h;
+}
 // The batched evaluation behind every hot-path entry point.
 // d_packed != nullptr: the packed ensemble result (k_pack) is also left at this DEVICE address of h's GPU.
 #define JQ_ERETRY_INTERNAL (-1000)      // run_eval_impl: k_backward_cq3 gave up (the handle leaves it alone for a while): evaluate again
@@ -88,42 +118,40 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
             return JQ_OK;
         }
     }
-    const int Nsig = 2 * h->Nc;
-    // src/evalobjgrad.jl:604-606
-    if (ncoeff % Nsig != 0 || ncoeff < 3 * Nsig) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "pcof must have an even number of elements >= %d, not %d", 3 * Nsig, ncoeff);
-        return fail(h, JQ_EINVAL, buf);
-    }
-    const int D1 = ncoeff / (Nsig * h->Nfreq);  // :608
-    // bcparams: nCoeff = Nfreq*D1*2*Ncoupled must equal length(pcof) (src/bsplines.jl:177-181)
-    if (h->Nfreq * D1 * Nsig != ncoeff)
-        return fail(h, JQ_EDIM, "DimensionMismatch: Inconsistent number of coefficients and size of parameter vector (nCoeff != length(pcof))");
-    if (D1 < 3) return fail(h, JQ_EINVAL, "need at least 3 B-spline coefficients per control function");
+    int rc = check_ncoeff(h, ncoeff);
+    if (rc) return rc;
+    const int D1 = ncoeff / (2 * h->Nc * h->Nfreq);  // src/evalobjgrad.jl:608
     if (nsamples < 1) return fail(h, JQ_EINVAL, "need at least one sample");
+    // grouped batch (jq_traceobjgrad_batch): G control vectors, pcof = their G coefficient blocks, nsamples = G x spg samples
+    const int G = h->grp_G, spg = h->grp_spg;
+    if (G > 0 && (nsamples != G * spg || eps || wgt || shift || hist_r || d_packed)) return fail(h, JQ_EHIP, "internal error: grouped batch with ensemble arguments");
+    const int nvec = G > 0 ? G : 1;      // (coefficient blocks, tile streams, gradients of the launch)
     // Structure embedding (try_embed): batches that would run on the dense / band MFMA families go to the embedded twin,
     // whose operators have the JQ_BW_T4 structure (quad-layout / JQ_BW_T4 slab kernels).  State histories stay here (their
     // rows are the user's), the implicit-midpoint path too.
-    if (h->emb && !hist_r && h->integrator == 1) {
-        const long long nc_used = (long long)nsamples * h->N;
-        // (full leakage weights: the row-lane kernels take every batch of an Ntot <= 16 problem -- the lane kernels have no low-rank terms)
-        const bool small_family = h->solver_id == 1 && ((h->rl_npj > 0 && (nc_used <= h->rl_max_cols || h->wrank > 0)) ||
-                                                        (h->lane_np > 0 && nc_used >= h->lane_min_cols && nc_used <= h->lane_max_cols));
-        if (h->emb_mode == 2 || !small_family) {
-            jq_handle* e = h->emb;
-            std::vector<double> sh(e->Ntot, 0.0);
-            for (int i = 0; i < h->Ntot; ++i)   // (default: the reference's 0.01 * 10^(j-2) by the USER's level index, src/ipopt_interface.jl:41-44)
-                sh[h->emb_row[i]] = shift ? shift[i] : (i >= 1 ? 0.01 * pow(10.0, (double)(i - 1)) : 0.0);
-            const int rc = run_eval(e, pcof, ncoeff, nsamples, eps, wgt, sh.data(), adjoint, nullptr, nullptr, out, d_packed);
-            if (rc != JQ_OK) h->err = e->err;
-            h->timing = e->timing;
-            return rc;
-        }
+    if (eval_target(h, nsamples, hist_r != nullptr) != h) {
+        jq_handle* e = h->emb;
+        std::vector<double> sh(e->Ntot, 0.0);
+        for (int i = 0; i < h->Ntot; ++i)   // (default: the reference's 0.01 * 10^(j-2) by the USER's level index, src/ipopt_interface.jl:41-44)
+            sh[h->emb_row[i]] = shift ? shift[i] : (i >= 1 ? 0.01 * pow(10.0, (double)(i - 1)) : 0.0);
+        e->grp_G = G, e->grp_spg = spg;      // (a grouped batch stays one: the shift table is not read without eps)
+        const int rc = run_eval(e, pcof, ncoeff, nsamples, eps, wgt, G > 0 ? nullptr : sh.data(), adjoint, nullptr, nullptr, out, d_packed);
+        e->grp_G = 0, e->grp_spg = 1;
+        if (rc != JQ_OK) h->err = e->err;
+        h->timing = e->timing;
+        return rc;
     }
     GateHold gate_hold;      // (held until the evaluation ends when the plan takes the split latency kernels)
     BatchPlan p;
-    int rc = plan_batch(h, nsamples, adjoint, hist_r != nullptr, gate_hold, &p);
+    rc = plan_batch(h, nsamples, adjoint, hist_r != nullptr, gate_hold, &p, G);
     if (rc) return rc;
+    if (p.groups != G) return fail(h, JQ_EHIP, "internal error: grouped batch on a kernel family that does not serve one");
+    std::vector<double> gwgt;
+    if (G > 0 && spg > 1) {      // (the padding samples of a vector's column quad weigh nothing -- like the unused columns of a single evaluation's quad)
+        gwgt.assign((size_t)nsamples, 0.0);
+        for (int g = 0; g < G; ++g) gwgt[(size_t)g * spg] = 1.0;
+        wgt = gwgt.data();
+    }
     const bool imr = (h->integrator == 2);
     const bool cq3 = p.cq_nr > 0, qsplit = p.qs_qw > 0;
     const long long ncols_used = (long long)nsamples * h->N;
@@ -132,7 +160,13 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
     const bool two_pass = adjoint && h->objFuncType != 1;
 
     // ---- capacity ------------------------------------------------------------------------------
-    if ((rc = dev_grow(h, &h->d_pcof, &h->cap_pcof, (size_t)ncoeff))) return rc;
+    if ((rc = dev_grow(h, &h->d_pcof, &h->cap_pcof, (size_t)nvec * ncoeff))) return rc;
+    const size_t gstride = G > 0 ? (size_t)(2 * p.cs + 1) * 2 * (size_t)p.stride : 0;      // doubles between the tile streams of two vectors
+    if (G > 0) {      // (sized by jq_create for ONE vector and the handle's chunk length)
+        if ((rc = dev_grow(h, &h->d_stream, &h->cap_stream, (size_t)G * gstride))) return rc;
+        if ((rc = dev_grow(h, &h->d_pq, &h->cap_pq, (size_t)G * (2 * p.cs + 1) * 2 * h->Nc))) return rc;
+        if (adjoint && (rc = dev_grow(h, &h->d_R, &h->cap_R, (size_t)G * p.cs * h->NcK * JQ_NTR))) return rc;
+    }
     if (p.state_doubles > h->cap_state || !h->d_state || !h->d_state_save) {
         h->cap_state = 0;
         if ((rc = dev_alloc(h, &h->d_state, p.state_doubles))) return rc;
@@ -146,7 +180,7 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
         h->cap_slabs = p.park_slabs;
     }
     if (adjoint && (rc = dev_grow(h, &h->d_traces, &h->cap_traces, (size_t)p.trace_rows * p.cs * ntr))) return rc;
-    if ((rc = dev_grow(h, &h->d_grad, &h->cap_grad, (size_t)2 * ncoeff))) return rc;
+    if ((rc = dev_grow(h, &h->d_grad, &h->cap_grad, (size_t)nvec * 2 * ncoeff))) return rc;      // [vector][forced | unforced][ncoeff]
     if ((rc = dev_grow(h, &h->d_res, &h->cap_res, (size_t)nsamples * 4))) return rc;
     const size_t cq3_quad = 64 + (size_t)8 * 8 * h->NT * 64 + 64;      // doubles per quad: JQ_CQ3_HEAD + JQ_CQ3_SLOTS * JQ_CQ3_ARRAYS * NT * 64 + JQ_CQ3_TAIL
     if (cq3) {
@@ -157,7 +191,7 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
 
     // ---- inputs --------------------------------------------------------------------------------
     hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(h->d_pcof, pcof, (size_t)ncoeff * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->d_pcof, pcof, (size_t)nvec * ncoeff * sizeof(double), hipMemcpyHostToDevice, s));
     bool use_shift = false;
     std::vector<double> colinfo(p.colinfo_doubles, 0.0);
     if (p.layout != SL_SLABS) {   // [eps per column slot | weight per column slot]  (lane kernels: cpw = 4, one slot per column)
@@ -187,7 +221,7 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
         tabs[p.ws_off + i] = shift ? shift[i] : (i >= 1 ? 0.01 * pow(10.0, (double)(i - 1)) : 0.0);
     }
     HIPCHK(h, hipMemcpyAsync(h->d_tabs, tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemsetAsync(h->d_grad, 0, (size_t)2 * ncoeff * sizeof(double), s));
+    HIPCHK(h, hipMemsetAsync(h->d_grad, 0, (size_t)nvec * 2 * ncoeff * sizeof(double), s));
 
     SplineArgs sp;
     sp.pcof = h->d_pcof; sp.cfreq = h->d_cfreq; sp.D1 = D1; sp.Nfreq = h->Nfreq; sp.Ncoupled = h->Nc; sp.nCoeff = ncoeff;
@@ -197,7 +231,7 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
     const double dt = h->T / h->nsteps;
     PropArgs a;
     memset(&a, 0, sizeof a);
-    a.stream = h->d_stream; a.cimg = p.cimg; a.state = h->d_state; a.colinfo = h->d_colinfo;
+    a.stream = h->d_stream; a.stream_gstride = (long long)gstride; a.cimg = p.cimg; a.state = h->d_state; a.colinfo = h->d_colinfo;
     a.traces = h->d_traces;
     a.tabs = h->d_tabs; a.stride = p.stride; a.pieces = (int)(p.stride * 8 / 1024); a.m = h->m;
     a.nslabs = p.prop_nslabs; a.Ncoupled = ctrl_gstart(h->Nc, 1) /* first control group */; a.Ntot = h->Ntot; a.N = h->N; a.use_shift = use_shift ? 1 : 0;
@@ -243,9 +277,9 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
     for (int n0 = 0; n0 < h->nsteps; n0 += p.cs) {
         const int nc = std::min(p.cs, h->nsteps - n0);
         const int ntp = 2 * nc + 1;
-        hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128), dim3(128), 0, s, sp, h->d_tf, n0, ntp, dt, h->d_pq);
-        hipLaunchKernelGGL(k_stream, dim3((unsigned)((p.stride + 255) / 256), ntp), dim3(256), 0, s, p.himg, h->d_pq,
-                           h->Nc, p.stride, 0.5 * dt, h->d_stream);
+        hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, sp, h->d_tf, n0, ntp, dt, h->d_pq);
+        hipLaunchKernelGGL(k_stream, dim3((unsigned)((p.stride + 255) / 256), ntp, nvec), dim3(256), 0, s, p.himg, h->d_pq,
+                           h->Nc, p.stride, 0.5 * dt, h->d_stream, (long long)gstride);
         a.nsteps_chunk = nc; a.step0 = n0; a.first_chunk = (n0 == 0); a.h = dt; a.forced = 1;
         a.hist_r = hist_r; a.hist_i = hist_i;
         a.wlr_lds = p.fwd.wlr;
@@ -277,7 +311,7 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
                            h->d_vti_r, h->N, nsamples, leak_scale, h->d_res, p.cpw);
     else if (p.term == TK_ROWLANE)
         hipLaunchKernelGGL(k_terminal_rowlane, dim3((nsamples + 63) / 64), dim3(64), 0, s, h->d_state, p.nwaves_rl, h->d_vtr_r,
-                           h->d_vti_r, h->N, nsamples, leak_scale, h->d_res, h->d_dvr_r, h->d_dvi_r, sv_mode);
+                           h->d_vti_r, h->N, nsamples, leak_scale, h->d_res, h->d_dvr_r, h->d_dvi_r, sv_mode, p.cpw);
     else if (p.term == TK_LANE)
         hipLaunchKernelGGL(p.klterm, dim3((nsamples + 63) / 64), dim3(64), 0, s, h->d_state, p.ncols, h->d_vtr_l, h->d_vti_l, h->N,
                            nsamples, leak_scale, h->d_res, h->d_dvr_l, h->d_dvi_l, sv_mode);
@@ -311,9 +345,9 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
             for (int n0 = 0; n0 < h->nsteps; n0 += p.cs) {
                 const int nc = std::min(p.cs, h->nsteps - n0);
                 const int ntp = 2 * nc + 1;
-                hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128), dim3(128), 0, s, sp, h->d_tb, n0, ntp, -dt, h->d_pq);
-                hipLaunchKernelGGL(k_stream, dim3((unsigned)((p.stride + 255) / 256), ntp), dim3(256), 0, s, p.himg,
-                                   h->d_pq, h->Nc, p.stride, -0.5 * dt, h->d_stream);
+                hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, sp, h->d_tb, n0, ntp, -dt, h->d_pq);
+                hipLaunchKernelGGL(k_stream, dim3((unsigned)((p.stride + 255) / 256), ntp, nvec), dim3(256), 0, s, p.himg,
+                                   h->d_pq, h->Nc, p.stride, -0.5 * dt, h->d_stream, (long long)gstride);
                 a.nsteps_chunk = nc; a.step0 = n0; a.first_chunk = (n0 == 0); a.h = -dt; a.forced = (pass == 0);
                 a.hist_r = nullptr; a.hist_i = nullptr;
                 a.wlr_lds = p.bwd.wlr;
@@ -367,11 +401,12 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
                         break;
                     }
                 }
-                hipLaunchKernelGGL(k_trace_reduce, dim3((unsigned)(((long long)nc * ntr_g + 255) / 256)), dim3(256), 0, s,
-                                   h->d_traces, p.trace_rows, nc, ntr_g, h->d_R);
+                // (grouped batch: per vector its own trace rows -- p.upg of them, the padding rows of the last slab belong to nobody -- and its own gradient)
+                hipLaunchKernelGGL(k_trace_reduce, dim3((unsigned)(((long long)nc * ntr_g + 255) / 256), nvec), dim3(256), 0, s,
+                                   h->d_traces, G > 0 ? p.upg : p.trace_rows, nc, ntr_g, h->d_R);
                 // gradbcarrier2! as a scatter: one workgroup per coefficient of the group's controls
-                hipLaunchKernelGGL(k_gradacc, dim3(ng * 2 * h->Nfreq * D1), dim3(JQ_GRADACC_THREADS), 0, s, sp, h->d_R, h->d_tb, n0, nc, -dt,
-                                   h->d_grad + (size_t)pass * ncoeff, q0, ng);
+                hipLaunchKernelGGL(k_gradacc, dim3(ng * 2 * h->Nfreq * D1, nvec), dim3(JQ_GRADACC_THREADS), 0, s, sp, h->d_R, h->d_tb, n0, nc, -dt,
+                                   h->d_grad + (size_t)pass * ncoeff, q0, ng, (long long)2 * ncoeff);
                 mfma += (long long)p.nslabs * nc * (2 * (8 + 2 * h->m) * p.tiles + 4 * trace_tiles);
                 if (n0 == 0) mfma += (long long)p.nslabs * trace_tiles;
             }
@@ -393,13 +428,14 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
     // ---- outputs -------------------------------------------------------------------------------
     out->res.resize((size_t)nsamples * 4);
     HIPCHK(h, hipMemcpyAsync(out->res.data(), h->d_res, out->res.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (adjoint) {
-        out->grad0.resize(ncoeff);
-        HIPCHK(h, hipMemcpyAsync(out->grad0.data(), h->d_grad, (size_t)ncoeff * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (two_pass) {
-            out->grad1.resize(ncoeff);
-            HIPCHK(h, hipMemcpyAsync(out->grad1.data(), h->d_grad + ncoeff, (size_t)ncoeff * sizeof(double),
-                                     hipMemcpyDeviceToHost, s));
+    if (adjoint) {      // (grouped batch: [vector][ncoeff] each)
+        out->grad0.resize((size_t)nvec * ncoeff);
+        if (two_pass) out->grad1.resize((size_t)nvec * ncoeff);
+        for (int g = 0; g < nvec; ++g) {
+            HIPCHK(h, hipMemcpyAsync(out->grad0.data() + (size_t)g * ncoeff, h->d_grad + (size_t)g * 2 * ncoeff, (size_t)ncoeff * sizeof(double), hipMemcpyDeviceToHost, s));
+            if (two_pass)
+                HIPCHK(h, hipMemcpyAsync(out->grad1.data() + (size_t)g * ncoeff, h->d_grad + (size_t)g * 2 * ncoeff + ncoeff, (size_t)ncoeff * sizeof(double),
+                                         hipMemcpyDeviceToHost, s));
         }
     }
     unsigned long long cq3_err = cq3_fault;

@@ -431,3 +431,38 @@ static int multi_traceobj_sweep(jq_handle* h, const double* pcof, int ncoeff, co
     return JQ_OK;
 }
 
+
+// jq_traceobjgrad_batch on a multi-device handle: the control vectors are block-partitioned over the devices (jq_shard_bounds); every
+// output column belongs to one vector, so there is nothing to reduce
+static int multi_traceobjgrad_batch(jq_handle* h, const double* pcofs, int ncoeff, int npcof, int evaladjoint, double* out4, double* totalgrad,
+                                    double* infidelgrad, double* leakgrad)
+{
+    DeviceGuard guard;
+    const int nd = (int)h->subs.size();
+    // (a refused call writes nothing: the coefficient count is checked before any device starts)
+    if (int rc = check_ncoeff(h->subs[0], ncoeff)) {
+        h->err = h->subs[0]->err;
+        return rc;
+    }
+    std::vector<int> rcs(nd, JQ_OK);
+    std::vector<std::thread> th;
+    for (int d = 0; d < nd; ++d)
+        th.emplace_back([&, d]() {
+            jq_handle* sub = h->subs[d];
+            int lo = 0, hi = 0;
+            jq_shard_bounds(npcof, d, nd, &lo, &hi);
+            sub->timing = jq_timing{};
+            const size_t off = (size_t)ncoeff * lo;
+            if (hi > lo)
+                rcs[d] = jq_traceobjgrad_batch(sub, pcofs + off, ncoeff, hi - lo, evaladjoint, out4 + (size_t)4 * lo, totalgrad ? totalgrad + off : nullptr,
+                                               infidelgrad ? infidelgrad + off : nullptr, leakgrad ? leakgrad + off : nullptr);
+        });
+    for (auto& t : th) t.join();
+    for (int d = 0; d < nd; ++d)
+        if (rcs[d] != JQ_OK) {
+            h->err = h->subs[d]->err;
+            return rcs[d];
+        }
+    multi_timing(h, 0.0);
+    return JQ_OK;
+}

@@ -131,6 +131,9 @@ struct BatchPlan {
     // geometry (prop_nslabs: PropArgs::nslabs -- waves of the row-lane kernels, columns of the lane kernels; bwd_block_ng2: backward
     // sweeps of two or more controls)
     int nslabs, prop_nslabs, cpw, qps, qs_blocks, trace_rows, cs;
+    // grouped batch (jq_traceobjgrad_batch): control vectors of the launch (0: not grouped -- also the answer to a request the chosen family
+    // cannot serve) and the units one vector owns = its trace rows (row-lane: waves, cooperative quad: column quads)
+    int groups, upg;
     long long nwaves_rl, ncols, nq_pad, stride;
     unsigned fwd_grid, fwd_block, bwd_grid, bwd_block, bwd_block_ng2;
     const double *himg, *cimg;
@@ -156,9 +159,15 @@ static long long plan_trace_tiles(const jq_handle* h, const BatchPlan& p, int q)
 //   Stormer-Verlet:    row-lane (3) > lane (2) > cooperative quad (8) > quad layout (6) > cooperative (1) > slab (0).
 // Side effects: the split latency kernels' cool-down (cq3_skip, cq3_last: once per evaluation of those families with a gradient) and,
 // when they are taken, the device held exclusively in gate_hold until the caller's scope ends.
-static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateHold& gate_hold, BatchPlan* p)
+// groups > 0: a GROUPED batch of that many control vectors (nsamples = groups x samples per vector), every workgroup working for exactly
+// one of them: Stormer-Verlet on the row-lane kernels (a vector per wave or waves: N < 4 packs N columns per wave, cpw) and on the
+// cooperative-quad kernels (a vector per column quad or consecutive quads; one workgroup per quad in both sweeps -- no two-quad forward
+// variant, no split backward kernels).  Column counts that would put two vectors into one wave / quad, and every other family, answer
+// p->groups = 0: the caller evaluates the vectors one after the other.  A grouped plan has no side effects.
+static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateHold& gate_hold, BatchPlan* p, int groups = 0)
 {
     memset(p, 0, sizeof *p);
+    const bool grp = groups > 0;
     if (adjoint && !h->rfreq.empty() && h->integrator != 1)
         return fail(h, JQ_EUNSUPPORTED, "uncoupled controls (Hunc_ops): gradients with the Stormer-Verlet integrator only (the reference's "
                                         "implicit-midpoint adjoint has no term for them, src/evalobjgrad.jl:1347)");
@@ -181,7 +190,7 @@ static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateH
     p->hbm = imr_coop && h->NT <= 6 && h->mat_elems_c > 0 && coop_imr_lds_bytes(h->NT, h->mat_elems_c) > JQ_LDS_MAX;
     if (imr_coop && (h->mat_elems_c == 0 || (p->hbm && !(h->NT == 6 && h->BWc == 5))))
         return fail(h, JQ_EUNSUPPORTED, "implicit midpoint: no kernels for these operators (no cooperative layout / images that do not fit the LDS)");
-    p->cpw = imr_rl ? imr_cols_per_wave(h->N) : 4;   // columns per wave of the row-lane kernels
+    p->cpw = imr_rl ? imr_cols_per_wave(h->N) : (grp && h->N < 4) ? h->N : 4;   // columns per wave of the row-lane kernels
     // Full leakage weights (jq_update_wmat): row-lane kernels for every batch of an Ntot <= 16 problem, quad-layout kernels with one slab
     // per workgroup for the 4 x 4 x n structure (cooperative-quad kernels: wfull_cq below), else the cooperative kernels (every batch size)
     // or where those do not exist the slab kernels <1, 0> / <6, 5>; no lane or JQ_BW_T4 slab kernels
@@ -224,7 +233,7 @@ static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateH
     const bool imr_cq = imr_dq || (imr_quad && h->N == 4 && h->parts == 1 && h->cq_max_quads > 0 && nquads_used <= h->cq_max_quads &&
                                    h->opt.on(O_IMR_CQ));
     // more column quads than CUs: the forward sweep takes two quads per workgroup (one round at ~ 1.5 x the time instead of two; cq_fwd2=0 / 1)
-    p->fwd2 = cq && !cq_dn && !wfull && (h->opt.has(O_CQ_FWD2) ? h->opt.on(O_CQ_FWD2) : nquads_used > h->num_cu);
+    p->fwd2 = cq && !cq_dn && !wfull && !grp && (h->opt.has(O_CQ_FWD2) ? h->opt.on(O_CQ_FWD2) : nquads_used > h->num_cu);
     // single evaluations and small ensembles: the backward sweep on three workgroups per column quad (state re-integration | adjoint step |
     // trace products, through a ring in global memory: jq_cq_split_kernels.h), all resident at once, in groups of 8 quads (quad q is slot
     // q & 3 of slab q >> 2); round 5: two workgroups (state | adjoint + traces) for 2 x quads <= CUs, Stormer-Verlet only (cq3=3: three or none)
@@ -241,7 +250,8 @@ static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateH
         // must have to WAIT for them, which it does from step 8 on (8 ring slots), so the first chunk must be longer than the ring (shorter
         // ones were a race, found in round 5 with option debug=16).  backward_chunk_steps gives the chunk length of the sweep below too.
         const long long cs_first = std::min<long long>(backward_chunk_steps(h, (size_t)p->nslabs * p->qps * (imr_cq ? h->NT : 1)), h->nsteps);
-        if (c3_set && c3_v == 0) why = "not taken: option cq3=0";
+        if (grp) why = "not taken: grouped batch of control vectors (one workgroup per column quad)";
+        else if (c3_set && c3_v == 0) why = "not taken: option cq3=0";
         else if (cs_first <= JQ_CQ3_RING) why = "not taken: the first chunk of the sweep is not longer than the hand-off ring (8 steps)";
         else if (p->cq_nr == 0) why = "not taken: two / three workgroups per column quad exceed the compute units";
         else if (h->cq3_off) why = "not taken: switched off after repeated faults (dead waits between the workgroups of a quad)";
@@ -251,8 +261,8 @@ static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateH
         else if (!gate_hold.acquire(dev_gate(h->device))) why = "not taken: another evaluation of this process is in flight on the device";
         cq3 = (why == nullptr);
         if (!cq3) p->cq_nr = 0;
-        if (h->cq3_skip > 0) --h->cq3_skip;
-        h->cq3_last = cq3 ? (p->cq_nr == 3 ? "taken: three workgroups per column quad, device held exclusively" : "taken: two workgroups per column quad, device held exclusively") : why;
+        if (h->cq3_skip > 0 && !grp) --h->cq3_skip;
+        if (!grp) h->cq3_last = cq3 ? (p->cq_nr == 3 ? "taken: three workgroups per column quad, device held exclusively" : "taken: two workgroups per column quad, device held exclusively") : why;
     }
     // A complex W needs W_i vr(t_n) mid-step: only the split kernels (state role steps ahead) have it; without them the quad-layout kernels.
     if (cq && wfull && !h->wlr_real && adjoint && !cq3) cq = false;
@@ -269,7 +279,7 @@ static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateH
     if (qs_on && quad && !imr && p->spw == 1 && !wfull && qsplit_lds(h, 4) <= JQ_LDS_MAX) p->qs_qw = 4;      // (!imr: the implicit-midpoint quad kernels also run with spw = 1)
     // (option qsplit=2: qw = 2 for every batch of the cooperative-quad plan that does not take the three-workgroup kernels -- tests)
     const bool qs_force2 = qs_set && h->opt.get(O_QSPLIT) == 2;
-    if (qs_on && cq && !cq_dn && !cq3 && !wfull && ((nquads_used > h->num_cu && 2 * p->nslabs <= h->num_cu) || qs_force2) && qsplit_lds(h, 2) <= JQ_LDS_MAX) p->qs_qw = 2;
+    if (qs_on && cq && !cq_dn && !cq3 && !wfull && !grp && ((nquads_used > h->num_cu && 2 * p->nslabs <= h->num_cu) || qs_force2) && qsplit_lds(h, 2) <= JQ_LDS_MAX) p->qs_qw = 2;
     const bool qsplit = p->qs_qw > 0;
     p->qs_blocks = qsplit ? (4 * p->nslabs + p->qs_qw - 1) / p->qs_qw : 0;
     // (full weights: the cooperative kernels sum their column dots through an LDS record behind the Jacobi norms, else the slab kernels serve)
@@ -293,6 +303,13 @@ static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateH
     p->family = imr_rl ? KF_ROWLANE_IMR : imr_cq ? KF_CQ_IMR : imr_quad ? KF_QUAD_IMR : imr_coop ? KF_COOP_IMR : rl ? KF_ROWLANE
               : lane ? KF_LANE : cq ? KF_CQ : quad ? KF_QUAD : coop ? KF_COOP : KF_SLAB;
     p->layout = rl ? SL_ROWLANE : lane ? SL_LANE : SL_SLABS;
+    if (grp) {      // units per vector; only column counts under which the single evaluation has the same layout (bit-identical results)
+        const bool n4 = h->N < 4 || h->N % 4 == 0;
+        if (p->family == KF_ROWLANE && !hist && n4) p->upg = h->N > 4 ? h->N / 4 : 1;
+        else if (p->family == KF_CQ && !hist && (h->parts > 1 || 16 % h->N == 0)) p->upg = h->parts > 1 ? 4 * h->parts : h->N > 4 ? h->N / 4 : 1;
+        if (p->upg == 0) return JQ_OK;      // (p->groups == 0: not served)
+        p->groups = groups;
+    }
     p->coop = coop;
     p->sched = JQ_SCHED[coop];
     p->rl_waves = rl_split3 ? 3 : rl_split ? 2 : 1;
@@ -334,6 +351,15 @@ static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateH
     // (JQ_BW_T4: a v_mfma_f64_4x4x4_4b is a quarter of the 16x16x4 instruction counted; implicit midpoint: data-dependent iteration counts)
     p->mfma_div = imr ? 0 : (!coop && !lane && !rl && h->BW == JQ_BW_T4) ? 4 : 1;
     p->cs = adjoint ? backward_chunk_steps(h, (size_t)p->trace_rows) : h->chunk_steps;
+    if (grp) {
+        // a chunk holds one tile stream per vector, each of THIS family's image size (not the largest image of any family jq_create sized the
+        // buffer by): as many steps as the stream budget holds -- option stream_bytes, default 1 GiB, or the buffer the handle has; run_eval
+        // grows a buffer that option chunk_steps kept below the budget.  Never longer than the single evaluation's chunk.
+        size_t budget = ((size_t)1 << 30) / sizeof(double);
+        if (h->opt.has(O_STREAM_BYTES) && h->opt.get(O_STREAM_BYTES) > 0) budget = (size_t)h->opt.get(O_STREAM_BYTES) / sizeof(double);
+        const long long tps = (long long)(std::max(budget, h->cap_stream) / ((size_t)groups * 2 * (size_t)p->stride));
+        p->cs = (int)std::max<long long>(1, std::min<long long>(p->cs, (tps - 1) / 2));
+    }
     if (cq3 && std::min(p->cs, h->nsteps) <= JQ_CQ3_RING)      // (the decision above was made for this very chunking)
         return fail(h, JQ_EHIP, "internal error: split latency kernels selected for a first chunk that is not longer than their hand-off ring");
     p->prop_nslabs = rl ? (int)p->nwaves_rl : lane ? (int)p->ncols : p->nslabs;

@@ -6,6 +6,8 @@ static int multi_eval_f_g_grad(jq_handle* h, const double* pcof, int ncoeff, con
                                const double* shift, bool adjoint, double* out2, double* infid_grad, double* leak_grad);
 static int multi_traceobj_sweep(jq_handle* h, const double* pcof, int ncoeff, const double* nodes, int nquad, const double* shift,
                                 double* out);
+static int multi_traceobjgrad_batch(jq_handle* h, const double* pcofs, int ncoeff, int npcof, int evaladjoint, double* out4, double* totalgrad,
+                                    double* infidelgrad, double* leakgrad);
 // a single evaluation cannot be sharded: multi-device handles run it on their first device
 #define JQ_ON_FIRST(h, call)                         \
     if (!(h)->subs.empty()) {                        \

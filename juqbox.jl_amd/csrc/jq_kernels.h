@@ -1079,7 +1079,19 @@ struct PropArgs {
     // itself and waits for all the others: co-residency is established before anybody depends on it) and of a wait between roles afterwards
     int rdv_polls;
     int wait_polls;
+    // Grouped batches (jq_traceobjgrad_batch; row-lane and cooperative-quad kernels only): the chunk holds one tile stream per control
+    // vector, `stream_gstride` doubles apart; a workgroup reads the stream of the vector its columns belong to (jq_group_stream).
+    // 0: one stream for everybody.  No other kernel reads this field.
+    long long stream_gstride;
 };
+// The tile stream of the control vector that unit `unit` of the launch (row-lane kernels: wave, cooperative-quad kernels: column quad)
+// works for, `upg` units per vector.  Wave-uniform by construction (block index and kernel arguments); the readfirstlane says so to the
+// compiler, so that the DMA keeps its scalar base.
+__device__ __forceinline__ const double* jq_group_stream(const PropArgs& a, int unit, int upg)
+{
+    const int g = __builtin_amdgcn_readfirstlane(unit / upg);
+    return a.stream + (size_t)g * (size_t)a.stream_gstride;
+}
 #ifndef JQ_MAX_WRANK
 #define JQ_MAX_WRANK 16       // largest rank of a full weight matrix the kernels take (include/juqbox_hip.h)
 #endif

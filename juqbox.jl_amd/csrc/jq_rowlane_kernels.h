@@ -225,9 +225,9 @@ struct RowOps {
     RowMat<NPJ> Kn0, S0, Kp05, S05, Kn1, S1;
 };
 template <int NPJ>
-__device__ __forceinline__ void rops_load_half(RowOps<NPJ>& o, const PropArgs& a, int n, int row)
+__device__ __forceinline__ void rops_load_half(RowOps<NPJ>& o, const PropArgs& a, const double* strm, int n, int row)
 {
-    cmat_t s = as_const(a.stream) + (size_t)(2 * (2 * n + 1)) * a.stride;
+    cmat_t s = as_const(strm) + (size_t)(2 * (2 * n + 1)) * a.stride;
     o.Kp05 = row_load<NPJ>(s, row);
     o.S05 = row_load<NPJ>(s + a.stride, row);
     o.Kn1 = row_load<NPJ>(s + 2 * a.stride, row);
@@ -261,9 +261,9 @@ struct RowOpsV {      // the view a step's code reads its operators through (the
 };
 // half point of step n -> H, integer point t_n+1 -> I
 template <int NPJ>
-__device__ __forceinline__ void rops_load_tp(RowTP<NPJ>& H, RowTP<NPJ>& I, const PropArgs& a, int n, int row)
+__device__ __forceinline__ void rops_load_tp(RowTP<NPJ>& H, RowTP<NPJ>& I, const PropArgs& a, const double* strm, int n, int row)
 {
-    cmat_t s = as_const(a.stream) + (size_t)(2 * (2 * n + 1)) * a.stride;
+    cmat_t s = as_const(strm) + (size_t)(2 * (2 * n + 1)) * a.stride;
     H.K = row_load<NPJ>(s, row);
     H.S = row_load<NPJ>(s + a.stride, row);
     I.K = row_load<NPJ>(s + 2 * a.stride, row);
@@ -273,11 +273,11 @@ __device__ __forceinline__ void rops_load_tp(RowTP<NPJ>& H, RowTP<NPJ>& I, const
     __builtin_amdgcn_sched_barrier(0);
 }
 template <int NPJ>
-__device__ __forceinline__ void rops_first(RowTP<NPJ>& I0, RowTP<NPJ>& H0, RowTP<NPJ>& I1, const PropArgs& a, int row)
+__device__ __forceinline__ void rops_first(RowTP<NPJ>& I0, RowTP<NPJ>& H0, RowTP<NPJ>& I1, const PropArgs& a, const double* strm, int row)
 {
-    I0.K = row_load<NPJ>(as_const(a.stream), row);
-    I0.S = row_load<NPJ>(as_const(a.stream) + a.stride, row);
-    rops_load_tp(H0, I1, a, 0, row);
+    I0.K = row_load<NPJ>(as_const(strm), row);
+    I0.S = row_load<NPJ>(as_const(strm) + a.stride, row);
+    rops_load_tp(H0, I1, a, strm, 0, row);
 }
 // STEP(n, integer point t_n, half point, integer point t_n+1, [load targets:] next half point, integer point t_n+2)
 #define JQ_RL_ROTATE(NSTEPS, STEP)                     \
@@ -366,11 +366,11 @@ struct RlRing {
         ++gi;
         si = (si == R - 1) ? 0 : si + 1;
     }
-    __device__ __forceinline__ void init(const PropArgs& a, double* ring, int lane, int row_)
+    __device__ __forceinline__ void init(const PropArgs& a, const double* strm, double* ring, int lane, int row_)
     {
         lds = ring;
         lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)ring;
-        src = (const char*)a.stream;
+        src = (const char*)strm;
         lo16 = 16u * lane;
         N = a.nsteps_chunk;
         row = row_;
@@ -457,6 +457,12 @@ struct RowW {
 #define JQ_ROWLANE_ARRAYS 4                                   // U, V, MU, NB
 #define JQ_ROWLANE_ROWS (JQ_ROWLANE_ARRAYS + JQ_MAXNC + 1)    // + carry rows + leak row
 
+// Grouped batch: a control vector owns max(1, N / 4) consecutive waves (the host pads the column slots so that no wave holds two vectors)
+__device__ __forceinline__ const double* rl_group_stream(const PropArgs& a)
+{
+    return jq_group_stream(a, (int)blockIdx.x, a.N > 4 ? a.N >> 2 : 1);
+}
+
 // Forward sweep of one chunk; a.nslabs = number of waves (4 columns each), grid = a.nslabs, block = 64.
 // (WF: low-rank full leakage weights compiled in -- separate instantiations, the Diagonal fast path is untouched)
 template <int NPJ, bool WF = false, bool HIST = false>
@@ -475,7 +481,7 @@ __global__ __launch_bounds__(64) void k_forward_rowlane(PropArgs a)
     RowW wl;
     if constexpr (WF) wl.init(a, lds_w, lane, 64);
     RlRing<NPJ, !HIST> ring;
-    ring.init(a, lds_w + (WF ? JQ_RL_WTAB : 0), lane, row);
+    ring.init(a, rl_group_stream(a), lds_w + (WF ? JQ_RL_WTAB : 0), lane, row);
     auto sweep = [&](auto terms) {
     constexpr int MT = decltype(terms)::value;
     for (int n = 0; n < a.nsteps_chunk; ++n) {
@@ -564,9 +570,10 @@ __global__ __launch_bounds__(64) void k_backward_rowlane(PropArgs a)
     if constexpr (WF) wl.init(a, lds_c + (RESIDENT ? 0 : (size_t)2 * Nc * a.stride), lane, 64);
     const double cf0 = a.forced ? 0.5 * a.h * a.tinv : 0.0;
     RowTP<NPJ> I0, I1, I2, H0, H1, H2;
-    rops_first(I0, H0, I1, a, row);
+    const double* strm = rl_group_stream(a);
+    rops_first(I0, H0, I1, a, strm, row);
     auto step = [&](int n, const RowTP<NPJ>& Pa, const RowTP<NPJ>& Ph, const RowTP<NPJ>& Pb, RowTP<NPJ>& Lh, RowTP<NPJ>& Li) {
-        rops_load_tp(Lh, Li, a, min(n + 1, a.nsteps_chunk - 1), row);   // lands during this step
+        rops_load_tp(Lh, Li, a, strm, min(n + 1, a.nsteps_chunk - 1), row);   // lands during this step
         const RowOpsV<NPJ> o{Pa.K, Pa.S, Ph.K, Ph.S, Pb.K, Pb.S};
         double un, v05, vnew;
         row_state<NPJ>(a, o, sw, u, v, un, v05, vnew);
@@ -679,15 +686,16 @@ __global__ __launch_bounds__(128) void k_backward_rowlane2(PropArgs a)
     }
     __syncthreads();
     RowOps<NPJ> o, nxt;
-    o.Kn0 = row_load<NPJ>(as_const(a.stream), row);
-    o.S0 = row_load<NPJ>(as_const(a.stream) + a.stride, row);
-    rops_load_half(o, a, 0, row);
+    const double* strm = rl_group_stream(a);
+    o.Kn0 = row_load<NPJ>(as_const(strm), row);
+    o.S0 = row_load<NPJ>(as_const(strm) + a.stride, row);
+    rops_load_half(o, a, strm, 0, row);
 
     if (role == 0) {
         // ---- state chain: one step ahead of the adjoint chain at most
         double u = st[0], v = st[nw * 64];
         for (int n = 0; n < a.nsteps_chunk; ++n) {
-            rops_load_half(nxt, a, min(n + 1, a.nsteps_chunk - 1), row);
+            rops_load_half(nxt, a, strm, min(n + 1, a.nsteps_chunk - 1), row);
             double un, v05, vnew;
             row_state<NPJ, RowOps<NPJ>, BLK>(a, o, sw, u, v, un, v05, vnew);
             double* r = rec + (n & 1) * 192;
@@ -724,7 +732,7 @@ __global__ __launch_bounds__(128) void k_backward_rowlane2(PropArgs a)
             if (q < Nc) carry[q] = -u0 * rmv<NPJ, true, BLK>(0.0, Hs[q], nb);
     }
     for (int n = 0; n < a.nsteps_chunk; ++n) {
-        rops_load_half(nxt, a, min(n + 1, a.nsteps_chunk - 1), row);
+        rops_load_half(nxt, a, strm, min(n + 1, a.nsteps_chunk - 1), row);
         __syncthreads();          // the state wave has published record n
         const double* r = rec + (n & 1) * 192;
         const double u = r[0], v05 = r[64], un = r[128];
@@ -818,7 +826,7 @@ __global__ __launch_bounds__(256) void k_backward_rowlane3(PropArgs a)
         // ---- state chain
         double u = st[0], v = st[nw * 64];
         RlRing<NPJ> ring;
-        ring.init(a, rings, lane, row);
+        ring.init(a, rl_group_stream(a), rings, lane, row);
         auto sweep = [&](auto terms) {
             constexpr int MT = decltype(terms)::value;
             int slot = 0;
@@ -850,7 +858,7 @@ __global__ __launch_bounds__(256) void k_backward_rowlane3(PropArgs a)
         double mu = st[2 * nw * 64], nb = st[3 * nw * 64];
         const double cfw = (a.forced ? 0.5 * a.h * a.tinv : 0.0) * wd;
         RlRing<NPJ> ring;
-        ring.init(a, rings + JQ_RL_RING_BYTES(NPJ) / 8, lane, row);
+        ring.init(a, rl_group_stream(a), rings + JQ_RL_RING_BYTES(NPJ) / 8, lane, row);
         auto sweep = [&](auto terms) {
             constexpr int MT = decltype(terms)::value;
             int slot = 0;

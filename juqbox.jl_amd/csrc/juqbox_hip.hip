@@ -159,6 +159,13 @@ struct jq_handle {
     double *d_wq = nullptr, *d_pack = nullptr;   // ensemble weights per sample; packed result [2 + 2 nCoeff] (multi-device all-reduce)
     size_t cap_pcof = 0, cap_slabs = 0, cap_traces = 0, cap_grad = 0, cap_res = 0, cap_state = 0, cap_colinfo = 0, cap_wq = 0, cap_pack = 0;
     int chunk_steps = 0;
+    size_t cap_stream = 0, cap_pq = 0, cap_R = 0;      // doubles of d_stream, d_pq, d_R (jq_create sizes them for one control vector; a grouped batch may grow them)
+    // jq_traceobjgrad_batch: the grouped batch run_eval is evaluating -- grp_G control vectors (0: none; pcof then holds grp_G coefficient
+    // blocks), each padded to grp_spg samples (cooperative-quad kernels with N < 4: a column quad per vector, the other columns weigh 0) --
+    // and what the last call did (jq_plan_info "pcof_batch")
+    int grp_G = 0, grp_spg = 1;
+    std::string pb_mode, pb_why;
+    int pb_family = -1, pb_per_launch = 0;
     // Structure embedding (try_embed): a second handle of the SAME problem with its two fastest Kronecker factors zero-padded
     // to 4 levels each (row i1 + d1 i2 + d1 d2 i3 -> i1 + 4 i2 + 16 i3), under which the operators have the JQ_BW_T4 structure;
     // batches that would otherwise run on the dense / band MFMA kernels go there (quad-layout / JQ_BW_T4 slab kernels).
@@ -247,6 +254,116 @@ extern "C" int jq_traceobjgrad(jq_handle* h, const double* pcof, int32_t ncoeff,
             }
         }
     }
+    return JQ_OK;
+}
+
+// What jq_traceobjgrad_batch does with npcof control vectors on this (single-device) handle: the number of vectors per launch of a grouped
+// batch (plan_batch with groups), or 0 -- the vectors one after the other -- with the reason in *why.  *spg: samples a vector is padded to.
+static int pcof_batch_per_launch(jq_handle* h, int npcof, bool adjoint, int* spg, int* family, const char** why)
+{
+    *spg = 1, *family = -1;
+    if (h->opt.has(O_PCOF_BATCH_MAX) && h->opt.get(O_PCOF_BATCH_MAX) <= 0) return *why = "option pcof_batch_max=0", 0;
+    if (npcof == 1) return *why = "one vector: the single evaluation (with the split backward kernels where they apply)", 0;
+    if (h->integrator != 1) return *why = "implicit-midpoint integrator: no grouped streams on its kernels", 0;
+    if (h->solver_id != 1) return *why = "Jacobi solver: served by the slab / cooperative kernels", 0;
+    // Two candidates, in plan_batch's order: row-lane kernels (a vector per wave(s)), cooperative-quad kernels (a vector per column quad(s); a
+    // slab's samples are packed, so with N < 4 a vector brings the padding samples of its quad along).  One vector's workgroups per compute unit;
+    // the candidate stands when the plan of a full launch AND of the last, shorter one choose its family (dry runs: a grouped plan has no side effects).
+    const int N = h->N;
+    *why = "the kernel family of this plan keeps one tile stream per launch (grouped: row-lane and cooperative-quad kernels, column counts 1, 2, 4, 8, 16 or beyond 16)";
+    for (int cand = 0; cand < 2; ++cand) {
+        const bool rl = cand == 0;
+        if (rl && (h->rl_npj == 0 || h->rl_max_cols < N)) continue;
+        const jq_handle* t = (!rl && h->emb) ? h->emb : h;      // (the embedded twin serves what the row-lane kernels do not)
+        const int upg = (!rl && t->parts > 1) ? 4 * t->parts : N > 4 ? (N + 3) / 4 : 1;
+        const int s1 = (!rl && N < 4) ? 4 / N : 1;
+        long long gmax = t->num_cu / upg;
+        if (rl) gmax = std::min<long long>(gmax, h->rl_max_cols / N);
+        else gmax = std::min<long long>(gmax, std::max(t->cq_max_quads, t->dq_max_quads) / upg);
+        if (h->opt.has(O_PCOF_BATCH_MAX)) gmax = std::min<long long>(gmax, h->opt.get(O_PCOF_BATCH_MAX));
+        gmax = std::min<long long>(gmax, npcof);
+        if (gmax < 1) continue;
+        bool ok = true;
+        for (int G : {(int)gmax, npcof % (int)gmax}) {
+            if (G == 0) continue;
+            GateHold hold;
+            BatchPlan p;
+            if (plan_batch(eval_target(h, G * s1, false), G * s1, adjoint, false, hold, &p, G) != JQ_OK) return *why = "the batch plan refuses this evaluation (the single call reports why)", 0;
+            if (G == (int)gmax) *family = (int)p.family;
+            ok = ok && p.groups == G && p.upg == upg && p.family == (rl ? KF_ROWLANE : KF_CQ);
+        }
+        if (!ok) continue;
+        *spg = s1;
+        *why = rl ? "row-lane kernels: a control vector per wave(s)" : "cooperative-quad kernels: a control vector per column quad(s)";
+        return (int)gmax;
+    }
+    return 0;
+}
+
+extern "C" int jq_traceobjgrad_batch(jq_handle* h, const double* pcofs, int32_t ncoeff, int32_t npcof, int32_t evaladjoint, double* out4,
+                                     double* totalgrad, double* infidelgrad, double* leakgrad)
+{
+    if (!h) return JQ_EINVAL;
+    if (!pcofs || !out4) return fail(h, JQ_EINVAL, "jq_traceobjgrad_batch: NULL pointer");
+    if (evaladjoint && (!totalgrad || !infidelgrad || !leakgrad))
+        return fail(h, JQ_EINVAL, "jq_traceobjgrad_batch: gradient outputs are required when evaladjoint != 0");
+    if (npcof < 1) return fail(h, JQ_EINVAL, "jq_traceobjgrad_batch: npcof must be >= 1");
+    if (!h->subs.empty()) return multi_traceobjgrad_batch(h, pcofs, ncoeff, npcof, evaladjoint, out4, totalgrad, infidelgrad, leakgrad);
+    int rc = check_ncoeff(h, ncoeff);      // (before anything is written)
+    if (rc) return rc;
+    const bool adjoint = evaladjoint != 0;
+    int spg = 1, family = -1;
+    const char* why = "";
+    const int per = pcof_batch_per_launch(h, npcof, adjoint, &spg, &family, &why);
+    h->pb_mode = per > 0 ? "grouped" : "sequential", h->pb_why = why, h->pb_family = family, h->pb_per_launch = per > 0 ? per : 1;
+    // column i of the outputs from the evaluation's record
+    auto put = [&](int i, const double* res, const double* g0, const double* g1) {
+        const double primary = res[0], secondary = res[1];
+        double* o4 = out4 + (size_t)4 * i;
+        o4[0] = primary + secondary;  // objfv (src/evalobjgrad.jl:765-766)
+        o4[1] = primary;
+        o4[2] = secondary;
+        o4[3] = primary;              // traceInfidelity == 1 - |s|^2 for pFidType 2 (:792)
+        if (!adjoint) return;
+        double *tg = totalgrad + (size_t)ncoeff * i, *ig = infidelgrad + (size_t)ncoeff * i, *lg = leakgrad + (size_t)ncoeff * i;
+        for (int k = 0; k < ncoeff; ++k) {
+            tg[k] = g0[k];
+            ig[k] = h->objFuncType != 1 ? g1[k] : g0[k];             // :951
+            lg[k] = h->objFuncType != 1 ? g0[k] - g1[k] : 0.0;      // :947
+        }
+    };
+    jq_timing tsum = {};
+    auto add_timing = [&](const jq_timing& t) {
+        const double keep[] = {tsum.ms_total, tsum.ms_propagate, tsum.ms_generate, tsum.ms_forward, tsum.ms_backward};
+        const long long keepn[] = {tsum.n_forward_launches, tsum.n_backward_launches, tsum.mfma_executed, tsum.mfma_backward, tsum.svts};
+        tsum = t;      // (family, size, band, variant: those of the last launch)
+        tsum.ms_total += keep[0], tsum.ms_propagate += keep[1], tsum.ms_generate += keep[2], tsum.ms_forward += keep[3], tsum.ms_backward += keep[4];
+        tsum.n_forward_launches += keepn[0], tsum.n_backward_launches += keepn[1], tsum.mfma_executed += keepn[2], tsum.mfma_backward += keepn[3], tsum.svts += keepn[4];
+        tsum.ms_shard_min = tsum.ms_shard_max = tsum.ms_total;
+    };
+    if (per <= 0) {      // every route without grouped streams: the single evaluation, vector by vector
+        for (int i = 0; i < npcof; ++i) {
+            EvalOut o;
+            if ((rc = run_eval(h, pcofs + (size_t)ncoeff * i, ncoeff, 1, nullptr, nullptr, nullptr, adjoint, nullptr, nullptr, &o))) return rc;
+            put(i, o.res.data(), o.grad0.data(), o.grad1.data());
+            add_timing(h->timing);
+        }
+        h->timing = tsum;
+        return JQ_OK;
+    }
+    for (int i0 = 0; i0 < npcof; i0 += per) {      // rounds of at most `per` vectors (results do not depend on the round a vector runs in)
+        const int G = std::min(per, npcof - i0);
+        EvalOut o;
+        h->grp_G = G, h->grp_spg = spg;
+        rc = run_eval(h, pcofs + (size_t)ncoeff * i0, ncoeff, G * spg, nullptr, nullptr, nullptr, adjoint, nullptr, nullptr, &o);
+        h->grp_G = 0, h->grp_spg = 1;
+        if (rc) return rc;
+        for (int g = 0; g < G; ++g)
+            put(i0 + g, o.res.data() + (size_t)4 * g * spg, adjoint ? o.grad0.data() + (size_t)ncoeff * g : nullptr,
+                (adjoint && h->objFuncType != 1) ? o.grad1.data() + (size_t)ncoeff * g : nullptr);
+        add_timing(h->timing);
+    }
+    h->timing = tsum;
     return JQ_OK;
 }
 

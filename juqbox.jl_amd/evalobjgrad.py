@@ -8,6 +8,11 @@
   traceobjgrad(pcof0, params, wa, verbose=False, evaladjoint=True)
                                         same argument order and return tuples as
                                         src/evalobjgrad.jl:504, :1027-1036.
+  traceobjgrad_batch(pcofs, params, wa, evaladjoint=True)
+                                        many control vectors of ONE problem in one library call
+                                        (jq_traceobjgrad_batch): column i = traceobjgrad of vector i.
+  gradient_check(pcof0, params, wa, kpars, h=1e-6)
+                                        adjoint gradient entries against central differences, from one batch.
 """
 import contextlib
 import ctypes
@@ -311,7 +316,8 @@ def traceobjgrad(pcof0, params: objparams, wa: Working_Arrays_HIP, verbose: bool
                                 infidelgrad, leakgrad)                                     (:1033)
     neither:                   (objfv, primaryobjf, secondaryobjf)                         (:1035)
     verbose (not evaladjoint): (objfv, unitaryhistory[Ntot,N,nsteps+1] complex, fidelity)  (:1031)
-    verbose and evaladjoint (the reference's forward-sensitivity self check, :1028) is out of scope.
+    verbose and evaladjoint (the reference's forward-sensitivity self check, :1028) is out of scope; gradient_check() below is its
+    accelerated stand-in (adjoint entries against central differences, all from one traceobjgrad_batch call).
     objfv excludes the Tikhonov term (added by the Ipopt callbacks, src/ipopt_interface.jl:96-98).
     """
     if not isinstance(wa, Working_Arrays_HIP):
@@ -341,3 +347,80 @@ def traceobjgrad(pcof0, params: objparams, wa: Working_Arrays_HIP, verbose: bool
         return out4[0], tg, out4[1], out4[2], out4[3], ig, lg
     _lib.check(L.jq_traceobjgrad(h, _ptr(pcof), n, 0, _ptr(out4), None, None, None), h)
     return out4[0], out4[1], out4[2]
+
+
+def _pcof_columns(pcofs, ncoeff):
+    """pcofs -> contiguous [npcof, ncoeff] array (one vector per row = the C ABI's column-major ncoeff x npcof).  A 2-D array holds one
+    vector per COLUMN, a sequence one vector per element, a 1-D array is one vector.  ValueError for everything else."""
+    if isinstance(pcofs, np.ndarray):
+        if pcofs.ndim == 1:
+            cols = [pcofs]
+        elif pcofs.ndim == 2:
+            cols = [pcofs[:, i] for i in range(pcofs.shape[1])]
+        else:
+            raise ValueError("traceobjgrad_batch: pcofs must be an ncoeff x npcof array or a sequence of vectors, not %d-dimensional" % pcofs.ndim)
+    else:
+        try:
+            cols = [np.asarray(c, dtype=np.float64) for c in pcofs]
+        except (TypeError, ValueError) as e:
+            raise ValueError("traceobjgrad_batch: pcofs must be an ncoeff x npcof array or a sequence of vectors (%s)" % e)
+    if len(cols) == 0:
+        raise ValueError("traceobjgrad_batch: need at least one control vector")
+    for i, c in enumerate(cols):
+        if np.ndim(c) != 1 or np.size(c) != ncoeff:
+            raise ValueError("traceobjgrad_batch: control vector %d has shape %r, expected (%d,) (wa.nCoeff)" % (i, np.shape(c), ncoeff))
+    return np.ascontiguousarray(np.stack([np.asarray(c, dtype=np.float64) for c in cols]))
+
+
+def traceobjgrad_batch(pcofs, params: objparams, wa: Working_Arrays_HIP, evaladjoint: bool = True):
+    """npcof independent evaluations traceobjgrad(pcofs[:, i], params, wa, False, evaladjoint) of ONE problem in one library call
+    (jq_traceobjgrad_batch).  On the row-lane and cooperative-quad (latency) kernels with the Stormer-Verlet integrator the vectors share
+    launches -- every workgroup reads the operator stream of its own vector --, everywhere else they run one after the other inside
+    the call (wa.plan_info()["pcof_batch"] says which).  Column i is bit-identical to the single call's result on the same kernel variant.
+
+    pcofs: an ncoeff x npcof array (one vector per column) or a sequence of equal-length vectors.
+    evaladjoint: (objfv[n], totalgrad[ncoeff, n], primaryobjf[n], secondaryobjf[n], traceInfidelity[n], infidelgrad[ncoeff, n],
+                  leakgrad[ncoeff, n] -- 0 x n for objFuncType == 1, like the single call's empty vector)
+    else:        (objfv[n], primaryobjf[n], secondaryobjf[n])
+    Shape errors raise ValueError before any library call."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("traceobjgrad_batch: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("traceobjgrad_batch: wa was allocated for a different objparams")
+    ncoeff = int(wa.nCoeff)
+    P = _pcof_columns(pcofs, ncoeff)
+    n = P.shape[0]
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    out4 = np.zeros((n, 4))
+    if not evaladjoint:
+        _lib.check(L.jq_traceobjgrad_batch(h, _ptr(P), ncoeff, n, 0, _ptr(out4), None, None, None), h)
+        return out4[:, 0].copy(), out4[:, 1].copy(), out4[:, 2].copy()
+    tg, ig, lg = np.zeros((n, ncoeff)), np.zeros((n, ncoeff)), np.zeros((n, ncoeff))
+    _lib.check(L.jq_traceobjgrad_batch(h, _ptr(P), ncoeff, n, 1, _ptr(out4), _ptr(tg), _ptr(ig), _ptr(lg)), h)
+    leak = np.zeros((0, n)) if params.objFuncType == 1 else np.ascontiguousarray(lg.T)
+    return (out4[:, 0].copy(), np.ascontiguousarray(tg.T), out4[:, 1].copy(), out4[:, 2].copy(), out4[:, 3].copy(),
+            np.ascontiguousarray(ig.T), leak)
+
+
+def gradient_check(pcof0, params: objparams, wa: Working_Arrays_HIP, kpars, h: float = 1e-6):
+    """The adjoint gradient against central differences: returns (totalgrad[kpars], fd) with
+    fd[j] = (f(p + h e_k) - f(p - h e_k)) / 2h for k = kpars[j], f = objfv.  All 2 len(kpars) + 1 evaluations are ONE
+    traceobjgrad_batch call (vector 0: p itself, then the + and - vector of every k).  The accelerated stand-in for the reference's
+    `verbose && evaladjoint` self check, which traceobjgrad refuses."""
+    p0 = np.asarray(pcof0, dtype=np.float64).ravel()
+    ks = [int(k) for k in np.atleast_1d(kpars)]
+    if p0.size != int(wa.nCoeff):
+        raise ValueError("gradient_check: pcof0 has %d elements, wa.nCoeff = %d" % (p0.size, wa.nCoeff))
+    for k in ks:
+        if not 0 <= k < p0.size:
+            raise ValueError("gradient_check: index %d outside 0 .. %d" % (k, p0.size - 1))
+    vecs = [p0]
+    for k in ks:
+        for sgn in (1.0, -1.0):
+            v = p0.copy()
+            v[k] += sgn * h
+            vecs.append(v)
+    objfv, tg = traceobjgrad_batch(vecs, params, wa, True)[:2]
+    fd = np.array([(objfv[1 + 2 * j] - objfv[2 + 2 * j]) / (2.0 * h) for j in range(len(ks))])
+    return tg[ks, 0].copy(), fd
