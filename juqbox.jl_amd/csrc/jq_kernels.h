@@ -224,6 +224,13 @@ __device__ __forceinline__ void a_axpy_rows1(Arr<NT>& y, const double* tab, int 
     for (int i = 0; i < NT; ++i) y.t[i] += jq_row(NEG ? -t4[4 * i] : t4[4 * i]) * x.t[i];
 #endif
 }
+// y += (+-) cw .* x   (quad layout: cw[i] = c * tab[16 i + g] of a_axpy_rows, formed once by the caller; (-c) t = -(c t) exactly)
+template <int NT, bool NEG>
+__device__ __forceinline__ void a_axpy_cw(Arr<NT>& y, const double* cw, const Arr<NT>& x)
+{
+#pragma unroll
+    for (int i = 0; i < NT; ++i) y.t[i][0] = fma(NEG ? -cw[i] : cw[i], x.t[i][0], y.t[i][0]);
+}
 // sum_rows tab[row] * x[row]^2
 template <int NT>
 __device__ __forceinline__ double a_wsq(const double* tab, int g, const Arr<NT>& x)
@@ -740,6 +747,43 @@ __device__ __forceinline__ void mm_t4q3(Arr<NT>& D0, const Arr<NT>& C0, const do
 {
     mm_t4q_multi<NT, 3, Z0, Z1, Z2, SH, T4qNoHook, SCM>(D0, C0, m0, D1, C1, m1, D2, C2, m2, x, sh0, sh1, sh2, wsr);
 }
+// Two products with the SAME operator (a K image with the folded shift, see mm_t4q SH) and two right-hand sides in one pass over the
+// blocks: D_k = C_k + M' x_k.  The A operand and the coefficients of a block are fetched -- and the shift folded -- once; each
+// accumulator chain keeps the order of t4q_block (MFMA, c0, c1, c2, c3).  x_k must not alias a D_j.
+template <int NT, bool Z0, bool Z1>
+__device__ __forceinline__ void mm_t4q_2rhs(Arr<NT>& D0, const Arr<NT>& C0, const Arr<NT>& x0, Arr<NT>& D1, const Arr<NT>& C1,
+                                            const Arr<NT>& x1, const double* mat, double shd, const double* wsr)
+{
+    const int lane = threadIdx.x & 63;
+    const double* ma = t4q_a(mat, lane);
+    const d4* cf = t4q_c<NT>(mat, lane);
+    double xold0 = 0.0, xold1 = 0.0;
+#pragma unroll
+    for (int mt = 0; mt < NT; ++mt) {
+        const double a = fma(shd, wsr[16 * mt], ma[mt * 64]);
+        const d4 c = t4q_cload(cf, mt);
+        const double xc0 = x0.t[mt][0], xc1 = x1.t[mt][0];
+        double acc0 = Z0 ? 0.0 : C0.t[mt][0], acc1 = Z1 ? 0.0 : C1.t[mt][0];
+        acc0 = __builtin_amdgcn_mfma_f64_4x4x4f64(a, xc0, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f64_4x4x4f64(a, xc1, acc1, 0, 0, 0);
+        acc0 = fma(c[0], row_shift4<0x114>(xc0), acc0);
+        acc1 = fma(c[0], row_shift4<0x114>(xc1), acc1);
+        acc0 = fma(c[1], row_shift4<0x104>(xc0), acc0);
+        acc1 = fma(c[1], row_shift4<0x104>(xc1), acc1);
+        if (mt > 0) {
+            acc0 = fma(c[2], xold0, acc0);
+            acc1 = fma(c[2], xold1, acc1);
+        }
+        if (mt + 1 < NT) {
+            acc0 = fma(c[3], x0.t[mt + 1 < NT ? mt + 1 : mt][0], acc0);
+            acc1 = fma(c[3], x1.t[mt + 1 < NT ? mt + 1 : mt][0], acc1);
+        }
+        xold0 = xc0, xold1 = xc1;
+        D0.t[mt][0] = acc0;
+        D1.t[mt][0] = acc1;
+        __builtin_amdgcn_sched_barrier(0);      // (fence per block, see mm_t4q_multi)
+    }
+}
 // the same with the operator in registers (the m + 1 products of a Horner chain share it: no LDS latency at their heads)
 template <int NT>
 __device__ __forceinline__ void t4q_load(OpQ<NT>& op, const double* mat)
@@ -983,6 +1027,21 @@ __device__ __forceinline__ void row_swap16(double& a, double& b)
     const jq_u2 hi = __builtin_amdgcn_permlane16_swap(x.u[1], y.u[1], false, false);
     x.u[0] = lo[0], y.u[0] = lo[1], x.u[1] = hi[0], y.u[1] = hi[1];
     a = x.d, b = y.d;
+}
+// (the two halves of wave_sum4: a pair that has to wait for its partner waits as ONE register pair)
+__device__ __forceinline__ double wave_sum4_half(double a, double b)
+{
+    row_swap32(a, b);
+    return a + b;      // rows: a0+a2, a1+a3, b0+b2, b1+b3
+}
+__device__ __forceinline__ double wave_sum4_join(double p, double q)      // p = half(a, b), q = half(c, d)
+{
+    row_swap16(p, q);
+    double r = p + q;
+    r = row_ror_add<8>(r);
+    r = row_ror_add<4>(r);
+    r = row_ror_add<2>(r);
+    return row_ror_add<1>(r);
 }
 __device__ __forceinline__ double wave_sum4(double a, double b, double c, double d)
 {
@@ -1809,6 +1868,18 @@ __device__ __forceinline__ void a_unpark(Arr<NT>& a, const double* park)
 #ifndef JQ_BWD_ADJ_FUSE   // adjoint step: K0 X and K1 X in one pass
 #define JQ_BWD_ADJ_FUSE 1
 #endif
+// Per-step trims of the three-slab quad-layout kernels: work outside the products that computed a value twice or reduced with half-empty
+// registers.  Same floating-point operations on the same values in the same order -- results bit-identical (tests/test_gpu_step_trim.py).
+//   bit 0: forward, the leak integrand tr(vr' W vr) of the new state is carried to the next step instead of being formed again
+//   bit 1: forward, ceps * ws[row] of this lane's rows is formed once in front of the time loop (four times six multiplies and LDS reads per step)
+//   bit 2: backward (ORD), the early trace sums of the controls 0 and 1 share one wave_sum4 (five calls a step instead of six at
+//          Ncoupled = 3, three instead of four at 2)
+//   bit 3: backward (UNI), use 6: the two products with K05 (vN += K05 un, L = K05 nb) in one pass -- operand fetched and shift-folded once
+// Measured one at a time against -DJQ_STEP_TRIM=0 (cnot3 x 3 072 samples, profiles/step_trim_ab.txt): bit 0 + 0.4 %, bit 1 + 0.6 %,
+// bit 2 + 1.1 %, bit 3 - 0.3 % (the pass without mm_t4q's one-block-ahead operand prefetch loses what the six FMAs save): off by default.
+#ifndef JQ_STEP_TRIM
+#define JQ_STEP_TRIM 7
+#endif
 #ifndef JQ_BWD3_NOOPQ     // twelve-wave backward kernel: Neumann recurrences of the ADJOINT step with the operator re-read from LDS per product
 #define JQ_BWD3_NOOPQ 0
 #endif
@@ -1825,11 +1896,13 @@ __device__ __forceinline__ void a_unpark(Arr<NT>& a, const double* park)
 // FOLD (quad layout, one sample per wave): `ceps` is the per-lane MASKED shift (+c eps on the lanes that hold the diagonal of the MFMA's
 // A operand, 0 elsewhere; 0 everywhere without a shift) and every product with a K image folds it into its operand (mm_t4q SH)
 // SC (quad layout, fused passes): the S images are uniform (s_image_uniform) -- their products take the compact operand (OpS, mm_t4s)
-template <int NT, int BW, bool JAC, int FUSE = 0, bool FOLD = false, bool REGOP = true, bool TERMS = false, typename RING = RingT<BW == JQ_BW_T4Q>, bool SC = false>
+// CW (quad layout, fused passes without FOLD): cw[i] = ceps * ws[16 i + g], formed by the caller once per launch (JQ_STEP_TRIM bit 1)
+template <int NT, int BW, bool JAC, int FUSE = 0, bool FOLD = false, bool REGOP = true, bool TERMS = false, typename RING = RingT<BW == JQ_BW_T4Q>, bool SC = false, bool CW = false>
 __device__ __forceinline__ void sv_state(RING& p, const PropArgs& a, bool active, double ceps, const double* ws, int g,
                                          const Arr<NT>& u, Arr<NT>& v, Arr<NT>& unew, Arr<NT>& vN, Arr<NT>& A, Arr<NT>& Ya,
-                                         Arr<NT>& Yb)
+                                         Arr<NT>& Yb, const double* cw = nullptr)
 {
+    static_assert(!CW || (BW == JQ_BW_T4Q && !JAC && FUSE != 0 && !FOLD), "CW: the fused quad-layout step with the shift applied to the results");
     static_assert(!SC || (BW == JQ_BW_T4Q && !JAC && FUSE == 3 && REGOP), "SC: the fused quad-layout step");
     if constexpr (BW == JQ_BW_T4Q && !JAC && FUSE != 0) {
         // Quad layout (always window staging: every image of the step is resident, the order of the uses is free): the products
@@ -1850,7 +1923,10 @@ __device__ __forceinline__ void sv_state(RING& p, const PropArgs& a, bool active
                 mm_z<NT, BW>(A, M0, u);
                 mm_c<NT, BW>(unew, u, M1, u);
             }
-            if (a.use_shift) a_axpy_rows(A, ceps, ws, g, u);
+            if (a.use_shift) {
+                if constexpr (CW) a_axpy_cw<NT, false>(A, cw, u);
+                else a_axpy_rows(A, ceps, ws, g, u);
+            }
             }
         }
         M0 = p.template next_ks<1, 1>();                    // S05
@@ -1874,8 +1950,13 @@ __device__ __forceinline__ void sv_state(RING& p, const PropArgs& a, bool active
                 mm_z<NT, BW>(A, M2, v);
             }
             if (a.use_shift) {
-                a_axpy_rows(unew, -ceps, ws, g, v);
-                a_axpy_rows(A, -ceps, ws, g, v);
+                if constexpr (CW) {
+                    a_axpy_cw<NT, true>(unew, cw, v);
+                    a_axpy_cw<NT, true>(A, cw, v);
+                } else {
+                    a_axpy_rows(unew, -ceps, ws, g, v);
+                    a_axpy_rows(A, -ceps, ws, g, v);
+                }
             }
             }
         }
@@ -2000,11 +2081,17 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
 
     // one time step: (u, v) -> (unew, vN); v is consumed (becomes v05).  The two array pairs swap
     // roles every step, so the loop body is written for two steps and nothing is ever copied.
+    // (three slabs per workgroup, JQ_STEP_TRIM -- LKC: lw = tr(vr' W vr) of the state a step starts from, carried from the step before;
+    //  CWH: cw = ceps * ws of this lane's rows)
+    constexpr bool TRIM3 = QUAD && MINW == 3 && !JAC && !UNI && JQ_FWD_FUSE != 0;
+    constexpr bool LKC = TRIM3 && (JQ_STEP_TRIM & 1), CWH = TRIM3 && (JQ_STEP_TRIM & 2);
+    double lw = 0.0;
+    double cw[CWH ? NT : 1] = {};
 #define JQ_FWD_STEP(U, V, UN, VN, NSTEP)                                                                         \
     {                                                                                                            \
         p.begin_step(NSTEP);                                                                                     \
-        if (active) leak += a_wsq(wd, g, U); /* trapezoidal part: tr(vr' W vr) at t_n (:700) */                  \
-        sv_state<NT, BW, JAC, JQ_FWD_FUSE, UNI, true, false, RingT<QUAD>, SC>(p, a, active, ceps, ws, g, U, V, UN, VN, A, Ya, Yb); \
+        if (active) leak += LKC ? lw : a_wsq(wd, g, U); /* trapezoidal part: tr(vr' W vr) at t_n (:700) */       \
+        sv_state<NT, BW, JAC, JQ_FWD_FUSE, UNI, true, false, RingT<QUAD>, SC, CWH>(p, a, active, ceps, ws, g, U, V, UN, VN, A, Ya, Yb, cw); \
         /* use 6: Kp05 again -- v(t+h) = v05 + c (K05 u_new + S05 v05) */                                        \
         const double* M6 = p.template next_ks<0, 1>();                                                                             \
         if (active) {                                                                                            \
@@ -2012,10 +2099,14 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
                 mm_t4q<NT, false, JQ_T4_DIAG | JQ_T4_RTERMS | JQ_T4_MTERMS, true>(VN, VN, M6, UN, ceps, ws + g);   \
             } else {                                                                                             \
                 mm_c<NT, BW>(VN, VN, M6, UN);                                                                    \
-                if (a.use_shift) a_axpy_rows(VN, ceps, ws, g, UN);                                               \
+                if (a.use_shift) {                                                                               \
+                    if constexpr (CWH) a_axpy_cw<NT, false>(VN, cw, UN);                                         \
+                    else a_axpy_rows(VN, ceps, ws, g, UN);                                                       \
+                }                                                                                                \
             }                                                                                                    \
             /* leak integrand: tr(vr' W vr + 2 vi05' W vi05) after the step (:716, penalf2a :2170-2180) */       \
-            leak += a_wsq(wd, g, UN) + 2.0 * a_wsq(wd, g, V);                                                    \
+            lw = a_wsq(wd, g, UN);                                                                               \
+            leak += lw + 2.0 * a_wsq(wd, g, V);                                                                  \
             if constexpr (WLR)                                                                                   \
                 if (wl.r > 0) {   /* full weights: tr(vr' Wr vr) at t_n and t_n+1, 2 tr(vi05' Wr vi05), -2 tr(vi05' Wi vr(t_n)) (:700, :716-718) */ \
                     double lk = 0.0;                                                                             \
@@ -2040,6 +2131,13 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
                 wl.dots(k, ua, p0, q0);
                 wl.put(k, 0, p0), wl.put(k, 1, q0);
             }
+    if (active) {      // (the row tables are complete behind the barrier of p.init)
+        if constexpr (LKC) lw = a_wsq(wd, g, ua);      // the first step of the chunk
+        if constexpr (CWH) {
+#pragma unroll
+            for (int i = 0; i < NT; ++i) cw[i] = ceps * ws[16 * i + g];
+        }
+    }
     int n = 0;
     for (; n + 1 < a.nsteps_chunk; n += 2) {
         JQ_FWD_STEP(ua, va, ub, vb, n)
@@ -2140,6 +2238,13 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
     // [workgroups][steps][ntr] instead of [waves][steps][ntr] (12 x less traffic with three slabs per workgroup).
     const int ntr = Nc * JQ_NTR;
     double* rec = carry + Nc * NTHREADS + (a.park_lds ? (size_t)NWAVES * (JQ_RL * NT) * 64 : 0);
+    // PK (ORD with three slabs per workgroup, JQ_STEP_TRIM bit 2): the early values t1, t3 of the controls 0 and 1 share ONE wave_sum4
+    // (slots 0, 2 and 1, 3; control 2: slots 4, 6 of a call of its own), the late groups follow, one per control as above: five calls a step
+    // instead of six at Ncoupled = 3, three instead of four at 2.  wave_sum4 adds every slot the same way, (x0 + x2) + (x1 + x3) and the
+    // same rotate-adds: the sums do not depend on the slot.  Same allocation (rslots), same HBM record.
+    // (Letting the early pair of control 2 wait for the first late call -- four calls -- keeps two partial dots alive through the adjoint
+    //  step: 12 B of scratch in the 168-register SC kernel, not kept.)
+    constexpr bool PK = ORD && MINW == 3 && (JQ_STEP_TRIM & 4);
     const int rslots = 8 * Nc;
     for (int i = threadIdx.x; i < 2 * NWAVES * rslots; i += blockDim.x) rec[i] = 0.0;   // (inactive waves never write theirs)
     auto flush_traces = [&](int k) {
@@ -2152,7 +2257,8 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
             // trace kk of control q: t1, t3 (kk = 0, 2) are the values a, b of the control's early group, t2, t4, t5
             // (kk = 1, 3, 4) the values a, b, c of its late group
             const int q = lane_ / JQ_NTR, kk = lane_ - q * JQ_NTR;
-            const int slot = (kk == 0 ? 0 : kk == 2 ? 2 : 4 * Nc + (kk == 1 ? 0 : kk == 3 ? 2 : 1)) + 4 * q;
+            const int slot = PK ? ((kk == 0 || kk == 2) ? (q == 1 ? 1 : 4 * (q >> 1)) + kk : 4 * ((Nc + 1) >> 1) + 4 * q + (kk == 1 ? 0 : kk == 3 ? 1 : 2))
+                                : (kk == 0 ? 0 : kk == 2 ? 2 : 4 * Nc + (kk == 1 ? 0 : kk == 3 ? 2 : 1)) + 4 * q;
             const double* r = rec + (size_t)(k & 1) * NWAVES * rslots + slot;
             double s = r[0];
 #pragma unroll
@@ -2237,8 +2343,12 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
         if (active) {
             if constexpr (UNI) {
                 constexpr int FULLQ = JQ_T4_DIAG | JQ_T4_RTERMS | JQ_T4_MTERMS;
-                mm_t4q<NT, false, FULLQ, true>(vN, vN, M, un, ceps, ws + g);
-                mm_t4q<NT, true, FULLQ, true>(L, L, M, nb, ceps, ws + g);
+                if constexpr (MINW == 3 && (JQ_STEP_TRIM & 8)) {
+                    mm_t4q_2rhs<NT, false, true>(vN, vN, un, L, L, nb, M, ceps, ws + g);
+                } else {
+                    mm_t4q<NT, false, FULLQ, true>(vN, vN, M, un, ceps, ws + g);
+                    mm_t4q<NT, true, FULLQ, true>(L, L, M, nb, ceps, ws + g);
+                }
             } else {
                 mm_c<NT, BW>(vN, vN, M, un);
                 if (a.use_shift) a_axpy_rows(vN, ceps, ws, g, un);
@@ -2270,6 +2380,7 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
         }
         // early traces with X (lets vr0 = u die here): tr1 = tr(vr0' Hanti_q X), tr3 = tr(vr' Hanti_q X)
         double o_p4 = 0.0;      // ORD: the new part of tr4 of control 1, formed in the pass of use 11
+        double pk = 0.0;      // PK: the half-reduced pair of control 0 waits for that of control 1
         for (int q = 0; q < Nc; ++q) {
             M = p.next_c(Nc + q);  // Hanti_q
             if (active) {
@@ -2279,6 +2390,21 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
                     else mm_t4q<NT, true, JQ_T4_MTERMS>(Ya, Ya, M, mu);
                 } else {
                     mm_z_bw<NT, BW>(Ya, M, mu, a.bw_trace[q]);
+                }
+                if constexpr (PK) {
+                    const double d1 = a_dot(u, Ya), d3 = a_dot(un, Ya);
+                    const double hp = wave_sum4_half(d1, d3);
+                    if (q == 0) {
+                        pk = hp;
+                    } else {
+                        // rows 0, 2, 1, 3 = slots 0 .. 3: t1, t3 of control 0, t1, t3 of control 1;  slots 4, 6: of control 2
+                        const double ts = (q == 1 ? wave_sum4_join(pk, hp) : wave_sum4_join(hp, wave_sum4_half(0.0, 0.0))) * wgt;
+                        // (row: formed here -- as a loop-invariant address it costs the 168-register kernel a spilled register)
+                        int row = lane_ >> 4;
+                        asm volatile("" : "+v"(row));
+                        if ((lane_ & 15) == 0) rec[((size_t)(n & 1) * NWAVES + wave) * rslots + 4 * (q - 1) + row] = ts;
+                    }
+                    continue;
                 }
                 // (UNI: the weight of the wave's one sample multiplies the SUMS)
                 const double ts = UNI ? wave_sum4(a_dot(u, Ya), a_dot(un, Ya), 0.0, 0.0) * wgt
@@ -2423,6 +2549,13 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
                 }
                 t4 = p4 + carry[q * NTHREADS + threadIdx.x];
                 carry[q * NTHREADS + threadIdx.x] = p4;
+                if constexpr (PK) {
+                    const double ts = wave_sum4_rows(t2, t4, t5, 0.0) * wgt;
+                    int row = lane_ >> 4;
+                    asm volatile("" : "+v"(row));
+                    if ((lane_ & 15) == 0) rec[((size_t)(n & 1) * NWAVES + wave) * rslots + 4 * (((Nc + 1) >> 1) + q) + row] = ts;
+                    continue;
+                }
                 const double ts = UNI ? wave_sum4(t2, t4, t5, 0.0) * wgt : wave_sum4(t2 * wgt, t4 * wgt, t5 * wgt, 0.0);   // rows 0, 2, 1: t2, t4, t5
                 if ((lane_ & 15) == 0) rec[((size_t)(n & 1) * NWAVES + wave) * rslots + 4 * (Nc + q) + (lane_ >> 4)] = ts;
             }
@@ -2438,10 +2571,17 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
     p.drain();
     flush_traces(a.nsteps_chunk - 1);
     if (active) {
-        a_store(u, st, lane);
-        a_store(v, st + KT * 64, lane);
-        a_store(mu, st + 2 * KT * 64, lane);
-        a_store(nb, st + 3 * KT * 64, lane);
+        int lane_s = lane;
+        if constexpr (PK) {
+            // (the image offset formed again: kept from the top of the kernel it is the register that spills -- 8 B of scratch)
+            int l = lane_;
+            asm volatile("" : "+v"(l));
+            lane_s = ((l >> 2) & 3) * 64 + 16 * (l >> 4) + 4 * (wave & 3) + (l & 3);
+        }
+        a_store(u, st, lane_s);
+        a_store(v, st + KT * 64, lane_s);
+        a_store(mu, st + 2 * KT * 64, lane_s);
+        a_store(nb, st + 3 * KT * 64, lane_s);
         for (int q = 0; q < Nc; ++q) {
             double cv = carry[q * NTHREADS + threadIdx.x];
             if constexpr (QUAD) cv = row_ror_add<8>(row_ror_add<4>(cv));   // only ever used summed over the rows of a column
