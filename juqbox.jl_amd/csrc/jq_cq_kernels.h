@@ -462,17 +462,12 @@ struct CqW {
     template <int NT>
     __device__ __forceinline__ void put(int vec, int blk, int lane_, double x) const
     {
-#ifndef JQ_EXP_W_NOPUT      // (timing experiment: wrong results)
         wpart[((size_t)vec * NT + blk) * 64 + lane_] = part(x);
-#endif
     }
     // sum_k coef_k[my row] (slot_k . x)[my column] -- behind the barrier that follows the put()s
     template <int NT>
     __device__ __forceinline__ double apply(int vec, int lane_, double cA) const
     {
-#ifdef JQ_EXP_W_NOAPPLY     // (timing experiment: wrong results)
-        return cA;
-#endif
         const double* r = wpart + (size_t)vec * NT * 64 + lane_;
         double d = r[0];
 #pragma unroll

@@ -124,9 +124,6 @@ template __global__ void k_forward_coop<JQ_NT, JQ_BW>(PropArgs);
 template __global__ void k_backward_coop<JQ_NT, JQ_BW>(PropArgs);
 #else
 #include "jq_kernels.h"
-#ifndef JQ_MINW_MAXNT
-#define JQ_MINW_MAXNT 2      // tile counts up to which two workgroups share a CU (slab kernels)
-#endif
 #define JQ_MINW ((JQ_NT <= JQ_MINW_MAXNT) ? 2 : 1)
 #if JQ_BW == 7 && JQ_VARIANT == 11  // quad layout, one slab per workgroup, full leakage weights (jq_update_wmat)
 template __global__ void k_forward<JQ_NT, JQ_BW, 1, false, true>(PropArgs);

@@ -26,6 +26,9 @@
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 #define JQ_WAVES 4            // waves (slabs) per workgroup
+#ifndef JQ_MINW_MAXNT
+#define JQ_MINW_MAXNT 2       // tile counts up to which two workgroups share a CU (slab kernels: MINW of their instantiations and of the host's look-up)
+#endif
 #define JQ_MAXNC 4            // max coupled controls supported by the trace/carry bookkeeping
 #define JQ_NTR 5              // trace scalars per control per backward step
 #define JQ_STATE_ARRAYS 4     // U, V, MU, NU
@@ -145,7 +148,7 @@ __device__ __forceinline__ double row_sum(const s1& p) { return p[0]; }
 #if defined(JQ_BW) && JQ_BW == 7
 typedef s1 jq_row;
 #define JQ_RL 1               // doubles per row element of an array
-#elif defined(JQ_BW) && JQ_BW == 8 && !defined(JQ_ROW_D4)
+#elif defined(JQ_BW) && JQ_BW == 8
 typedef s4 jq_row;
 #define JQ_RL 4
 #else
@@ -187,13 +190,7 @@ __device__ __forceinline__ double a_dot(const Arr<NT>& x, const Arr<NT>& y)
 {
     double s = 0.0;
 #pragma unroll
-    for (int i = 0; i < NT; ++i) {
-#if JQ_RL == 1 && defined(JQ_EXP_DOTFMA)
-        s = fma(x.t[i][0], y.t[i][0], s);
-#else
-        s += row_sum(x.t[i] * y.t[i]);
-#endif
-    }
+    for (int i = 0; i < NT; ++i) s += row_sum(x.t[i] * y.t[i]);      // (quad layout: hipcc contracts this into an FMA chain)
     return s;
 }
 // y += c * tab .* x   (tab: per-row table in LDS, padded to 16*NT rows, stored [block][g][r] so that the four
@@ -531,25 +528,6 @@ __device__ __forceinline__ double row_shift4(double x)
         int i[2];
     } a, b;
     a.d = x;
-#ifdef JQ_EXP_NOSHIFT      // timing experiment only (wrong results): what the lane shifts cost
-    return x;
-#endif
-#ifdef JQ_EXP_BPERM        // one shift direction through the LDS crossbar (ds_bpermute_b32) instead of the VALU
-    if (CTRL == 0x114) {
-        const int addr = (((int)(threadIdx.x & 63) - 4) & 63) * 4;
-        b.i[0] = __builtin_amdgcn_ds_bpermute(addr, a.i[0]);
-        b.i[1] = __builtin_amdgcn_ds_bpermute(addr, a.i[1]);
-        return b.d;
-    }
-#endif
-#ifdef JQ_EXP_BPERM2       // both directions
-    {
-        const int addr = (((int)(threadIdx.x & 63) + (CTRL == 0x114 ? -4 : 4)) & 63) * 4;
-        b.i[0] = __builtin_amdgcn_ds_bpermute(addr, a.i[0]);
-        b.i[1] = __builtin_amdgcn_ds_bpermute(addr, a.i[1]);
-        return b.d;
-    }
-#endif
     b.i[0] = __builtin_amdgcn_update_dpp(0, a.i[0], CTRL, 0xf, 0xf, true);
     b.i[1] = __builtin_amdgcn_update_dpp(0, a.i[1], CTRL, 0xf, 0xf, true);
     return b.d;
@@ -585,18 +563,6 @@ __device__ __forceinline__ void t4q_block(Arr<NT>& D, const Arr<NT>& C, const Ar
     constexpr bool diag = MODE & JQ_T4_DIAG, rt = MODE & JQ_T4_RTERMS, mtm = MODE & JQ_T4_MTERMS;
     const double xc = x.t[mt][0];
     double acc = ZEROC ? 0.0 : C.t[mt][0];
-#ifdef JQ_EXP_MFMA_LAST      // experiment: coupling FMAs first, the MFMA last (its result is not read by the VALU for a whole product)
-    const double xnext = x.t[mt + 1 < NT ? mt + 1 : mt][0];
-    if constexpr (rt) {
-        acc = fma(c[0], row_shift4<0x114>(xc), acc);
-        acc = fma(c[1], row_shift4<0x104>(xc), acc);
-    }
-    if constexpr (mtm) {
-        if (mt > 0) acc = fma(c[2], xold, acc);
-        if (mt + 1 < NT) acc = fma(c[3], xnext, acc);
-    }
-    if constexpr (diag) acc = __builtin_amdgcn_mfma_f64_4x4x4f64(a, xc, acc, 0, 0, 0);
-#else
     if constexpr (diag) acc = __builtin_amdgcn_mfma_f64_4x4x4f64(a, xc, acc, 0, 0, 0);
     if constexpr (rt) {
         acc = fma(c[0], row_shift4<0x114>(xc), acc);
@@ -606,7 +572,6 @@ __device__ __forceinline__ void t4q_block(Arr<NT>& D, const Arr<NT>& C, const Ar
         if (mt > 0) acc = fma(c[2], xold, acc);
         if (mt + 1 < NT) acc = fma(c[3], x.t[mt + 1 < NT ? mt + 1 : mt][0], acc);
     }
-#endif
     xold = xc;
     D.t[mt][0] = acc;
 }
@@ -628,18 +593,7 @@ __device__ __forceinline__ void mm_t4q(Arr<NT>& D, const Arr<NT>& C, const doubl
     if constexpr (diag && SH) a_cur = fma(shd, wsr[0], a_cur);
     if constexpr (coef) c_cur = t4q_cload(cf, 0);
     double xold = 0.0;
-#ifdef JQ_EXP_NOPF      // experiment: the operands of THIS block only (no one-block-ahead prefetch: 10 registers less in flight)
-#pragma unroll
-    for (int mt = 0; mt < NT; ++mt) {
-        double a = 0.0;
-        d4 c = {0.0, 0.0, 0.0, 0.0};
-        if constexpr (diag) a = ma[mt * 64];
-        if constexpr (coef) c = t4q_cload(cf, mt);
-        t4q_block<NT, ZEROC, MODE>(D, C, x, mt, a, c, xold);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    return;
-#endif
+    // (operands one block ahead: 10 registers more in flight; fetching per block doubled the waits per step and spilled 144 B)
 #pragma unroll
     for (int mt = 0; mt < NT; ++mt) {
         const double a = a_cur;
@@ -705,10 +659,8 @@ __device__ __forceinline__ void mm_t4q_multi(Arr<NT>& D0, const Arr<NT>& C0, con
         const double su = row_shift4<0x114>(xc), sd = row_shift4<0x104>(xc);
         hook(mt, su, sd);
         double acc[3] = {Z0 ? 0.0 : C0.t[mt][0], (NP > 1 && !Z1) ? C1.t[mt][0] : 0.0, (NP > 2 && !Z2) ? C2.t[mt][0] : 0.0};
-#ifndef JQ_EXP_MFMA_LAST
 #pragma unroll
         for (int k = 0; k < NP; ++k) acc[k] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[k], xc, acc[k], 0, 0, 0);
-#endif
 #pragma unroll
         for (int k = 0; k < NP; ++k) acc[k] = fma(c[k][0], su, acc[k]);
 #pragma unroll
@@ -721,10 +673,6 @@ __device__ __forceinline__ void mm_t4q_multi(Arr<NT>& D0, const Arr<NT>& C0, con
 #pragma unroll
             for (int k = 0; k < NP; ++k) acc[k] = fma(c[k][3], xn, acc[k]);
         }
-#ifdef JQ_EXP_MFMA_LAST
-#pragma unroll
-        for (int k = 0; k < NP; ++k) acc[k] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[k], xc, acc[k], 0, 0, 0);
-#endif
         xold = xc;
         D0.t[mt][0] = acc[0];
         if constexpr (NP > 1) D1.t[mt][0] = acc[1];
@@ -747,43 +695,6 @@ __device__ __forceinline__ void mm_t4q3(Arr<NT>& D0, const Arr<NT>& C0, const do
 {
     mm_t4q_multi<NT, 3, Z0, Z1, Z2, SH, T4qNoHook, SCM>(D0, C0, m0, D1, C1, m1, D2, C2, m2, x, sh0, sh1, sh2, wsr);
 }
-// Two products with the SAME operator (a K image with the folded shift, see mm_t4q SH) and two right-hand sides in one pass over the
-// blocks: D_k = C_k + M' x_k.  The A operand and the coefficients of a block are fetched -- and the shift folded -- once; each
-// accumulator chain keeps the order of t4q_block (MFMA, c0, c1, c2, c3).  x_k must not alias a D_j.
-template <int NT, bool Z0, bool Z1>
-__device__ __forceinline__ void mm_t4q_2rhs(Arr<NT>& D0, const Arr<NT>& C0, const Arr<NT>& x0, Arr<NT>& D1, const Arr<NT>& C1,
-                                            const Arr<NT>& x1, const double* mat, double shd, const double* wsr)
-{
-    const int lane = threadIdx.x & 63;
-    const double* ma = t4q_a(mat, lane);
-    const d4* cf = t4q_c<NT>(mat, lane);
-    double xold0 = 0.0, xold1 = 0.0;
-#pragma unroll
-    for (int mt = 0; mt < NT; ++mt) {
-        const double a = fma(shd, wsr[16 * mt], ma[mt * 64]);
-        const d4 c = t4q_cload(cf, mt);
-        const double xc0 = x0.t[mt][0], xc1 = x1.t[mt][0];
-        double acc0 = Z0 ? 0.0 : C0.t[mt][0], acc1 = Z1 ? 0.0 : C1.t[mt][0];
-        acc0 = __builtin_amdgcn_mfma_f64_4x4x4f64(a, xc0, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f64_4x4x4f64(a, xc1, acc1, 0, 0, 0);
-        acc0 = fma(c[0], row_shift4<0x114>(xc0), acc0);
-        acc1 = fma(c[0], row_shift4<0x114>(xc1), acc1);
-        acc0 = fma(c[1], row_shift4<0x104>(xc0), acc0);
-        acc1 = fma(c[1], row_shift4<0x104>(xc1), acc1);
-        if (mt > 0) {
-            acc0 = fma(c[2], xold0, acc0);
-            acc1 = fma(c[2], xold1, acc1);
-        }
-        if (mt + 1 < NT) {
-            acc0 = fma(c[3], x0.t[mt + 1 < NT ? mt + 1 : mt][0], acc0);
-            acc1 = fma(c[3], x1.t[mt + 1 < NT ? mt + 1 : mt][0], acc1);
-        }
-        xold0 = xc0, xold1 = xc1;
-        D0.t[mt][0] = acc0;
-        D1.t[mt][0] = acc1;
-        __builtin_amdgcn_sched_barrier(0);      // (fence per block, see mm_t4q_multi)
-    }
-}
 // the same with the operator in registers (the m + 1 products of a Horner chain share it: no LDS latency at their heads)
 template <int NT>
 __device__ __forceinline__ void t4q_load(OpQ<NT>& op, const double* mat)
@@ -794,16 +705,7 @@ __device__ __forceinline__ void t4q_load(OpQ<NT>& op, const double* mat)
 #pragma unroll
     for (int mt = 0; mt < NT; ++mt) {
         op.a[mt] = ma[mt * 64];
-#ifdef JQ_EXP_OPQ_EDGE
-        // (round 5 experiment: the first block has no neighbour below and the last one none above -- their coefficients c[2] / c[3]
-        //  are never used, but a 32-byte read keeps the register pair of the whole record alive: read the halves that are used)
-        const double* cd = (const double*)(cf + mt * 16);
-        op.c[mt][0] = cd[0], op.c[mt][1] = cd[1];
-        op.c[mt][2] = mt > 0 ? cd[2] : 0.0;
-        op.c[mt][3] = mt + 1 < NT ? cd[3] : 0.0;
-#else
         op.c[mt] = t4q_cload(cf, mt);
-#endif
     }
 }
 template <int NT>
@@ -1720,10 +1622,10 @@ __device__ __forceinline__ void jacobi_add(Arr<NT>& out, const Arr<NT>& bpa, con
     for (int i = 0; i < NT; ++i) out.t[i] = (bpa.t[i] - A.t[i]) + (in_a ? Ya.t[i] : Yb.t[i]);
 }
 
-// REGOP (quad layout): the operator of the chain's m + 1 products is held in 10 NT registers (OpQ); false: every product reads it from
-// LDS again (mm_t4q) -- 60 registers less inside the recurrence at NT = 6
+// Quad layout: the operator of the chain's m + 1 products is held in 10 NT registers (OpQ).  (Re-reading it from LDS per product, 60
+// registers less inside the recurrence at NT = 6, was rejected for the twelve-wave backward kernel: profiles/r05_exp_variants.txt.)
 // SC (quad layout, Neumann): S is uniform -- the operand is an OpS (3 + 2 NT doubles)
-template <int NT, int BW, bool JAC, bool REGOP = true, bool SC = false>
+template <int NT, int BW, bool JAC, bool SC = false>
 __device__ __forceinline__ void horner_add(Arr<NT>& out, const Arr<NT>& bpa, const Arr<NT>& A, const double* S, int m,
                                            Arr<NT>& Ya, Arr<NT>& Yb, double jacobi_tol2, int ncol, int jac_wg = -1)
 {
@@ -1757,11 +1659,7 @@ __device__ __forceinline__ void horner_add(Arr<NT>& out, const Arr<NT>& bpa, con
         mm_c<NT, BW>(out, bpa, S, A);
         return;
     }
-#ifdef JQ_EXP_NOOPQ
-    if constexpr (false) {
-#else
-    if constexpr (BW == JQ_BW_T4Q && REGOP) {
-#endif
+    if constexpr (BW == JQ_BW_T4Q) {
         OpQ<NT> op;
         t4q_load(op, S);
         mm_t4q_regs(Ya, A, op, A);
@@ -1778,7 +1676,7 @@ __device__ __forceinline__ void horner_add(Arr<NT>& out, const Arr<NT>& bpa, con
     }
     mm_c<NT, BW>(Ya, A, S, A);  // Y1 = A + S A
     --rem;
-    if constexpr (BW == JQ_BW_OD || BW == JQ_BW_T4 || BW == JQ_BW_T4Q) {
+    if constexpr (BW == JQ_BW_OD || BW == JQ_BW_T4) {
         // mm_od / mm_t4 are alias-safe: the recurrence runs in place and Yb is never touched (48 registers less)
         for (; rem > 0; --rem) mm_c<NT, BW>(Ya, A, S, Ya);
         mm_c<NT, BW>(out, bpa, S, Ya);
@@ -1801,10 +1699,7 @@ __device__ __forceinline__ void horner_add(Arr<NT>& out, const Arr<NT>& bpa, con
 // Ya and A's OWN registers (A is destroyed), every term is added to out.  Three arrays where the Horner form needs four (out, A, Ya, Yb) --
 // m array additions more per call.  For the widest slab kernels (six tile rows, band / dense tiles): their backward sweep keeps eight
 // arrays alive through a recurrence and spills two of them (k_backward<6, 5>: 388 B of scratch per lane in round 5).
-#ifndef JQ_BWD_TERMS
-#define JQ_BWD_TERMS 1
-#endif
-constexpr bool jq_bwd_terms(int NT, int BW, bool JAC) { return JQ_BWD_TERMS && !JAC && NT >= 6 && BW != JQ_BW_OD && BW != JQ_BW_T4 && BW != JQ_BW_T4Q; }
+constexpr bool jq_bwd_terms(int NT, int BW, bool JAC) { return !JAC && NT >= 6 && BW != JQ_BW_OD && BW != JQ_BW_T4 && BW != JQ_BW_T4Q; }
 template <int NT, int BW>
 __device__ __forceinline__ void neumann_terms_add(Arr<NT>& out, Arr<NT>& A, const double* S, int m, Arr<NT>& Ya)
 {
@@ -1852,59 +1747,39 @@ __device__ __forceinline__ void a_unpark(Arr<NT>& a, const double* park)
         for (int r = 0; r < JQ_RL; ++r) a.t[i][r] = park[(JQ_RL * i + r) * 64];
 }
 
-// Which sweeps use the fused passes of sv_state (measured with scripts/exp_variants.sh at cnot3 x 3 072 samples, DESIGN.md
-// section 6, round 3): forward 337 -> 318 ms -- most of it (-17 ms) from having four stages instead of six (fewer branch fences),
-// the shared lane shifts add -2.5 ms; the twelve-wave backward kernel loses with ANY of it in its state step (104 -> 144 .. 540 B
-// of scratch: 838 -> 915 .. 1 400 ms) and gains 6 ms from K0 X / K1 X in one pass (no extra registers).
-#ifndef JQ_FWD_FUSE
-#define JQ_FWD_FUSE 3
-#endif
-#ifndef JQ_BWD_FUSE
-#define JQ_BWD_FUSE 3
-#endif
-#ifndef JQ_BWD_FUSE3      // ... of the twelve-wave backward kernel (168 registers per wave)
-#define JQ_BWD_FUSE3 0
-#endif
-#ifndef JQ_BWD_ADJ_FUSE   // adjoint step: K0 X and K1 X in one pass
-#define JQ_BWD_ADJ_FUSE 1
-#endif
-// Per-step trims of the three-slab quad-layout kernels: work outside the products that computed a value twice or reduced with half-empty
-// registers.  Same floating-point operations on the same values in the same order -- results bit-identical (tests/test_gpu_step_trim.py).
-//   bit 0: forward, the leak integrand tr(vr' W vr) of the new state is carried to the next step instead of being formed again
-//   bit 1: forward, ceps * ws[row] of this lane's rows is formed once in front of the time loop (four times six multiplies and LDS reads per step)
-//   bit 2: backward (ORD), the early trace sums of the controls 0 and 1 share one wave_sum4 (five calls a step instead of six at
-//          Ncoupled = 3, three instead of four at 2)
-//   bit 3: backward (UNI), use 6: the two products with K05 (vN += K05 un, L = K05 nb) in one pass -- operand fetched and shift-folded once
-// Measured one at a time against -DJQ_STEP_TRIM=0 (cnot3 x 3 072 samples, profiles/step_trim_ab.txt): bit 0 + 0.4 %, bit 1 + 0.6 %,
-// bit 2 + 1.1 %, bit 3 - 0.3 % (the pass without mm_t4q's one-block-ahead operand prefetch loses what the six FMAs save): off by default.
-#ifndef JQ_STEP_TRIM
-#define JQ_STEP_TRIM 7
-#endif
-#ifndef JQ_BWD3_NOOPQ     // twelve-wave backward kernel: Neumann recurrences of the ADJOINT step with the operator re-read from LDS per product
-#define JQ_BWD3_NOOPQ 0
-#endif
-#ifndef JQ_BWD3_NOOPQ_STATE   // ... and of the state re-integration inside it
-#define JQ_BWD3_NOOPQ_STATE 0
-#endif
+// Which sweeps use the fused passes of sv_state (cnot3 x 3 072 samples): every quad-layout sweep but the
+// state step of the twelve-wave backward kernel without folded shifts.  Forward 337 -> 318 ms -- most of it (-17 ms) from having four
+// stages instead of six (fewer branch fences), the shared lane shifts add -2.5 ms; the twelve-wave backward kernel loses with ANY of
+// it in its state step (104 -> 144 .. 540 B of scratch: 838 -> 915 .. 1 400 ms) and gains 6 ms from K0 X / K1 X in one pass (no
+// extra registers).
+// The three-slab quad-layout kernels keep work that is the same in every step outside the products (same floating-point operations
+// on the same values in the same order as forming it per step: tests/test_gpu_step_trim.py holds them to the earlier results bit for
+// bit; one at a time + 0.4 %, + 0.6 %, + 1.1 %, profiles/step_trim_ab.txt):
+//   forward: the leak integrand tr(vr' W vr) of the new state is carried to the next step instead of being formed again (LKC), and
+//            ceps * ws[row] of this lane's rows is formed once in front of the time loop (CWH: 4 x 6 multiplies and LDS reads per step)
+//   backward (ORD): the early trace sums of the controls 0 and 1 share one wave_sum4 (PK: five calls a step instead of six at
+//            Ncoupled = 3, three instead of four at 2)
+// Tried and dropped: the two products of use 6 with K05 in one pass over the blocks (UNI backward), - 0.2 % -- see
+// profiles/step_trim_ab.txt; the source is in the history at 23ed703.
 // State (re-)integration, operator uses 0..5 of one Stormer-Verlet step (forward step!,
 // src/StormerVerlet.jl:461-504, also used with h<0 by the backward sweep, src/evalobjgrad.jl:879).
 //   in : u (preserved), v (CONSUMED: overwritten in place by v05 = v(t+h/2))
 //   out: unew = u(t+h), vN = v05 + S05 v05 (the caller finishes v(t+h) = vN + Kp05 unew with use 6)
 //   A, Ya, Yb: scratch arrays.          Operator order per step: Kp05 S05 Kn0 S0 Kn1 S1 (Kp05).
 // At most 8 arrays are live here (u, v/v05, unew, vN, A, Ya, Yb + one of the caller's).
-// FUSE (quad layout only): bit 0 = K05 u with S0 u in one pass, bit 1 = S05 v05 with K0 v05 and K1 v05 in one pass
+// FUSE (quad layout only): K05 u with S0 u in one pass, and S05 v05 with K0 v05 and K1 v05 in one pass
 // FOLD (quad layout, one sample per wave): `ceps` is the per-lane MASKED shift (+c eps on the lanes that hold the diagonal of the MFMA's
 // A operand, 0 elsewhere; 0 everywhere without a shift) and every product with a K image folds it into its operand (mm_t4q SH)
 // SC (quad layout, fused passes): the S images are uniform (s_image_uniform) -- their products take the compact operand (OpS, mm_t4s)
-// CW (quad layout, fused passes without FOLD): cw[i] = ceps * ws[16 i + g], formed by the caller once per launch (JQ_STEP_TRIM bit 1)
-template <int NT, int BW, bool JAC, int FUSE = 0, bool FOLD = false, bool REGOP = true, bool TERMS = false, typename RING = RingT<BW == JQ_BW_T4Q>, bool SC = false, bool CW = false>
+// CW (quad layout, fused passes without FOLD): cw[i] = ceps * ws[16 i + g], formed by the caller once per launch
+template <int NT, int BW, bool JAC, bool FUSE = false, bool FOLD = false, bool TERMS = false, typename RING = RingT<BW == JQ_BW_T4Q>, bool SC = false, bool CW = false>
 __device__ __forceinline__ void sv_state(RING& p, const PropArgs& a, bool active, double ceps, const double* ws, int g,
                                          const Arr<NT>& u, Arr<NT>& v, Arr<NT>& unew, Arr<NT>& vN, Arr<NT>& A, Arr<NT>& Ya,
                                          Arr<NT>& Yb, const double* cw = nullptr)
 {
-    static_assert(!CW || (BW == JQ_BW_T4Q && !JAC && FUSE != 0 && !FOLD), "CW: the fused quad-layout step with the shift applied to the results");
-    static_assert(!SC || (BW == JQ_BW_T4Q && !JAC && FUSE == 3 && REGOP), "SC: the fused quad-layout step");
-    if constexpr (BW == JQ_BW_T4Q && !JAC && FUSE != 0) {
+    static_assert(!CW || (BW == JQ_BW_T4Q && !JAC && FUSE && !FOLD), "CW: the fused quad-layout step with the shift applied to the results");
+    static_assert(!SC || (BW == JQ_BW_T4Q && !JAC && FUSE), "SC: the fused quad-layout step");
+    if constexpr (BW == JQ_BW_T4Q && !JAC && FUSE) {
         // Quad layout (always window staging: every image of the step is resident, the order of the uses is free): the products
         // that share a right-hand side are made in ONE pass over the blocks so that they share its lane shifts -- K05 u with
         // S0 u, and S05 v05 with K0 v05 and K1 v05: 5 + 2m passes instead of 8 + 2m (the products are the same 8 + 2m).
@@ -1914,19 +1789,13 @@ __device__ __forceinline__ void sv_state(RING& p, const PropArgs& a, bool active
         const double* M1 = p.template next_ks<1, 0>();      // S0
         if (active) {
             if constexpr (FOLD) {
-                static_assert(!FOLD || (FUSE & 3) == 3 || FUSE == 0, "FOLD: fused or generic path");
                 mm_t4q2<NT, true, false, 1, SC ? 2 : 0>(A, A, M0, unew, u, M1, u, ceps, 0.0, ws + g);
             } else {
-            if constexpr (FUSE & 1) {
                 mm_t4q2<NT, true, false, 0, SC ? 2 : 0>(A, A, M0, unew, u, M1, u);        // A = c K05 u ;  unew = u + c S0 u
-            } else {
-                mm_z<NT, BW>(A, M0, u);
-                mm_c<NT, BW>(unew, u, M1, u);
-            }
-            if (a.use_shift) {
-                if constexpr (CW) a_axpy_cw<NT, false>(A, cw, u);
-                else a_axpy_rows(A, ceps, ws, g, u);
-            }
+                if (a.use_shift) {
+                    if constexpr (CW) a_axpy_cw<NT, false>(A, cw, u);
+                    else a_axpy_rows(A, ceps, ws, g, u);
+                }
             }
         }
         M0 = p.template next_ks<1, 1>();                    // S05
@@ -1934,7 +1803,7 @@ __device__ __forceinline__ void sv_state(RING& p, const PropArgs& a, bool active
             if constexpr (SC) mm_t4s<NT, false>(A, A, M0, v);
             else mm_c<NT, BW>(A, A, M0, v);                            // A = c (K05 u + S05 v)
             a_add(v, A);
-            horner_add<NT, BW, JAC, REGOP, SC>(v, v, A, M0, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);       // v = v05
+            horner_add<NT, BW, JAC, SC>(v, v, A, M0, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);       // v = v05
         }
         M1 = p.template next_ks<0, 0>();                    // Kn0
         const double* M2 = p.template next_ks<0, 2>();      // Kn1
@@ -1942,22 +1811,16 @@ __device__ __forceinline__ void sv_state(RING& p, const PropArgs& a, bool active
             if constexpr (FOLD) {
                 mm_t4q3<NT, false, false, true, 6, SC ? 1 : 0>(vN, v, M0, unew, unew, M1, A, A, M2, v, 0.0, -ceps, -ceps, ws + g);
             } else {
-            if constexpr (FUSE & 2) {
                 mm_t4q3<NT, false, false, true, 0, SC ? 1 : 0>(vN, v, M0, unew, unew, M1, A, A, M2, v);     // vN = v05 + S05 v05 ; unew -= c K0 v05 ; A = -c K1 v05
-            } else {
-                mm_c<NT, BW>(vN, v, M0, v);
-                mm_c<NT, BW>(unew, unew, M1, v);
-                mm_z<NT, BW>(A, M2, v);
-            }
-            if (a.use_shift) {
-                if constexpr (CW) {
-                    a_axpy_cw<NT, true>(unew, cw, v);
-                    a_axpy_cw<NT, true>(A, cw, v);
-                } else {
-                    a_axpy_rows(unew, -ceps, ws, g, v);
-                    a_axpy_rows(A, -ceps, ws, g, v);
+                if (a.use_shift) {
+                    if constexpr (CW) {
+                        a_axpy_cw<NT, true>(unew, cw, v);
+                        a_axpy_cw<NT, true>(A, cw, v);
+                    } else {
+                        a_axpy_rows(unew, -ceps, ws, g, v);
+                        a_axpy_rows(A, -ceps, ws, g, v);
+                    }
                 }
-            }
             }
         }
         M0 = p.template next_ks<1, 2>();                    // S1
@@ -1965,7 +1828,7 @@ __device__ __forceinline__ void sv_state(RING& p, const PropArgs& a, bool active
             if constexpr (SC) mm_t4s<NT, false>(A, A, M0, unew);
             else mm_c<NT, BW>(A, A, M0, unew);                         // A = c (S1 (u + c kappa1) - K1 v05)
             a_add(unew, A);
-            horner_add<NT, BW, JAC, REGOP, SC>(unew, unew, A, M0, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);
+            horner_add<NT, BW, JAC, SC>(unew, unew, A, M0, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);
         }
         return;
     }
@@ -1986,7 +1849,7 @@ __device__ __forceinline__ void sv_state(RING& p, const PropArgs& a, bool active
         mm_c<NT, BW>(A, A, M, v);
         a_add(v, A);
         if constexpr (TERMS) neumann_terms_add<NT, BW>(v, A, M, a.m, Ya);
-        else horner_add<NT, BW, JAC, REGOP>(v, v, A, M, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);
+        else horner_add<NT, BW, JAC>(v, v, A, M, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);
         mm_c<NT, BW>(vN, v, M, v);
     }
     // use 2: Kn0 -- unew = u - c K0 v05
@@ -2018,7 +1881,7 @@ __device__ __forceinline__ void sv_state(RING& p, const PropArgs& a, bool active
         mm_c<NT, BW>(A, A, M, unew);
         a_add(unew, A);
         if constexpr (TERMS) neumann_terms_add<NT, BW>(unew, A, M, a.m, Ya);
-        else horner_add<NT, BW, JAC, REGOP>(unew, unew, A, M, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);
+        else horner_add<NT, BW, JAC>(unew, unew, A, M, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);
     }
 }
 
@@ -2081,17 +1944,17 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
 
     // one time step: (u, v) -> (unew, vN); v is consumed (becomes v05).  The two array pairs swap
     // roles every step, so the loop body is written for two steps and nothing is ever copied.
-    // (three slabs per workgroup, JQ_STEP_TRIM -- LKC: lw = tr(vr' W vr) of the state a step starts from, carried from the step before;
+    // (three slabs per workgroup -- LKC: lw = tr(vr' W vr) of the state a step starts from, carried from the step before;
     //  CWH: cw = ceps * ws of this lane's rows)
-    constexpr bool TRIM3 = QUAD && MINW == 3 && !JAC && !UNI && JQ_FWD_FUSE != 0;
-    constexpr bool LKC = TRIM3 && (JQ_STEP_TRIM & 1), CWH = TRIM3 && (JQ_STEP_TRIM & 2);
+    constexpr bool TRIM3 = QUAD && MINW == 3 && !JAC && !UNI;
+    constexpr bool LKC = TRIM3, CWH = TRIM3;
     double lw = 0.0;
     double cw[CWH ? NT : 1] = {};
 #define JQ_FWD_STEP(U, V, UN, VN, NSTEP)                                                                         \
     {                                                                                                            \
         p.begin_step(NSTEP);                                                                                     \
         if (active) leak += LKC ? lw : a_wsq(wd, g, U); /* trapezoidal part: tr(vr' W vr) at t_n (:700) */       \
-        sv_state<NT, BW, JAC, JQ_FWD_FUSE, UNI, true, false, RingT<QUAD>, SC, CWH>(p, a, active, ceps, ws, g, U, V, UN, VN, A, Ya, Yb, cw); \
+        sv_state<NT, BW, JAC, true, UNI, false, RingT<QUAD>, SC, CWH>(p, a, active, ceps, ws, g, U, V, UN, VN, A, Ya, Yb, cw); \
         /* use 6: Kp05 again -- v(t+h) = v05 + c (K05 u_new + S05 v05) */                                        \
         const double* M6 = p.template next_ks<0, 1>();                                                                             \
         if (active) {                                                                                            \
@@ -2190,7 +2053,7 @@ template <int NT, int BW, int MINW, bool JAC, bool WLRT = false, bool UNI = fals
 __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_T4Q) ? 1 : MINW) void k_backward(PropArgs a)
 {
     static_assert(!ORD || (UNI && BW == JQ_BW_T4Q && !JAC), "ORD: a variant of the UNI quad-layout kernel");
-    static_assert(!SC || (ORD && MINW == 3 && !WLRT && !JQ_BWD3_NOOPQ && !JQ_BWD3_NOOPQ_STATE), "SC: a variant of the ORD three-slab kernel");
+    static_assert(!SC || (ORD && MINW == 3 && !WLRT), "SC: a variant of the ORD three-slab kernel");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int KT = 4 * NT;
     const int lane_ = threadIdx.x & 63;
@@ -2238,15 +2101,22 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
     // [workgroups][steps][ntr] instead of [waves][steps][ntr] (12 x less traffic with three slabs per workgroup).
     const int ntr = Nc * JQ_NTR;
     double* rec = carry + Nc * NTHREADS + (a.park_lds ? (size_t)NWAVES * (JQ_RL * NT) * 64 : 0);
-    // PK (ORD with three slabs per workgroup, JQ_STEP_TRIM bit 2): the early values t1, t3 of the controls 0 and 1 share ONE wave_sum4
+    // PK (ORD with three slabs per workgroup): the early values t1, t3 of the controls 0 and 1 share ONE wave_sum4
     // (slots 0, 2 and 1, 3; control 2: slots 4, 6 of a call of its own), the late groups follow, one per control as above: five calls a step
     // instead of six at Ncoupled = 3, three instead of four at 2.  wave_sum4 adds every slot the same way, (x0 + x2) + (x1 + x3) and the
     // same rotate-adds: the sums do not depend on the slot.  Same allocation (rslots), same HBM record.
     // (Letting the early pair of control 2 wait for the first late call -- four calls -- keeps two partial dots alive through the adjoint
     //  step: 12 B of scratch in the 168-register SC kernel, not kept.)
-    constexpr bool PK = ORD && MINW == 3 && (JQ_STEP_TRIM & 4);
+    constexpr bool PK = ORD && MINW == 3;
     const int rslots = 8 * Nc;
     for (int i = threadIdx.x; i < 2 * NWAVES * rslots; i += blockDim.x) rec[i] = 0.0;   // (inactive waves never write theirs)
+    // PK: lane 16 row of this wave stores its sum of a wave_sum4 group into the wave's record of step n, slots base .. base + 3
+    auto put_group = [&](int n, int base, double ts) {
+        // (row: formed here -- as a loop-invariant address it costs the 168-register kernel a spilled register)
+        int row = lane_ >> 4;
+        asm volatile("" : "+v"(row));
+        if ((lane_ & 15) == 0) rec[((size_t)(n & 1) * NWAVES + wave) * rslots + base + row] = ts;
+    };
     auto flush_traces = [&](int k) {
         if (!QUAD && a.batch > 0) {   // batched staging has no workgroup barrier in every step
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -2304,9 +2174,6 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
     WLow<NT, QUAD> wl;
     if constexpr (WLR) wl.init(a, lane_, smem);
     const bool wforce = WLR && a.wrank > 0 && a.forced;
-    // (twelve-wave kernel, 168 registers per wave: JQ_BWD3_NOOPQ=1 lets the Neumann recurrences read their operator from LDS per product
-    //  instead of holding it in 60 registers -- no spill stores left in the time loop, round 5 experiment)
-    constexpr bool BREG = !(QUAD && MINW >= 3 && JQ_BWD3_NOOPQ);
 
     if (a.first_chunk) {
         // carry_q = tr(vr' Hsym_q lambdai) at t = T: the "vr0/lambdai0" term of the first backward
@@ -2334,7 +2201,7 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
         // mu's registers serve as the scratch array A of the state step
         // (UNI: the fused stages -- shared lane shifts of u and of v05 -- also in the twelve-wave kernel: round 3 measured them slower there,
         //  104 -> 144 ... 172 B of scratch; with the registers the UNI variant frees they pay: backward sweep 772 -> 757 ms, round 4)
-        sv_state<NT, BW, JAC, (MINW >= 3 ? (UNI ? 3 : JQ_BWD_FUSE3) : JQ_BWD_FUSE), UNI, !(QUAD && MINW >= 3 && JQ_BWD3_NOOPQ_STATE), jq_bwd_terms(NT, BW, JAC), RingT<QUAD>, SC>(p, a, active, ceps, ws, g, u, v, un, vN, mu, Ya, Yb);
+        sv_state<NT, BW, JAC, (MINW >= 3 ? UNI : true), UNI, jq_bwd_terms(NT, BW, JAC), RingT<QUAD>, SC>(p, a, active, ceps, ws, g, u, v, un, vN, mu, Ya, Yb);
         // (every wave has passed a workgroup barrier since it finished step n-1: begin_step in window mode, the operator
         // switches of sv_state otherwise)
         if (n > 0) flush_traces(n - 1);
@@ -2343,12 +2210,8 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
         if (active) {
             if constexpr (UNI) {
                 constexpr int FULLQ = JQ_T4_DIAG | JQ_T4_RTERMS | JQ_T4_MTERMS;
-                if constexpr (MINW == 3 && (JQ_STEP_TRIM & 8)) {
-                    mm_t4q_2rhs<NT, false, true>(vN, vN, un, L, L, nb, M, ceps, ws + g);
-                } else {
-                    mm_t4q<NT, false, FULLQ, true>(vN, vN, M, un, ceps, ws + g);
-                    mm_t4q<NT, true, FULLQ, true>(L, L, M, nb, ceps, ws + g);
-                }
+                mm_t4q<NT, false, FULLQ, true>(vN, vN, M, un, ceps, ws + g);
+                mm_t4q<NT, true, FULLQ, true>(L, L, M, nb, ceps, ws + g);
             } else {
                 mm_c<NT, BW>(vN, vN, M, un);
                 if (a.use_shift) a_axpy_rows(vN, ceps, ws, g, un);
@@ -2376,7 +2239,7 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
                     }
             a_add(mu, L);
             if constexpr (jq_bwd_terms(NT, BW, JAC)) neumann_terms_add<NT, BW>(mu, L, M, a.m, Ya);      // (L is scratch from here on)
-            else horner_add<NT, BW, JAC, BREG, SC>(mu, mu, L, M, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);
+            else horner_add<NT, BW, JAC, SC>(mu, mu, L, M, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);
         }
         // early traces with X (lets vr0 = u die here): tr1 = tr(vr0' Hanti_q X), tr3 = tr(vr' Hanti_q X)
         double o_p4 = 0.0;      // ORD: the new part of tr4 of control 1, formed in the pass of use 11
@@ -2398,11 +2261,7 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
                         pk = hp;
                     } else {
                         // rows 0, 2, 1, 3 = slots 0 .. 3: t1, t3 of control 0, t1, t3 of control 1;  slots 4, 6: of control 2
-                        const double ts = (q == 1 ? wave_sum4_join(pk, hp) : wave_sum4_join(hp, wave_sum4_half(0.0, 0.0))) * wgt;
-                        // (row: formed here -- as a loop-invariant address it costs the 168-register kernel a spilled register)
-                        int row = lane_ >> 4;
-                        asm volatile("" : "+v"(row));
-                        if ((lane_ & 15) == 0) rec[((size_t)(n & 1) * NWAVES + wave) * rslots + 4 * (q - 1) + row] = ts;
+                        put_group(n, 4 * (q - 1), (q == 1 ? wave_sum4_join(pk, hp) : wave_sum4_join(hp, wave_sum4_half(0.0, 0.0))) * wgt);
                     }
                     continue;
                 }
@@ -2412,7 +2271,7 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
                 if ((lane_ & 15) == 0) rec[((size_t)(n & 1) * NWAVES + wave) * rslots + 4 * q + (lane_ >> 4)] = ts;
             }
         }
-        if constexpr (QUAD && !JAC && (JQ_BWD_ADJ_FUSE & 1)) {
+        if constexpr (QUAD && !JAC) {
             // uses 8 and 9 in one pass (they share X): L = -c K0 X ; vN(scratch Q) = -c K1 X
             M = p.template next_ks<0, 0>();
             const double* M9 = p.template next_ks<0, 2>();
@@ -2428,18 +2287,18 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
                 }
             }
         } else {
-        // use 8: Kn0 -- L = -c K0 X
-        M = p.template next_ks<0, 0>();
-        if (active) {
-            mm_z<NT, BW>(L, M, mu);
-            if (a.use_shift) a_axpy_rows(L, -ceps, ws, g, mu);
-        }
-        // use 9: Kn1 -- vN(scratch Q) = -c K1 X
-        M = p.template next_ks<0, 2>();
-        if (active) {
-            mm_z<NT, BW>(vN, M, mu);
-            if (a.use_shift) a_axpy_rows(vN, -ceps, ws, g, mu);
-        }
+            // use 8: Kn0 -- L = -c K0 X
+            M = p.template next_ks<0, 0>();
+            if (active) {
+                mm_z<NT, BW>(L, M, mu);
+                if (a.use_shift) a_axpy_rows(L, -ceps, ws, g, mu);
+            }
+            // use 9: Kn1 -- vN(scratch Q) = -c K1 X
+            M = p.template next_ks<0, 2>();
+            if (active) {
+                mm_z<NT, BW>(vN, M, mu);
+                if (a.use_shift) a_axpy_rows(vN, -ceps, ws, g, mu);
+            }
         }
         // use 10: S05 -- L = -c l2 = -c (K0 X + S05 li + hi0) ; Q = -c (S05 (li + c l2) + K1 X + hi1) ;
         //               nb_new = nb + L + sum_j S^j Q          (li_new = li + c (l2 + l1))
@@ -2466,7 +2325,7 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
             a_add(L, nb);
             a_add(L, vN);                     // L = nb + L + Q
             if constexpr (jq_bwd_terms(NT, BW, JAC)) neumann_terms_add<NT, BW>(L, vN, M, a.m, Ya);      // (vN = Q is scratch from here on)
-            else horner_add<NT, BW, JAC, BREG, SC>(L, L, vN, M, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);  // L = nb_new
+            else horner_add<NT, BW, JAC, SC>(L, L, vN, M, a.m, Ya, Yb, a.jacobi_tol2, a.N, a.jac_wg_lds);  // L = nb_new
             a_add(nb, L);                     // nb = nb_old + nb_new = -(li0 + li)
         }
         // use 11: Kp05 -- vN(scratch G) = X + c K05 nb_new (= lambda_r^{1/2} - c K05 li_new)
@@ -2550,10 +2409,7 @@ __global__ __launch_bounds__((BW == JQ_BW_T4Q) ? 256 * MINW : 256, (BW == JQ_BW_
                 t4 = p4 + carry[q * NTHREADS + threadIdx.x];
                 carry[q * NTHREADS + threadIdx.x] = p4;
                 if constexpr (PK) {
-                    const double ts = wave_sum4_rows(t2, t4, t5, 0.0) * wgt;
-                    int row = lane_ >> 4;
-                    asm volatile("" : "+v"(row));
-                    if ((lane_ & 15) == 0) rec[((size_t)(n & 1) * NWAVES + wave) * rslots + 4 * (((Nc + 1) >> 1) + q) + row] = ts;
+                    put_group(n, 4 * (((Nc + 1) >> 1) + q), wave_sum4_rows(t2, t4, t5, 0.0) * wgt);
                     continue;
                 }
                 const double ts = UNI ? wave_sum4(t2, t4, t5, 0.0) * wgt : wave_sum4(t2 * wgt, t4 * wgt, t5 * wgt, 0.0);   // rows 0, 2, 1: t2, t4, t5

@@ -28,9 +28,6 @@ __device__ __forceinline__ double quad_sample_sum(double x, int N, int j)
 // OPREG: the operators of a step live in registers for all its fixed-point iterations (one slab per workgroup, one wave per
 // SIMD: 512 registers); otherwise (two slabs per workgroup, two waves per SIMD: 256 registers) every application re-reads
 // its A operands and coefficient records from the LDS images.
-#ifndef JQ_IMR_CREG      // experiment: coupling-coefficient records of the step's operators in registers (1) or re-read from LDS (0)
-#define JQ_IMR_CREG 1
-#endif
 template <int NT, bool OPREG>
 struct QuadImr {
     const double* K;     // images of the step (LDS, lane offset applied)
@@ -83,7 +80,7 @@ struct QuadImr {
     {
         const int lane = threadIdx.x & 63;
         const double *Kp = K, *Sp = S;
-        if constexpr (!OPREG || !JQ_IMR_CREG) {
+        if constexpr (!OPREG) {
             // the images do not change between the fixed-point iterations: without this the compiler hoists all 60 operand
             // reads out of the iteration loop -- into registers this variant does not have (184 spilled to scratch)
             // (an opaque ZERO offset, not an opaque pointer: the pointers must stay visibly LDS addresses -- ds_read, not flat loads)
@@ -115,7 +112,7 @@ struct QuadImr {
             const double un = pu.t[mt + 1 < NT ? mt + 1 : mt][0], vn = pv.t[mt + 1 < NT ? mt + 1 : mt][0];
             const double uu = row_shift4<0x114>(xu), ud = row_shift4<0x104>(xu);
             const double vu = row_shift4<0x114>(xv), vd = row_shift4<0x104>(xv);
-            const d4 cs = (OPREG && JQ_IMR_CREG) ? oS.c[mt] : t4q_cload(cfS, mt), ck = (OPREG && JQ_IMR_CREG) ? oK.c[mt] : t4q_cload(cfK, mt);
+            const d4 cs = OPREG ? oS.c[mt] : t4q_cload(cfS, mt), ck = OPREG ? oK.c[mt] : t4q_cload(cfK, mt);
             double au = qu.t[mt][0], av = qv.t[mt][0];
             au = fma(cs[0], uu, au);
             av = fma(ck[0], uu, av);

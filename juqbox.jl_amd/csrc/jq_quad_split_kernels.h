@@ -182,7 +182,7 @@ __global__ __launch_bounds__(128 * QW, 1) void k_backward_qsplit(PropArgs a)
     {                                                                                                                   \
         p.begin_step(K);                                                                                                \
         if ((K) >= 2) flush_traces((K) - 2);      /* the adjoint waves finished step K - 2 in super-step K - 1 */        \
-        sv_state<NT, BW, false, JQ_BWD_FUSE, false>(p, a, active, ceps, ws, g, U, V, UN, VN, A, Ya, Yb);                \
+        sv_state<NT, BW, false, true, false>(p, a, active, ceps, ws, g, U, V, UN, VN, A, Ya, Yb);                \
         const double* M6 = p.template next_ks<0, 1>();                                                                  \
         if (active) {                                                                                                   \
             mm_c<NT, BW>(VN, VN, M6, UN);                                                                               \
@@ -284,10 +284,7 @@ __global__ __launch_bounds__(128 * QW, 1) void k_backward_qsplit(PropArgs a)
             // it in use 10; four quads per workgroup (two waves per SIMD: the pipe is full, rides buy nothing) 281.9 / 312.3 / 280.0 --
             // there the ride needs vi05 in the first pass of the step, a moment after it was asked for, and the wave that stalls on the
             // L2 round trip holds up a SIMD that has no idle slots to lose.
-#ifndef JQ_QS_EARLY4
-#define JQ_QS_EARLY4 0
-#endif
-            constexpr bool EARLY = (QW <= 2) || JQ_QS_EARLY4;
+            constexpr bool EARLY = QW <= 2;
             const double* M = p.template next_ks<0, 1>();
             if (active) {
                 if constexpr (EARLY)

@@ -39,9 +39,6 @@
 #define JQ_CODE_HASH "unknown"
 #endif
 #define JQ_VERSION "gfx950 juqbox_hip 0.4.0 src:" JQ_SRC_HASH " code:" JQ_CODE_HASH
-#ifndef JQ_MINW_MAXNT
-#define JQ_MINW_MAXNT 2      // tile counts up to which two workgroups share a CU (slab kernels; jq_kernel_inst.hip)
-#endif
 
 static thread_local std::string g_create_error;
 // JQ_DEBUG_TIMING=1: every propagator launch's HIP-event time on stderr (development aid; changes no result and no kernel choice)

@@ -2,8 +2,8 @@
 # Kernel experiments: build variants of the quad-layout 12-wave kernels (k_6_7.o) with extra -D flags and link one
 # library per variant (juqbox.jl_amd/csrc/../exp/libjq_<tag>.so; selected with JQ_LIB=<path>).
 # usage: scripts/exp_variants.sh tag1:"-DA -DB" tag2:"" ...
-# e.g. the per-step trims of the three-slab kernels, the parent-equivalent build and each item alone (csrc/jq_kernels.h JQ_STEP_TRIM):
-#   scripts/exp_variants.sh trim0:-DJQ_STEP_TRIM=0 trim1:-DJQ_STEP_TRIM=1 trim2:-DJQ_STEP_TRIM=2 trim4:-DJQ_STEP_TRIM=4 trim8:-DJQ_STEP_TRIM=8 trim15:
+# (the kernel headers carry no experiment switches of their own: an experiment adds its #ifdef, is measured here, and its decision
+#  replaces the switch -- scripts/compare_device_code.py shows that taking a switch out changed no kernel)
 # (every variant library reports "<version> src:<hash>+<tag>" from jq_version(): profiles recorded for the production build cannot be
 #  joined with a variant, and vice versa)
 cd "$(dirname "$0")/../juqbox.jl_amd/csrc"

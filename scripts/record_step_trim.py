@@ -3,7 +3,7 @@ tests/test_gpu_step_trim.py: infidelity, leak and both gradients as float.hex() 
 
     python3 scripts/record_step_trim.py [DIR]          (default: tests/golden/step_trim; needs a GPU; library: JQ_LIB or the built one)
 
-The committed files were written by the build BEFORE the per-step trims (JQ_STEP_TRIM, csrc/jq_kernels.h): the trims keep every
+The committed files were written by the build BEFORE the per-step trims (LKC, CWH, PK in csrc/jq_kernels.h): the trims keep every
 floating-point operation, its operands and its order, so the kernels must reproduce these files bit for bit."""
 import json
 import os

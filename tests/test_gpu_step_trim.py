@@ -1,5 +1,5 @@
-"""GPU (-m gpu): the per-step trims of the three-slab quad-layout kernels (JQ_STEP_TRIM, csrc/jq_kernels.h: carried leak integrand,
-hoisted shift table, packed early trace reductions; one pass for the two K05 products of use 6 is built with bit 3 only) remove repeated work only -- the same
+"""GPU (-m gpu): the per-step trims of the three-slab quad-layout kernels (LKC, CWH, PK in csrc/jq_kernels.h: carried leak integrand,
+hoisted shift table, packed early trace reductions) remove repeated work only -- the same
 floating-point operations on the same values in the same order.  tests/golden/step_trim/ holds what the build BEFORE them returned
 (scripts/record_step_trim.py, float.hex() strings); the kernels must reproduce it exactly.  3 072 samples each:
   a  cnot3 x 300 steps, perturbed ensemble: one chunk of even length
