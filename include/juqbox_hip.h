@@ -43,7 +43,7 @@ extern "C" {
  *     the rank of a full weight matrix; full leakage weights with the Jacobi solver;
  * 6 = continuation adjoints: jq_update_dvds, jq_set_sv_type, jq_get_sv_type (params.dVds_r / dVds_i / sv_type); later, with no
  *     change of a layout or of an existing entry point: jq_s_uniform (host-only structure test), jq_traceobjgrad_batch (many control
- *     vectors of one problem in one call). */
+ *     vectors of one problem in one call), jq_eval_f_g_grad_batch (many control vectors x the nodes of one ensemble in one call). */
 #define JQ_ABI_VERSION 6
 
 #define JQ_MAX_CONTROLS 16 /* control Hamiltonians the fast kernels hold in registers; more: cooperative kernels (no limit)    */
@@ -374,6 +374,28 @@ int jq_state_populations(jq_handle *h, const double *pcof, int32_t ncoeff, const
 int jq_eval_f_g_grad(jq_handle *h, const double *pcof, int32_t ncoeff, const double *nodes, const double *weights,
                      int32_t nquad, const double *shift, int32_t compute_adjoint, double *out2, double *infid_grad,
                      double *leak_grad);
+
+/*
+ * npcof risk-neutral evaluations jq_eval_f_g_grad(pcofs[:, i], nodes, weights, shift, ...) of ONE problem over ONE set of nodes:
+ * multi-start optimisation, batched line searches, finite-difference checks of the risk-neutral gradient, population optimisers,
+ * robustness curves of several pulses.
+ * pcofs: [ncoeff x npcof] column-major; out2: [2 x npcof]; infid_grad / leak_grad: [ncoeff x npcof] (NULL allowed when
+ * compute_adjoint == 0); node_out: [4 x nquad x npcof] or NULL -- per vector and node the record of jq_traceobj_sweep.
+ * Column i of every output equals what jq_eval_f_g_grad (node_out: jq_traceobj_sweep) returns for pcofs[:, i] under the handle's
+ * current settings (sv_type, weights, solver, target, objFuncType) -- bit for bit on the same kernel variant and chunk length.
+ * Grouped batches: Stormer-Verlet with the Neumann solver on the row-lane (family 3) and cooperative-quad kernels (family 8, its dense
+ * policy included).  A vector's nquad * N columns are laid out as the single call lays them out and padded to a whole wave / column
+ * quad (zero-weight slots / samples); the next vector starts at the next one, every workgroup reads the tile stream of its vector.  A
+ * launch takes as many vectors as keep its samples inside what the family accepts for an ensemble (option pcof_batch_max: fewer),
+ * larger batches run in rounds.  Everything else -- implicit midpoint, the Jacobi solver, the other kernel families, an ensemble that
+ * is itself too large for families 3 / 8, cooperative quad with N not dividing 16 and not beyond it -- runs one ensemble evaluation
+ * per vector inside the call.  jq_plan_info reports what the last call did ("pcof_batch": mode, vectors_per_launch, nodes_per_vector).
+ * Errors: the single call's codes for the coefficient count, JQ_EINVAL for NULL required pointers, npcof < 1 or nquad < 1; a refused
+ * call writes nothing.  Multi-device handles shard the VECTORS (jq_shard_bounds); the nodes of a vector stay on one device.
+ */
+int jq_eval_f_g_grad_batch(jq_handle *h, const double *pcofs, int32_t ncoeff, int32_t npcof, const double *nodes,
+                           const double *weights, int32_t nquad, const double *shift, int32_t compute_adjoint, double *out2,
+                           double *infid_grad, double *leak_grad, double *node_out);
 
 /*
  * The same evaluation with the result left ON THE DEVICE for a caller that runs its own collective (one process per GPU:

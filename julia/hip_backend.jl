@@ -339,6 +339,33 @@ function eval_f_g_grad!(pcof::Vector{Float64}, params::objparams, wa::AbstractWo
     params.lastLeakIntegral = params.last_leak
 end
 
+# eval_f_g_grad! for many control vectors over ONE set of nodes in one call (jq_eval_f_g_grad_batch): column i of every result is what
+# eval_f_g_grad!(pcofs[:, i], ...) leaves in params.last_* -- which this method does not touch (they memoise one vector).  On the
+# latency kernels (row-lane, cooperative quad; Stormer-Verlet) launches hold G vectors x nquad nodes, elsewhere one ensemble per vector.
+# Returns (infidelity[n], leak[n], infid_grad[ncoeff, n], leak_grad[ncoeff, n] -- 0 x n for objFuncType == 1) and with per_node = true
+# also the 4 x nquad x n array of traceobj_sweep records.
+function eval_f_g_grad_batch(pcofs::Matrix{Float64}, params::objparams, wa::AbstractWorkingArraysHIP, nodes::AbstractArray,
+                             weights::AbstractArray, compute_adjoint::Bool = true; shift = nothing, per_node::Bool = false)
+    ncoeff, n = size(pcofs)
+    n >= 1 || throw(ArgumentError("eval_f_g_grad_batch: need at least one control vector"))
+    nd = collect(Float64, nodes); wt = collect(Float64, weights)
+    (length(nd) == length(wt) && length(nd) >= 1) || throw(ArgumentError("eval_f_g_grad_batch: nodes and weights must have the same length >= 1"))
+    sync!(wa, params)
+    out2 = zeros(2, n)
+    ig = zeros(ncoeff, compute_adjoint ? n : 0); lg = similar(ig)
+    node_out = zeros(4, length(nd), per_node ? n : 0)
+    sh = shift === nothing ? C_NULL : pointer(shift)
+    GC.@preserve shift begin
+        jqcheck(wa, ccall((:jq_eval_f_g_grad_batch, libjq), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+            wa.handle, pcofs, ncoeff, n, nd, wt, length(nd), sh, compute_adjoint ? 1 : 0, out2,
+            compute_adjoint ? pointer(ig) : C_NULL, compute_adjoint ? pointer(lg) : C_NULL, per_node ? pointer(node_out) : C_NULL))
+    end
+    compute_adjoint || (ig = zeros(ncoeff, n); lg = zeros(ncoeff, n))
+    res = (out2[1, :], out2[2, :], ig, (params.objFuncType == 1 ? zeros(0, n) : lg))
+    return per_node ? (res..., node_out) : res
+end
+
 # One process per GPU (MPI.jl): each rank evaluates its shard and leaves the packed sums on its device; the caller
 # all-reduces `d_packed` (2 + 2 nCoeff doubles on the GPU, e.g. a ROCArray) over the ranks.
 function shard_bounds(nquad::Integer, rank::Integer, world::Integer)

@@ -85,6 +85,7 @@ SYMBOLS = {
     "jq_traceobj_sweep": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_i32, c_dp, c_i32, c_dp, c_dp]),
     "jq_plan_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, c_i32]),
     "jq_s_uniform": (ctypes.c_int, [c_dp, c_i32, c_i32]),
+    "jq_eval_f_g_grad_batch": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_i32, c_i32, c_dp, c_dp, c_i32, c_dp, c_i32, c_dp, c_dp, c_dp, c_dp]),
     "jq_traceobjgrad_batch": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_i32, c_i32, c_i32, c_dp, c_dp, c_dp, c_dp]),
     "jq_last_timing": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(jq_timing)]),
     "jq_version": (ctypes.c_char_p, []),

@@ -543,14 +543,16 @@ __global__ __launch_bounds__(256) void k_pop_max(const double* __restrict__ hr, 
 // ---------------------------------------------------------------------------------------------
 // Row-lane kernels (jq_rowlane_kernels.h): initial state and terminal condition in their state-file layout
 // state file <- (Uinit, 0, ...).  uinit: [N][16] (column ic of Uinit, zero padded).  grid = waves, block = 64
-// cpw: columns per wave (4, or N*floor(4/N) in the sample-aligned packing of the implicit-midpoint kernels)
+// Column packing: every `cpw` consecutive columns start at a fresh group of `wpg` waves and fill its 4 wpg slots from the front.
+// wpg = 1: columns per wave (4, or N*floor(4/N) in the sample-aligned packing of the implicit-midpoint kernels); grouped batches: cpw = the
+// columns of one control vector (a multiple of N), wpg = the waves it owns
 __global__ void k_init_state_rowlane(double* state, long long nw, const double* __restrict__ uinit, int N, long long ncols_used,
-                                     int cpw)
+                                     int cpw, int wpg)
 {
     const int lane = threadIdx.x;
     const long long w = blockIdx.x;
-    const int c = lane >> 4;
-    const long long col = w * cpw + c;
+    const int c = 4 * (int)(w % wpg) + (lane >> 4);      // slot inside the group
+    const long long col = (w / wpg) * cpw + c;
     for (int r = 0; r < JQ_ROWLANE_ROWS; ++r) {
         double val = 0.0;
         if (r == 0 && c < cpw && col < ncols_used) val = uinit[(col % N) * 16 + (lane & 15)];
@@ -560,17 +562,18 @@ __global__ void k_init_state_rowlane(double* state, long long nw, const double* 
 
 // fidelity, leak and adjoint terminal condition per sample (thread per sample; see k_terminal)
 // (mode, dvr, dvi: see k_terminal; the dVds image has the layout of vtr / vti)
-// cpw: columns per wave (4; grouped batches with N < 4: N, so that every wave holds the columns of one control vector)
+// cpw, wpg: the column packing of k_init_state_rowlane (4, 1; grouped batches: the columns and the waves of one control vector, so that
+// no wave holds the columns of two)
 __global__ void k_terminal_rowlane(double* state, long long nw, const double* __restrict__ vtr, const double* __restrict__ vti,
                                    int N, int nsamples, double leak_scale, double* res, const double* __restrict__ dvr,
-                                   const double* __restrict__ dvi, int mode, int cpw)
+                                   const double* __restrict__ dvi, int mode, int cpw, int wpg)
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nsamples) return;
     double re = 0.0, im = 0.0, lk = 0.0;
     for (int ic = 0; ic < N; ++ic) {
         const long long col = (long long)s * N + ic;
-        const size_t base = (size_t)(col / cpw) * 64 + (size_t)(col % cpw) * 16;
+        const size_t base = (size_t)(col / cpw) * wpg * 64 + (size_t)(col % cpw) * 16;
         for (int r = 0; r < 16; ++r) {
             const double u = state[base + r], v = state[(size_t)nw * 64 + base + r];
             const double tr = vtr[ic * 16 + r], ti = vti[ic * 16 + r];
@@ -585,7 +588,7 @@ __global__ void k_terminal_rowlane(double* state, long long nw, const double* __
     if (mode >= 3) {      // s_D: the same sums against the dVds image
         for (int ic = 0; ic < N; ++ic) {
             const long long col = (long long)s * N + ic;
-            const size_t base = (size_t)(col / cpw) * 64 + (size_t)(col % cpw) * 16;
+            const size_t base = (size_t)(col / cpw) * wpg * 64 + (size_t)(col % cpw) * 16;
             for (int r = 0; r < 16; ++r) {
                 const double u = state[base + r], v = state[(size_t)nw * 64 + base + r];
                 const double tr = dvr[ic * 16 + r], ti = dvi[ic * 16 + r];
@@ -601,7 +604,7 @@ __global__ void k_terminal_rowlane(double* state, long long nw, const double* __
     const double *xr = from_d ? dvr : vtr, *xi = from_d ? dvi : vti;
     for (int ic = 0; ic < N; ++ic) {
         const long long col = (long long)s * N + ic;
-        const size_t base = (size_t)(col / cpw) * 64 + (size_t)(col % cpw) * 16;
+        const size_t base = (size_t)(col / cpw) * wpg * 64 + (size_t)(col % cpw) * 16;
         for (int r = 0; r < 16; ++r) {
             const double tr = xr[ic * 16 + r], ti = xi[ic * 16 + r];
             double lr = jq_dot2(aim, ti, are, tr) / N, nb = -(jq_det2(aim, tr, are, ti) / N);

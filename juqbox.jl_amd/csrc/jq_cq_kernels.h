@@ -598,10 +598,10 @@ __device__ __forceinline__ CqSetup<NT> cq_setup(const PropArgs& a)
 {
     return cq_setup<NT>(a, (int)blockIdx.x >> 2, (int)blockIdx.x & 3);
 }
-// Grouped batch (one column quad per workgroup): a control vector owns max(1, N / 4) consecutive quads, N > 16: those of its `parts` slabs
+// Grouped batch (one column quad per workgroup): a control vector owns a.group_units consecutive quads (the host pads its samples to whole quads)
 __device__ __forceinline__ const double* cq_group_stream(const PropArgs& a)
 {
-    return jq_group_stream(a, (int)blockIdx.x, a.parts > 1 ? 4 * a.parts : a.N > 4 ? a.N >> 2 : 1);
+    return jq_group_stream(a, (int)blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------

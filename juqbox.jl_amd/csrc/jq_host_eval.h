@@ -74,7 +74,7 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
     const long long ncols_split = (long long)nsamples * h->N;
     const bool small_family_batch = (h->rl_npj > 0 && ncols_split <= h->rl_max_cols) ||
                                     (h->lane_np > 0 && ncols_split >= h->lane_min_cols && ncols_split <= h->lane_max_cols);
-    if (!h->in_split && !small_family_batch && h->wrank == 0 && h->quad_max_slabs > 0 && h->integrator == 1 && h->solver_id == 1 && !hist_r && eps && nsamples > 1 && !h->opt.on(O_NOSPLIT)) {
+    if (!h->in_split && h->grp_G == 0 && !small_family_batch && h->wrank == 0 && h->quad_max_slabs > 0 && h->integrator == 1 && h->solver_id == 1 && !hist_r && eps && nsamples > 1 && !h->opt.on(O_NOSPLIT)) {
         // candidates: the largest number of FULL rounds of the quad-layout kernels with 1, 2 or 3 slabs per workgroup
         long long n_main = 0;
         double best = t4_plan_cost(h, nsamples) - 1e-9;
@@ -122,9 +122,11 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
     if (rc) return rc;
     const int D1 = ncoeff / (2 * h->Nc * h->Nfreq);  // src/evalobjgrad.jl:608
     if (nsamples < 1) return fail(h, JQ_EINVAL, "need at least one sample");
-    // grouped batch (jq_traceobjgrad_batch): G control vectors, pcof = their G coefficient blocks, nsamples = G x spg samples
-    const int G = h->grp_G, spg = h->grp_spg;
-    if (G > 0 && (nsamples != G * spg || eps || wgt || shift || hist_r || d_packed)) return fail(h, JQ_EHIP, "internal error: grouped batch with ensemble arguments");
+    // grouped batch (jq_traceobjgrad_batch, jq_eval_f_g_grad_batch): G control vectors, pcof = their G coefficient blocks, nsamples = G x spg
+    // samples: per vector the grp_Q samples of the caller (eps, wgt: [grp_Q], the same nodes for every vector; without them one sample of
+    // weight 1) and the padding that ends its last column quad
+    const int G = h->grp_G, spg = h->grp_spg, Q = h->grp_Q;
+    if (G > 0 && (nsamples != G * spg || Q < 1 || Q > spg || hist_r || d_packed)) return fail(h, JQ_EHIP, "internal error: grouped batch with a state history or a packed result");
     const int nvec = G > 0 ? G : 1;      // (coefficient blocks, tile streams, gradients of the launch)
     // Structure embedding (try_embed): batches that would run on the dense / band MFMA families go to the embedded twin,
     // whose operators have the JQ_BW_T4 structure (quad-layout / JQ_BW_T4 slab kernels).  State histories stay here (their
@@ -134,9 +136,9 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
         std::vector<double> sh(e->Ntot, 0.0);
         for (int i = 0; i < h->Ntot; ++i)   // (default: the reference's 0.01 * 10^(j-2) by the USER's level index, src/ipopt_interface.jl:41-44)
             sh[h->emb_row[i]] = shift ? shift[i] : (i >= 1 ? 0.01 * pow(10.0, (double)(i - 1)) : 0.0);
-        e->grp_G = G, e->grp_spg = spg;      // (a grouped batch stays one: the shift table is not read without eps)
-        const int rc = run_eval(e, pcof, ncoeff, nsamples, eps, wgt, G > 0 ? nullptr : sh.data(), adjoint, nullptr, nullptr, out, d_packed);
-        e->grp_G = 0, e->grp_spg = 1;
+        e->grp_G = G, e->grp_spg = spg, e->grp_Q = Q;      // (a grouped batch stays one)
+        const int rc = run_eval(e, pcof, ncoeff, nsamples, eps, wgt, sh.data(), adjoint, nullptr, nullptr, out, d_packed);
+        e->grp_G = 0, e->grp_spg = 1, e->grp_Q = 1;
         if (rc != JQ_OK) h->err = e->err;
         h->timing = e->timing;
         return rc;
@@ -146,11 +148,17 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
     rc = plan_batch(h, nsamples, adjoint, hist_r != nullptr, gate_hold, &p, G);
     if (rc) return rc;
     if (p.groups != G) return fail(h, JQ_EHIP, "internal error: grouped batch on a kernel family that does not serve one");
-    std::vector<double> gwgt;
-    if (G > 0 && spg > 1) {      // (the padding samples of a vector's column quad weigh nothing -- like the unused columns of a single evaluation's quad)
+    std::vector<double> gwgt, geps;
+    if (G > 0 && (spg > 1 || eps || wgt)) {      // (the padding samples of a vector's column quad weigh nothing -- like the unused columns of a single evaluation's quad)
         gwgt.assign((size_t)nsamples, 0.0);
-        for (int g = 0; g < G; ++g) gwgt[(size_t)g * spg] = 1.0;
+        if (eps) geps.assign((size_t)nsamples, 0.0);
+        for (int g = 0; g < G; ++g)
+            for (int q = 0; q < Q; ++q) {
+                gwgt[(size_t)g * spg + q] = wgt ? wgt[q] : 1.0;
+                if (eps) geps[(size_t)g * spg + q] = eps[q];
+            }
         wgt = gwgt.data();
+        if (eps) eps = geps.data();
     }
     const bool imr = (h->integrator == 2);
     const bool cq3 = p.cq_nr > 0, qsplit = p.qs_qw > 0;
@@ -197,7 +205,7 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
     if (p.layout != SL_SLABS) {   // [eps per column slot | weight per column slot]  (lane kernels: cpw = 4, one slot per column)
         for (long long c = 0; c < ncols_used; ++c) {
             const int smp = (int)(c / h->N);
-            const long long slot = (c / p.cpw) * 4 + (c % p.cpw);
+            const long long slot = (c / p.cpw) * 4 * p.wpg + (c % p.cpw);
             colinfo[slot] = eps ? eps[smp] : 0.0;
             colinfo[p.ncols + slot] = wgt ? wgt[smp] : 1.0;
             if (eps && eps[smp] != 0.0) use_shift = true;
@@ -231,7 +239,7 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
     const double dt = h->T / h->nsteps;
     PropArgs a;
     memset(&a, 0, sizeof a);
-    a.stream = h->d_stream; a.stream_gstride = (long long)gstride; a.cimg = p.cimg; a.state = h->d_state; a.colinfo = h->d_colinfo;
+    a.stream = h->d_stream; a.stream_gstride = (long long)gstride; a.group_units = G > 0 ? p.upg : 1; a.cimg = p.cimg; a.state = h->d_state; a.colinfo = h->d_colinfo;
     a.traces = h->d_traces;
     a.tabs = h->d_tabs; a.stride = p.stride; a.pieces = (int)(p.stride * 8 / 1024); a.m = h->m;
     a.nslabs = p.prop_nslabs; a.Ncoupled = ctrl_gstart(h->Nc, 1) /* first control group */; a.Ntot = h->Ntot; a.N = h->N; a.use_shift = use_shift ? 1 : 0;
@@ -266,7 +274,7 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
 
     if (p.layout == SL_ROWLANE)
         hipLaunchKernelGGL(k_init_state_rowlane, dim3((unsigned)p.nwaves_rl), dim3(64), 0, s, h->d_state, p.nwaves_rl, h->d_uinit_r, h->N,
-                           ncols_used, p.cpw);
+                           ncols_used, p.cpw, p.wpg);
     else if (p.layout == SL_LANE)
         hipLaunchKernelGGL(p.klinit, dim3((unsigned)(p.ncols / 64)), dim3(64), 0, s, h->d_state, p.ncols, h->d_uinit_l, h->N, ncols_used);
     else
@@ -311,7 +319,7 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
                            h->d_vti_r, h->N, nsamples, leak_scale, h->d_res, p.cpw);
     else if (p.term == TK_ROWLANE)
         hipLaunchKernelGGL(k_terminal_rowlane, dim3((nsamples + 63) / 64), dim3(64), 0, s, h->d_state, p.nwaves_rl, h->d_vtr_r,
-                           h->d_vti_r, h->N, nsamples, leak_scale, h->d_res, h->d_dvr_r, h->d_dvi_r, sv_mode, p.cpw);
+                           h->d_vti_r, h->N, nsamples, leak_scale, h->d_res, h->d_dvr_r, h->d_dvi_r, sv_mode, p.cpw, p.wpg);
     else if (p.term == TK_LANE)
         hipLaunchKernelGGL(p.klterm, dim3((nsamples + 63) / 64), dim3(64), 0, s, h->d_state, p.ncols, h->d_vtr_l, h->d_vti_l, h->N,
                            nsamples, leak_scale, h->d_res, h->d_dvr_l, h->d_dvi_l, sv_mode);

@@ -150,10 +150,10 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
         kv("latency_split", std::string("{\"last_decision\": \"") + d + "\", \"faults\": " + num(t2->cq3_faults) + ", \"faults_xcd\": " + num(t2->cq3_faults_xcd) + ", \"abandoned_at_rendezvous\": " + num(t2->cq3_busy) + ", \"cooling_down\": " + num(t2->cq3_skip) +
                                 ", \"off\": " + (t2->cq3_off ? "true" : "false") + "}");
     }
-    // jq_traceobjgrad_batch: what the last call did with its control vectors -- "grouped" (one launch for many vectors, each workgroup reading
+    // jq_traceobjgrad_batch / jq_eval_f_g_grad_batch (nodes_per_vector: 1 / its nquad): what the last call did with its control vectors -- "grouped" (one launch for many vectors, each workgroup reading
     // the tile stream of its own) or "sequential" (the single evaluation per vector), and why
     kv("pcof_batch", std::string("{\"mode\": \"") + (h->pb_mode.empty() ? "none yet" : h->pb_mode) + "\", \"family\": " + num(h->pb_family) + ", \"vectors_per_launch\": " + num(h->pb_per_launch) +
-                         ", \"reason\": \"" + h->pb_why + "\"}");
+                         ", \"nodes_per_vector\": " + num(h->pb_nodes) + ", \"reason\": \"" + h->pb_why + "\"}");
     o += "}";
     if (buflen > 0) {
         const size_t n = std::min(o.size(), (size_t)buflen - 1);

@@ -466,3 +466,39 @@ static int multi_traceobjgrad_batch(jq_handle* h, const double* pcofs, int ncoef
     multi_timing(h, 0.0);
     return JQ_OK;
 }
+
+// jq_eval_f_g_grad_batch on a multi-device handle: the control vectors are block-partitioned over the devices (jq_shard_bounds), the nodes
+// of a vector stay together -- every output column belongs to one vector, so there is nothing to reduce
+static int multi_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int ncoeff, int npcof, const double* nodes, const double* weights, int nquad,
+                                     const double* shift, int compute_adjoint, double* out2, double* infid_grad, double* leak_grad, double* node_out)
+{
+    DeviceGuard guard;
+    const int nd = (int)h->subs.size();
+    // (a refused call writes nothing: the coefficient count is checked before any device starts)
+    if (int rc = check_ncoeff(h->subs[0], ncoeff)) {
+        h->err = h->subs[0]->err;
+        return rc;
+    }
+    std::vector<int> rcs(nd, JQ_OK);
+    std::vector<std::thread> th;
+    for (int d = 0; d < nd; ++d)
+        th.emplace_back([&, d]() {
+            jq_handle* sub = h->subs[d];
+            int lo = 0, hi = 0;
+            jq_shard_bounds(npcof, d, nd, &lo, &hi);
+            sub->timing = jq_timing{};
+            const size_t off = (size_t)ncoeff * lo;
+            if (hi > lo)
+                rcs[d] = jq_eval_f_g_grad_batch(sub, pcofs + off, ncoeff, hi - lo, nodes, weights, nquad, shift, compute_adjoint, out2 + (size_t)2 * lo,
+                                                infid_grad ? infid_grad + off : nullptr, leak_grad ? leak_grad + off : nullptr,
+                                                node_out ? node_out + (size_t)4 * nquad * lo : nullptr);
+        });
+    for (auto& t : th) t.join();
+    for (int d = 0; d < nd; ++d)
+        if (rcs[d] != JQ_OK) {
+            h->err = h->subs[d]->err;
+            return rcs[d];
+        }
+    multi_timing(h, 0.0);
+    return JQ_OK;
+}

@@ -131,9 +131,10 @@ struct BatchPlan {
     // geometry (prop_nslabs: PropArgs::nslabs -- waves of the row-lane kernels, columns of the lane kernels; bwd_block_ng2: backward
     // sweeps of two or more controls)
     int nslabs, prop_nslabs, cpw, qps, qs_blocks, trace_rows, cs;
-    // grouped batch (jq_traceobjgrad_batch): control vectors of the launch (0: not grouped -- also the answer to a request the chosen family
-    // cannot serve) and the units one vector owns = its trace rows (row-lane: waves, cooperative quad: column quads)
-    int groups, upg;
+    // grouped batch (jq_traceobjgrad_batch, jq_eval_f_g_grad_batch): control vectors of the launch (0: not grouped -- also the answer to a
+    // request the chosen family cannot serve) and the units one vector owns = its trace rows (row-lane: waves, cooperative quad: column
+    // quads; PropArgs::group_units); wpg: waves that every cpw columns of the row-lane layouts start afresh at (1 unless grouped)
+    int groups, upg, wpg;
     long long nwaves_rl, ncols, nq_pad, stride;
     unsigned fwd_grid, fwd_block, bwd_grid, bwd_block, bwd_block_ng2;
     const double *himg, *cimg;
@@ -159,11 +160,12 @@ static long long plan_trace_tiles(const jq_handle* h, const BatchPlan& p, int q)
 //   Stormer-Verlet:    row-lane (3) > lane (2) > cooperative quad (8) > quad layout (6) > cooperative (1) > slab (0).
 // Side effects: the split latency kernels' cool-down (cq3_skip, cq3_last: once per evaluation of those families with a gradient) and,
 // when they are taken, the device held exclusively in gate_hold until the caller's scope ends.
-// groups > 0: a GROUPED batch of that many control vectors (nsamples = groups x samples per vector), every workgroup working for exactly
-// one of them: Stormer-Verlet on the row-lane kernels (a vector per wave or waves: N < 4 packs N columns per wave, cpw) and on the
-// cooperative-quad kernels (a vector per column quad or consecutive quads; one workgroup per quad in both sweeps -- no two-quad forward
-// variant, no split backward kernels).  Column counts that would put two vectors into one wave / quad, and every other family, answer
-// p->groups = 0: the caller evaluates the vectors one after the other.  A grouped plan has no side effects.
+// groups > 0: a GROUPED batch of that many control vectors (nsamples = groups x samples per vector -- one, or the nodes of an ensemble with
+// the padding samples the caller added), every workgroup working for exactly one of them: Stormer-Verlet on the row-lane kernels (a vector's
+// columns packed four per wave like an ensemble of its samples, the next vector at the next wave: cpw, wpg) and on the cooperative-quad
+// kernels (a vector per column quad or consecutive quads, packed like an ensemble of its samples; one workgroup per quad in both sweeps --
+// no two-quad forward variant, no split backward kernels).  Column counts that would put two vectors into one quad, and every other
+// family, answer p->groups = 0: the caller evaluates the vectors one after the other.  A grouped plan has no side effects.
 static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateHold& gate_hold, BatchPlan* p, int groups = 0)
 {
     memset(p, 0, sizeof *p);
@@ -190,7 +192,9 @@ static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateH
     p->hbm = imr_coop && h->NT <= 6 && h->mat_elems_c > 0 && coop_imr_lds_bytes(h->NT, h->mat_elems_c) > JQ_LDS_MAX;
     if (imr_coop && (h->mat_elems_c == 0 || (p->hbm && !(h->NT == 6 && h->BWc == 5))))
         return fail(h, JQ_EUNSUPPORTED, "implicit midpoint: no kernels for these operators (no cooperative layout / images that do not fit the LDS)");
-    p->cpw = imr_rl ? imr_cols_per_wave(h->N) : (grp && h->N < 4) ? h->N : 4;   // columns per wave of the row-lane kernels
+    const int spv = grp ? nsamples / groups : 1;      // samples of one control vector
+    p->cpw = imr_rl ? imr_cols_per_wave(h->N) : grp ? spv * h->N : 4;   // columns per wave of the row-lane kernels (grouped: per vector, on wpg waves)
+    p->wpg = (grp && !imr_rl) ? (spv * h->N + 3) / 4 : 1;
     // Full leakage weights (jq_update_wmat): row-lane kernels for every batch of an Ntot <= 16 problem, quad-layout kernels with one slab
     // per workgroup for the 4 x 4 x n structure (cooperative-quad kernels: wfull_cq below), else the cooperative kernels (every batch size)
     // or where those do not exist the slab kernels <1, 0> / <6, 5>; no lane or JQ_BW_T4 slab kernels
@@ -200,7 +204,7 @@ static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateH
     const bool wjac = wfull && h->solver_id == 2;      // full weights with the Jacobi solver: cooperative kernels, else the slab kernels <1, 0> / <6, 5>
     const bool rl = imr_rl || (!imr && h->rl_npj > 0 && h->solver_id == 1 && (ncols_used <= h->rl_max_cols || wfull));
     const bool lane = !imr && !rl && !wfull && h->lane_np > 0 && h->solver_id == 1 && ncols_used >= h->lane_min_cols && ncols_used <= h->lane_max_cols;
-    p->nwaves_rl = (ncols_used + p->cpw - 1) / p->cpw;
+    p->nwaves_rl = (ncols_used + p->cpw - 1) / p->cpw * p->wpg;
     p->ncols = rl ? 4 * p->nwaves_rl : (ncols_used + 63) / 64 * 64;      // row-lane: column SLOTS (4 per wave)
     // JQ_BW_T4 structure: the quad-layout kernels (a slab per wave quartet: 3 x shorter dependent chain than the cooperative kernels)
     if (!imr && !lane && !rl && h->solver_id == 1 && p->nslabs <= h->quad_max_slabs) {
@@ -304,9 +308,12 @@ static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateH
               : lane ? KF_LANE : cq ? KF_CQ : quad ? KF_QUAD : coop ? KF_COOP : KF_SLAB;
     p->layout = rl ? SL_ROWLANE : lane ? SL_LANE : SL_SLABS;
     if (grp) {      // units per vector; only column counts under which the single evaluation has the same layout (bit-identical results)
-        const bool n4 = h->N < 4 || h->N % 4 == 0;
-        if (p->family == KF_ROWLANE && !hist && n4) p->upg = h->N > 4 ? h->N / 4 : 1;
-        else if (p->family == KF_CQ && !hist && (h->parts > 1 || 16 % h->N == 0)) p->upg = h->parts > 1 ? 4 * h->parts : h->N > 4 ? h->N / 4 : 1;
+        const bool n4 = spv > 1 || h->N < 4 || h->N % 4 == 0;      // (one sample per vector: the column counts jq_traceobjgrad_batch has always grouped)
+        if (nsamples != groups * spv) return JQ_OK;
+        if (p->family == KF_ROWLANE && !hist && n4) p->upg = p->wpg;
+        // (cooperative quad: full slabs of whole samples, so that a quad is a trace row and holds one vector -- the caller pads with samples)
+        else if (p->family == KF_CQ && !hist && h->parts > 1) p->upg = 4 * h->parts * spv;
+        else if (p->family == KF_CQ && !hist && 16 % h->N == 0 && (spv * h->N) % 4 == 0) p->upg = spv * h->N / 4;
         if (p->upg == 0) return JQ_OK;      // (p->groups == 0: not served)
         p->groups = groups;
     }

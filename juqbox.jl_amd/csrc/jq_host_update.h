@@ -8,6 +8,8 @@ static int multi_traceobj_sweep(jq_handle* h, const double* pcof, int ncoeff, co
                                 double* out);
 static int multi_traceobjgrad_batch(jq_handle* h, const double* pcofs, int ncoeff, int npcof, int evaladjoint, double* out4, double* totalgrad,
                                     double* infidelgrad, double* leakgrad);
+static int multi_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int ncoeff, int npcof, const double* nodes, const double* weights, int nquad,
+                                     const double* shift, int compute_adjoint, double* out2, double* infid_grad, double* leak_grad, double* node_out);
 // a single evaluation cannot be sharded: multi-device handles run it on their first device
 #define JQ_ON_FIRST(h, call)                         \
     if (!(h)->subs.empty()) {                        \

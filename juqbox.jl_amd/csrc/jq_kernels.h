@@ -1042,15 +1042,18 @@ struct PropArgs {
     int wait_polls;
     // Grouped batches (jq_traceobjgrad_batch; row-lane and cooperative-quad kernels only): the chunk holds one tile stream per control
     // vector, `stream_gstride` doubles apart; a workgroup reads the stream of the vector its columns belong to (jq_group_stream).
-    // 0: one stream for everybody.  No other kernel reads this field.
+    // 0: one stream for everybody.  group_units: the units of the launch one vector owns (row-lane kernels: waves, cooperative-quad kernels:
+    // column quads) -- a run-time number, a vector may bring the nodes of an ensemble along (jq_eval_f_g_grad_batch); 1 when nothing is
+    // grouped.  No other kernel reads these fields.
     long long stream_gstride;
+    int group_units;
 };
 // The tile stream of the control vector that unit `unit` of the launch (row-lane kernels: wave, cooperative-quad kernels: column quad)
-// works for, `upg` units per vector.  Wave-uniform by construction (block index and kernel arguments); the readfirstlane says so to the
+// works for, a.group_units units per vector.  Wave-uniform by construction (block index and kernel arguments); the readfirstlane says so to the
 // compiler, so that the DMA keeps its scalar base.
-__device__ __forceinline__ const double* jq_group_stream(const PropArgs& a, int unit, int upg)
+__device__ __forceinline__ const double* jq_group_stream(const PropArgs& a, int unit)
 {
-    const int g = __builtin_amdgcn_readfirstlane(unit / upg);
+    const int g = __builtin_amdgcn_readfirstlane(unit / a.group_units);
     return a.stream + (size_t)g * (size_t)a.stream_gstride;
 }
 #ifndef JQ_MAX_WRANK

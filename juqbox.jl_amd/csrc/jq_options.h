@@ -77,7 +77,7 @@ static const JqOptDesc g_jq_opt[O_COUNT] = {
     {"multi_same_device", 0, 0, "TEST MODE of jq_create_multi: 1 = up to 16 sub-handles may share physical GPUs, host-side sum in place of the all-reduce"},
     {"cq3_rdv_us", JQ_OPT_UNSET, 0, "two- / three-workgroup latency kernels: microseconds the workgroups of a launch wait for each other at its start before the launch is abandoned and the evaluation repeated on one workgroup per quad (default: one launch duration, 2 .. 100 ms)"},
     {"cq3_wait_ms", JQ_OPT_UNSET, 0, "two- / three-workgroup latency kernels: milliseconds a wait between roles may take after a passed rendezvous before the launch is declared dead (default: 10 x the launch's expected duration, at least 50 ms)"},
-    {"pcof_batch_max", JQ_OPT_UNSET, 0, "jq_traceobjgrad_batch: control vectors per launch of a grouped batch (default: one vector's workgroups per compute unit; 0: the vectors one after the other; larger batches run in rounds, bit-identical)"},
+    {"pcof_batch_max", JQ_OPT_UNSET, 0, "jq_traceobjgrad_batch / jq_eval_f_g_grad_batch: control vectors per launch of a grouped batch (default: one vector's workgroups per compute unit, with an ensemble per vector as many as the kernel family accepts samples for; 0: the vectors one after the other; larger batches run in rounds, bit-identical)"},
     {"debug", 0, JQ_OPT_HOOK, "bit 16 / 32: the consumer roles / the state role of the split latency kernels start ~ 5 ms late (results unchanged); bits 1, 2, 4, 8: profiling experiments with WRONG results (experiment builds only)"},
     {"cq3_fault", 0, JQ_OPT_HOOK, "1: the split latency kernels report a dead wait, 3: a failed start-up rendezvous (exercises fall-back and cool-down)"},
 };

@@ -457,10 +457,10 @@ struct RowW {
 #define JQ_ROWLANE_ARRAYS 4                                   // U, V, MU, NB
 #define JQ_ROWLANE_ROWS (JQ_ROWLANE_ARRAYS + JQ_MAXNC + 1)    // + carry rows + leak row
 
-// Grouped batch: a control vector owns max(1, N / 4) consecutive waves (the host pads the column slots so that no wave holds two vectors)
+// Grouped batch: a control vector owns a.group_units consecutive waves (the host pads the column slots so that no wave holds two vectors)
 __device__ __forceinline__ const double* rl_group_stream(const PropArgs& a)
 {
-    return jq_group_stream(a, (int)blockIdx.x, a.N > 4 ? a.N >> 2 : 1);
+    return jq_group_stream(a, (int)blockIdx.x);
 }
 
 // Forward sweep of one chunk; a.nslabs = number of waves (4 columns each), grid = a.nslabs, block = 64.

@@ -159,10 +159,11 @@ struct jq_handle {
     size_t cap_stream = 0, cap_pq = 0, cap_R = 0;      // doubles of d_stream, d_pq, d_R (jq_create sizes them for one control vector; a grouped batch may grow them)
     // jq_traceobjgrad_batch: the grouped batch run_eval is evaluating -- grp_G control vectors (0: none; pcof then holds grp_G coefficient
     // blocks), each padded to grp_spg samples (cooperative-quad kernels with N < 4: a column quad per vector, the other columns weigh 0) --
+    // of which the first grp_Q are the caller's (jq_eval_f_g_grad_batch: the nodes of its ensemble, the same for every vector) --
     // and what the last call did (jq_plan_info "pcof_batch")
-    int grp_G = 0, grp_spg = 1;
+    int grp_G = 0, grp_spg = 1, grp_Q = 1;
     std::string pb_mode, pb_why;
-    int pb_family = -1, pb_per_launch = 0;
+    int pb_family = -1, pb_per_launch = 0, pb_nodes = 1;
     // Structure embedding (try_embed): a second handle of the SAME problem with its two fastest Kronecker factors zero-padded
     // to 4 levels each (row i1 + d1 i2 + d1 d2 i3 -> i1 + 4 i2 + 16 i3), under which the operators have the JQ_BW_T4 structure;
     // batches that would otherwise run on the dense / band MFMA kernels go there (quad-layout / JQ_BW_T4 slab kernels).
@@ -254,9 +255,10 @@ extern "C" int jq_traceobjgrad(jq_handle* h, const double* pcof, int32_t ncoeff,
     return JQ_OK;
 }
 
-// What jq_traceobjgrad_batch does with npcof control vectors on this (single-device) handle: the number of vectors per launch of a grouped
-// batch (plan_batch with groups), or 0 -- the vectors one after the other -- with the reason in *why.  *spg: samples a vector is padded to.
-static int pcof_batch_per_launch(jq_handle* h, int npcof, bool adjoint, int* spg, int* family, const char** why)
+// What jq_traceobjgrad_batch (Q = 1) / jq_eval_f_g_grad_batch (Q nodes per vector) do with npcof control vectors on this (single-device)
+// handle: the number of vectors per launch of a grouped batch (plan_batch with groups), or 0 -- the vectors one after the other -- with the
+// reason in *why.  *spg: samples a vector is padded to.
+static int pcof_batch_per_launch(jq_handle* h, int npcof, int Q, bool adjoint, int* spg, int* family, const char** why)
 {
     *spg = 1, *family = -1;
     if (h->opt.has(O_PCOF_BATCH_MAX) && h->opt.get(O_PCOF_BATCH_MAX) <= 0) return *why = "option pcof_batch_max=0", 0;
@@ -264,19 +266,21 @@ static int pcof_batch_per_launch(jq_handle* h, int npcof, bool adjoint, int* spg
     if (h->integrator != 1) return *why = "implicit-midpoint integrator: no grouped streams on its kernels", 0;
     if (h->solver_id != 1) return *why = "Jacobi solver: served by the slab / cooperative kernels", 0;
     // Two candidates, in plan_batch's order: row-lane kernels (a vector per wave(s)), cooperative-quad kernels (a vector per column quad(s); a
-    // slab's samples are packed, so with N < 4 a vector brings the padding samples of its quad along).  One vector's workgroups per compute unit;
-    // the candidate stands when the plan of a full launch AND of the last, shorter one choose its family (dry runs: a grouped plan has no side effects).
+    // slab's samples are packed, so a vector brings the padding samples that end its last quad along).  Q = 1: one vector's workgroups per
+    // compute unit.  An ensemble per vector (Q > 1) fills the device by itself (SWAP-02 x 512 nodes: 384 waves): as many vectors as the family
+    // accepts samples for (rl_max_cols, cq_max_quads, dq_max_quads).  The candidate stands when the plan of a full launch AND of the last,
+    // shorter one choose its family (dry runs: a grouped plan has no side effects).
     const int N = h->N;
     *why = "the kernel family of this plan keeps one tile stream per launch (grouped: row-lane and cooperative-quad kernels, column counts 1, 2, 4, 8, 16 or beyond 16)";
     for (int cand = 0; cand < 2; ++cand) {
         const bool rl = cand == 0;
         if (rl && (h->rl_npj == 0 || h->rl_max_cols < N)) continue;
         const jq_handle* t = (!rl && h->emb) ? h->emb : h;      // (the embedded twin serves what the row-lane kernels do not)
-        const int upg = (!rl && t->parts > 1) ? 4 * t->parts : N > 4 ? (N + 3) / 4 : 1;
-        const int s1 = (!rl && N < 4) ? 4 / N : 1;
-        long long gmax = t->num_cu / upg;
-        if (rl) gmax = std::min<long long>(gmax, h->rl_max_cols / N);
-        else gmax = std::min<long long>(gmax, std::max(t->cq_max_quads, t->dq_max_quads) / upg);
+        if (!rl && t->parts == 1 && 16 % N != 0) continue;      // (samples that straddle column quads)
+        const int upg = (!rl && t->parts > 1) ? 4 * t->parts * Q : (Q * N + 3) / 4;
+        const int s1 = (!rl && t->parts == 1) ? 4 * upg / N : Q;
+        long long gmax = rl ? h->rl_max_cols / (Q > 1 ? 4 * upg : N) : std::max(t->cq_max_quads, t->dq_max_quads) / upg;
+        if (Q == 1) gmax = std::min<long long>(gmax, t->num_cu / upg);
         if (h->opt.has(O_PCOF_BATCH_MAX)) gmax = std::min<long long>(gmax, h->opt.get(O_PCOF_BATCH_MAX));
         gmax = std::min<long long>(gmax, npcof);
         if (gmax < 1) continue;
@@ -297,6 +301,17 @@ static int pcof_batch_per_launch(jq_handle* h, int npcof, bool adjoint, int* spg
     return 0;
 }
 
+// timing of a batch call: sums over its launches; family, size, band, variant: those of the last one
+static void batch_add_timing(jq_timing& tsum, const jq_timing& t)
+{
+    const double keep[] = {tsum.ms_total, tsum.ms_propagate, tsum.ms_generate, tsum.ms_forward, tsum.ms_backward};
+    const long long keepn[] = {tsum.n_forward_launches, tsum.n_backward_launches, tsum.mfma_executed, tsum.mfma_backward, tsum.svts};
+    tsum = t;
+    tsum.ms_total += keep[0], tsum.ms_propagate += keep[1], tsum.ms_generate += keep[2], tsum.ms_forward += keep[3], tsum.ms_backward += keep[4];
+    tsum.n_forward_launches += keepn[0], tsum.n_backward_launches += keepn[1], tsum.mfma_executed += keepn[2], tsum.mfma_backward += keepn[3], tsum.svts += keepn[4];
+    tsum.ms_shard_min = tsum.ms_shard_max = tsum.ms_total;
+}
+
 extern "C" int jq_traceobjgrad_batch(jq_handle* h, const double* pcofs, int32_t ncoeff, int32_t npcof, int32_t evaladjoint, double* out4,
                                      double* totalgrad, double* infidelgrad, double* leakgrad)
 {
@@ -311,8 +326,8 @@ extern "C" int jq_traceobjgrad_batch(jq_handle* h, const double* pcofs, int32_t 
     const bool adjoint = evaladjoint != 0;
     int spg = 1, family = -1;
     const char* why = "";
-    const int per = pcof_batch_per_launch(h, npcof, adjoint, &spg, &family, &why);
-    h->pb_mode = per > 0 ? "grouped" : "sequential", h->pb_why = why, h->pb_family = family, h->pb_per_launch = per > 0 ? per : 1;
+    const int per = pcof_batch_per_launch(h, npcof, 1, adjoint, &spg, &family, &why);
+    h->pb_mode = per > 0 ? "grouped" : "sequential", h->pb_why = why, h->pb_family = family, h->pb_per_launch = per > 0 ? per : 1, h->pb_nodes = 1;
     // column i of the outputs from the evaluation's record
     auto put = [&](int i, const double* res, const double* g0, const double* g1) {
         const double primary = res[0], secondary = res[1];
@@ -330,14 +345,7 @@ extern "C" int jq_traceobjgrad_batch(jq_handle* h, const double* pcofs, int32_t 
         }
     };
     jq_timing tsum = {};
-    auto add_timing = [&](const jq_timing& t) {
-        const double keep[] = {tsum.ms_total, tsum.ms_propagate, tsum.ms_generate, tsum.ms_forward, tsum.ms_backward};
-        const long long keepn[] = {tsum.n_forward_launches, tsum.n_backward_launches, tsum.mfma_executed, tsum.mfma_backward, tsum.svts};
-        tsum = t;      // (family, size, band, variant: those of the last launch)
-        tsum.ms_total += keep[0], tsum.ms_propagate += keep[1], tsum.ms_generate += keep[2], tsum.ms_forward += keep[3], tsum.ms_backward += keep[4];
-        tsum.n_forward_launches += keepn[0], tsum.n_backward_launches += keepn[1], tsum.mfma_executed += keepn[2], tsum.mfma_backward += keepn[3], tsum.svts += keepn[4];
-        tsum.ms_shard_min = tsum.ms_shard_max = tsum.ms_total;
-    };
+    auto add_timing = [&](const jq_timing& t) { batch_add_timing(tsum, t); };
     if (per <= 0) {      // every route without grouped streams: the single evaluation, vector by vector
         for (int i = 0; i < npcof; ++i) {
             EvalOut o;
@@ -351,7 +359,7 @@ extern "C" int jq_traceobjgrad_batch(jq_handle* h, const double* pcofs, int32_t 
     for (int i0 = 0; i0 < npcof; i0 += per) {      // rounds of at most `per` vectors (results do not depend on the round a vector runs in)
         const int G = std::min(per, npcof - i0);
         EvalOut o;
-        h->grp_G = G, h->grp_spg = spg;
+        h->grp_G = G, h->grp_spg = spg, h->grp_Q = 1;
         rc = run_eval(h, pcofs + (size_t)ncoeff * i0, ncoeff, G * spg, nullptr, nullptr, nullptr, adjoint, nullptr, nullptr, &o);
         h->grp_G = 0, h->grp_spg = 1;
         if (rc) return rc;
@@ -553,6 +561,73 @@ extern "C" int jq_traceobj_sweep(jq_handle* h, const double* pcof, int32_t ncoef
     return JQ_OK;
 }
 
+// jq_eval_f_g_grad for npcof control vectors and ONE set of nodes: grouped launches of G vectors x nquad nodes where the plan allows
+// (pcof_batch_per_launch), else one ensemble evaluation per vector -- the very calls jq_eval_f_g_grad makes.
+extern "C" int jq_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int32_t ncoeff, int32_t npcof, const double* nodes,
+                                      const double* weights, int32_t nquad, const double* shift, int32_t compute_adjoint, double* out2,
+                                      double* infid_grad, double* leak_grad, double* node_out)
+{
+    if (!h) return JQ_EINVAL;
+    if (!pcofs || !nodes || !weights || !out2) return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_batch: NULL pointer");
+    if (npcof < 1) return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_batch: npcof must be >= 1");
+    if (nquad < 1) return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_batch: nquad must be >= 1");
+    if (compute_adjoint && (!infid_grad || !leak_grad))
+        return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_batch: gradient outputs are required when compute_adjoint != 0");
+    if (!h->subs.empty())
+        return multi_eval_f_g_grad_batch(h, pcofs, ncoeff, npcof, nodes, weights, nquad, shift, compute_adjoint, out2, infid_grad, leak_grad, node_out);
+    int rc = check_ncoeff(h, ncoeff);      // (before anything is written)
+    if (rc) return rc;
+    const bool adjoint = compute_adjoint != 0;
+    int spg = 1, family = -1;
+    const char* why = "";
+    const int per = pcof_batch_per_launch(h, npcof, nquad, adjoint, &spg, &family, &why);
+    h->pb_mode = per > 0 ? "grouped" : "sequential", h->pb_why = why, h->pb_family = family, h->pb_per_launch = per > 0 ? per : 1, h->pb_nodes = nquad;
+    // column i of the outputs from the records of its nquad samples (the sums in node order: src/ipopt_interface.jl:58-59)
+    auto put = [&](int i, const double* res, const double* g0, const double* g1) {
+        double inf = 0.0, leak = 0.0;
+        for (int q = 0; q < nquad; ++q) {
+            const double primary = res[(size_t)q * 4 + 0], secondary = res[(size_t)q * 4 + 1];
+            inf += primary * weights[q];
+            leak += secondary * weights[q];
+            if (node_out) {      // (the record of jq_traceobj_sweep)
+                double* o4 = node_out + ((size_t)i * nquad + q) * 4;
+                o4[0] = primary + secondary, o4[1] = primary, o4[2] = secondary, o4[3] = primary;
+            }
+        }
+        out2[(size_t)2 * i] = inf, out2[(size_t)2 * i + 1] = leak;
+        if (!adjoint) return;
+        double *ig = infid_grad + (size_t)ncoeff * i, *lg = leak_grad + (size_t)ncoeff * i;
+        for (int k = 0; k < ncoeff; ++k) {
+            ig[k] = h->objFuncType != 1 ? g1[k] : g0[k];             // "infidelgrad stores the totalgrad" (src/evalobjgrad.jl:949-951)
+            lg[k] = h->objFuncType != 1 ? g0[k] - g1[k] : 0.0;
+        }
+    };
+    jq_timing tsum = {};
+    if (per <= 0) {      // every route without grouped streams: one ensemble evaluation per vector
+        for (int i = 0; i < npcof; ++i) {
+            EvalOut o;
+            if ((rc = run_eval(h, pcofs + (size_t)ncoeff * i, ncoeff, nquad, nodes, weights, shift, adjoint, nullptr, nullptr, &o))) return rc;
+            put(i, o.res.data(), o.grad0.data(), o.grad1.data());
+            batch_add_timing(tsum, h->timing);
+        }
+        h->timing = tsum;
+        return JQ_OK;
+    }
+    for (int i0 = 0; i0 < npcof; i0 += per) {      // rounds of at most `per` vectors (results do not depend on the round a vector runs in)
+        const int G = std::min(per, npcof - i0);
+        EvalOut o;
+        h->grp_G = G, h->grp_spg = spg, h->grp_Q = nquad;
+        rc = run_eval(h, pcofs + (size_t)ncoeff * i0, ncoeff, G * spg, nodes, weights, shift, adjoint, nullptr, nullptr, &o);
+        h->grp_G = 0, h->grp_spg = 1, h->grp_Q = 1;
+        if (rc) return rc;
+        for (int g = 0; g < G; ++g)
+            put(i0 + g, o.res.data() + (size_t)4 * g * spg, adjoint ? o.grad0.data() + (size_t)ncoeff * g : nullptr,
+                (adjoint && h->objFuncType != 1) ? o.grad1.data() + (size_t)ncoeff * g : nullptr);
+        batch_add_timing(tsum, h->timing);
+    }
+    h->timing = tsum;
+    return JQ_OK;
+}
 
 #include "jq_host_multi.h"      // multi-device handles: one process, N GPUs, one RCCL all-reduce
 #include "jq_host_info.h"      // options of a live handle, plan and timing introspection

@@ -5,7 +5,7 @@ signatures, so any L-BFGS driver can call them)."""
 import numpy as np
 
 from . import _lib
-from .evalobjgrad import Working_Arrays_HIP, _f64, _ptr
+from .evalobjgrad import Working_Arrays_HIP, _f64, _pcof_columns, _ptr
 from .setup_utils import tikhonov_grad, tikhonov_pen
 
 
@@ -142,6 +142,60 @@ def eval_f_g_grad(pcof, params, wa, nodes=(0.0,), weights=(1.0,), compute_adjoin
     params.lastTraceInfidelity = params.last_infidelity
     params.lastLeakIntegral = params.last_leak
     return params.last_infidelity, params.last_leak
+
+
+def eval_f_g_grad_batch(pcofs, params, wa, nodes, weights, compute_adjoint=True, shift=None, per_node=False):
+    """eval_f_g_grad for npcof control vectors over ONE set of quadrature nodes in one library call (jq_eval_f_g_grad_batch): multi-start
+    optimisation, batched line searches, finite-difference checks of the risk-neutral gradient, population optimisers, robustness curves
+    of several pulses.  Stormer-Verlet / Neumann on the row-lane and cooperative-quad kernels: launches of G vectors x nquad nodes, every
+    workgroup reading the operator stream of its own vector; everywhere else one ensemble evaluation per vector inside the call
+    (wa.plan_info()["pcof_batch"] says which).  Column i is bit-identical to eval_f_g_grad(pcofs[:, i], ...) on the same kernel variant
+    and chunk length.
+
+    pcofs: an ncoeff x npcof array (one vector per column) or a sequence of equal-length vectors.
+    Returns (infidelity[npcof], leak[npcof], infid_grad[ncoeff, npcof], leak_grad[ncoeff, npcof]) -- the gradients are zero without
+    compute_adjoint, leak_grad is 0 x npcof for objFuncType == 1 -- and with per_node=True also the array [4, nquad, npcof] of
+    (objfv, primaryobjf, secondaryobjf, traceInfidelity) per node and vector (traceobj_sweep of every vector).
+    params.last_* are left alone: they memoise ONE vector.  Shape errors raise ValueError before any library call."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("eval_f_g_grad_batch: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("eval_f_g_grad_batch: wa was allocated for a different objparams")
+    ncoeff = int(wa.nCoeff)
+    try:
+        nodes, weights = np.asarray(nodes, dtype=np.float64), np.asarray(weights, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("eval_f_g_grad_batch: nodes and weights must be vectors of numbers (%s)" % e)
+    if nodes.ndim != 1 or weights.ndim != 1 or nodes.size != weights.size:
+        raise ValueError("eval_f_g_grad_batch: nodes and weights must be vectors of the same length, not %r and %r" % (nodes.shape, weights.shape))
+    if nodes.size < 1:
+        raise ValueError("eval_f_g_grad_batch: need at least one node")
+    nodes, weights = _f64(nodes), _f64(weights)
+    sh = None
+    if shift is not None:
+        if np.shape(shift) != (int(params.Ntot),):
+            raise ValueError("eval_f_g_grad_batch: shift must have one entry per level, not shape %r" % (np.shape(shift),))
+        sh = _f64(shift)
+    P = _pcof_columns(pcofs, ncoeff)
+    n, nq = P.shape[0], nodes.size
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    out2 = np.zeros((n, 2))
+    node_out = np.zeros((n, nq, 4)) if per_node else None
+    ig = lg = None
+    if compute_adjoint:
+        ig, lg = np.zeros((n, ncoeff)), np.zeros((n, ncoeff))
+    _lib.check(L.jq_eval_f_g_grad_batch(h, _ptr(P), ncoeff, n, _ptr(nodes), _ptr(weights), nq, _ptr(sh), 1 if compute_adjoint else 0,
+                                        _ptr(out2), _ptr(ig), _ptr(lg), _ptr(node_out)), h)
+    infid_grad = np.ascontiguousarray(ig.T) if compute_adjoint else np.zeros((ncoeff, n))
+    if params.objFuncType == 1:
+        leak_grad = np.zeros((0, n))
+    else:
+        leak_grad = np.ascontiguousarray(lg.T) if compute_adjoint else np.zeros((ncoeff, n))
+    res = (out2[:, 0].copy(), out2[:, 1].copy(), infid_grad, leak_grad)
+    if per_node:
+        res += (np.ascontiguousarray(node_out.transpose(2, 1, 0)),)
+    return res
 
 
 def _stale(pcof, params):
