@@ -1,10 +1,53 @@
 // jq_host_eval.h -- part of the host side of libjuqbox_hip.so (included by juqbox_hip.hip, ONE translation unit; not a stand-alone header):
-// run_eval: a batch evaluated by its plan (plan_batch, jq_host_plan.h), chunk by chunk.
+// run_eval: one EvalRequest -- everything an evaluation is given; the handle carries none of it -- evaluated by its plan (plan_batch,
+// jq_host_plan.h), chunk by chunk, into an EvalOut; and what the entry points make of an EvalOut (out_record, out_grads, timing_add).
+struct EvalRequest {
+    const double* pcof = nullptr;   // ncoeff coefficients (grouped batch: `groups` blocks of them)
+    int ncoeff = 0;
+    int nsamples = 1;               // (grouped batch: groups x spg)
+    const double* eps = nullptr;    // [nsamples] perturbation per sample (NULL: none); grouped batch: [nodes], the same for every vector
+    const double* wgt = nullptr;    // ... weight per sample (NULL: 1)
+    const double* shift = nullptr;  // [Ntot] perturbation per level (NULL: the reference's table)
+    bool adjoint = false;
+    double *hist_r = nullptr, *hist_i = nullptr;   // DEVICE arrays of Ntot x N x (nsteps + 1) doubles: the state history of the one sample
+    double* d_packed = nullptr;     // the packed ensemble result (k_pack) is also left at this DEVICE address of h's GPU
+    // grouped batch (pcof_batch): `groups` control vectors (0: none), each padded to `spg` samples (cooperative-quad kernels with N < 4: a column
+    // quad per vector, the other columns weigh 0), of which the first `nodes` are the caller's
+    int groups = 0, spg = 1, nodes = 1;
+    bool split_part = false;        // one part of a split batch: not split again
+};
 struct EvalOut {
     std::vector<double> res;    // [nsamples][4] primary, secondary, Re s, Im s
     std::vector<double> grad0;  // forced adjoint (total gradient), weighted sum over samples
     std::vector<double> grad1;  // unforced adjoint (infidelity gradient), only objFuncType != 1
 };
+// (objfv, primaryobjf, secondaryobjf, traceInfidelity) of a sample from its record in EvalOut::res
+static void out_record(double* out4, const double* res)
+{
+    const double primary = res[0], secondary = res[1];
+    out4[0] = primary + secondary;  // objfv (src/evalobjgrad.jl:765-766)
+    out4[1] = primary;
+    out4[2] = secondary;
+    out4[3] = primary;              // traceInfidelity == 1 - |s|^2 for pFidType 2 (:792)
+}
+// the gradients the reference returns from the forced (g0) and the unforced (g1, objFuncType != 1 only) adjoint; total may be NULL
+static void out_grads(const jq_handle* h, int ncoeff, const double* g0, const double* g1, double* total, double* infid, double* leak)
+{
+    const bool two = h->objFuncType != 1;
+    for (int i = 0; i < ncoeff; ++i) {
+        if (total) total[i] = g0[i];
+        infid[i] = two ? g1[i] : g0[i];       // "infidelgrad stores the totalgrad" (src/evalobjgrad.jl:949-951)
+        leak[i] = two ? g0[i] - g1[i] : 0.0;  // :947
+    }
+}
+// the fields of a timing record that add up over the launches of one call
+static void timing_add(jq_timing& sum, const jq_timing& part)
+{
+    sum.ms_total += part.ms_total, sum.ms_propagate += part.ms_propagate, sum.ms_generate += part.ms_generate;
+    sum.ms_forward += part.ms_forward, sum.ms_backward += part.ms_backward;
+    sum.n_forward_launches += part.n_forward_launches, sum.n_backward_launches += part.n_backward_launches;
+    sum.mfma_executed += part.mfma_executed, sum.mfma_backward += part.mfma_backward, sum.svts += part.svts;
+}
 
 __global__ void k_add_to(double* __restrict__ y, const double* __restrict__ x, int n)
 {
@@ -42,27 +85,28 @@ static jq_handle* eval_target(jq_handle* h, int nsamples, bool hist)
     }
     return h;
 }
-// The batched evaluation behind every hot-path entry point.
-// d_packed != nullptr: the packed ensemble result (k_pack) is also left at this DEVICE address of h's GPU.
+// The batched evaluation behind every hot-path entry point.  It writes the handle's buffers and their capacities, the bookkeeping of the
+// three-workgroup kernels, `timing` and `err`.
 #define JQ_ERETRY_INTERNAL (-1000)      // run_eval_impl: k_backward_cq3 gave up (the handle leaves it alone for a while): evaluate again
 #define JQ_CQ3_MAX_FAULTS 6
-static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamples, const double* eps, const double* wgt,
-                         const double* shift, bool adjoint, double* hist_r, double* hist_i, EvalOut* out, double* d_packed);
-static int run_eval(jq_handle* h, const double* pcof, int ncoeff, int nsamples, const double* eps, const double* wgt,
-                    const double* shift, bool adjoint, double* hist_r, double* hist_i, EvalOut* out, double* d_packed = nullptr)
+static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out);
+static int run_eval(jq_handle* h, const EvalRequest& rq, EvalOut* out)
 {
     DevGate& gate = dev_gate(h->device);
     const bool outer = g_eval_depth++ == 0;
     if (outer) gate.enter();
-    int rc = run_eval_impl(h, pcof, ncoeff, nsamples, eps, wgt, shift, adjoint, hist_r, hist_i, out, d_packed);
-    if (rc == JQ_ERETRY_INTERNAL) rc = run_eval_impl(h, pcof, ncoeff, nsamples, eps, wgt, shift, adjoint, hist_r, hist_i, out, d_packed);
+    int rc = run_eval_impl(h, rq, out);
+    if (rc == JQ_ERETRY_INTERNAL) rc = run_eval_impl(h, rq, out);
     if (outer) gate.leave();
     --g_eval_depth;
     return rc;
 }
-static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamples, const double* eps, const double* wgt,
-                         const double* shift, bool adjoint, double* hist_r, double* hist_i, EvalOut* out, double* d_packed)
+static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
 {
+    const double *const pcof = rq.pcof, *const shift = rq.shift, *eps = rq.eps, *wgt = rq.wgt;      // (eps, wgt: a grouped batch expands them below)
+    const int ncoeff = rq.ncoeff, nsamples = rq.nsamples;
+    const bool adjoint = rq.adjoint;
+    double *const hist_r = rq.hist_r, *const hist_i = rq.hist_i, *const d_packed = rq.d_packed;
     HIPCHK(h, hipSetDevice(h->device));
     // Ensembles that do not fill their last round: the time of a batch is a staircase in its size (every workgroup runs the
     // whole sequential time loop; cnot3: 3 072 samples = one round of the three-slab quad-layout kernels 1.18 s, 3 200 samples =
@@ -74,7 +118,7 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
     const long long ncols_split = (long long)nsamples * h->N;
     const bool small_family_batch = (h->rl_npj > 0 && ncols_split <= h->rl_max_cols) ||
                                     (h->lane_np > 0 && ncols_split >= h->lane_min_cols && ncols_split <= h->lane_max_cols);
-    if (!h->in_split && h->grp_G == 0 && !small_family_batch && h->wrank == 0 && h->quad_max_slabs > 0 && h->integrator == 1 && h->solver_id == 1 && !hist_r && eps && nsamples > 1 && !h->opt.on(O_NOSPLIT)) {
+    if (!rq.split_part && rq.groups == 0 && !small_family_batch && h->wrank == 0 && h->quad_max_slabs > 0 && h->integrator == 1 && h->solver_id == 1 && !hist_r && eps && nsamples > 1 && !h->opt.on(O_NOSPLIT)) {
         // candidates: the largest number of FULL rounds of the quad-layout kernels with 1, 2 or 3 slabs per workgroup
         long long n_main = 0;
         double best = t4_plan_cost(h, nsamples) - 1e-9;
@@ -86,10 +130,11 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
             if (c < best) best = c, n_main = nm;
         }
         if (n_main > 0) {
-            h->in_split = true;
             EvalOut o2;
             const int n1 = (int)n_main, n2 = nsamples - n1;
-            int rc = run_eval(h, pcof, ncoeff, n1, eps, wgt, shift, adjoint, nullptr, nullptr, out, d_packed);
+            EvalRequest part = rq;
+            part.split_part = true, part.nsamples = n1;
+            int rc = run_eval(h, part, out);
             const jq_timing t1 = h->timing;
             const size_t npk = (size_t)2 + 2 * (size_t)ncoeff;
             if (rc == JQ_OK && d_packed) {
@@ -97,8 +142,8 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
                 if (rc == JQ_OK && hipMemcpyAsync(h->d_pk2, d_packed, npk * sizeof(double), hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
                     rc = fail(h, JQ_EHIP, "hipMemcpyAsync (packed result of the first part of a split batch)");
             }
-            if (rc == JQ_OK) rc = run_eval(h, pcof, ncoeff, n2, eps + n1, wgt ? wgt + n1 : nullptr, shift, adjoint, nullptr, nullptr, &o2, d_packed);
-            h->in_split = false;
+            part.nsamples = n2, part.eps = eps + n1, part.wgt = wgt ? wgt + n1 : nullptr;
+            if (rc == JQ_OK) rc = run_eval(h, part, &o2);
             if (rc != JQ_OK) return rc;
             if (d_packed) {
                 hipLaunchKernelGGL(k_add_to, dim3((unsigned)((npk + 255) / 256)), dim3(256), 0, h->stream, d_packed, h->d_pk2, (int)npk);
@@ -109,10 +154,7 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
             for (size_t i = 0; i < out->grad0.size() && i < o2.grad0.size(); ++i) out->grad0[i] += o2.grad0[i];
             for (size_t i = 0; i < out->grad1.size() && i < o2.grad1.size(); ++i) out->grad1[i] += o2.grad1[i];
             // timing: sums; the kernel family / size / band reported are those of the first (larger) part
-            h->timing.ms_total += t1.ms_total, h->timing.ms_propagate += t1.ms_propagate, h->timing.ms_generate += t1.ms_generate;
-            h->timing.ms_forward += t1.ms_forward, h->timing.ms_backward += t1.ms_backward;
-            h->timing.n_forward_launches += t1.n_forward_launches, h->timing.n_backward_launches += t1.n_backward_launches;
-            h->timing.mfma_executed += t1.mfma_executed, h->timing.mfma_backward += t1.mfma_backward, h->timing.svts += t1.svts;
+            timing_add(h->timing, t1);
             h->timing.kernel_family = t1.kernel_family, h->timing.kernel_size = t1.kernel_size, h->timing.kernel_band = t1.kernel_band;
             h->timing.ms_shard_min = h->timing.ms_shard_max = h->timing.ms_total;
             return JQ_OK;
@@ -122,10 +164,10 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
     if (rc) return rc;
     const int D1 = ncoeff / (2 * h->Nc * h->Nfreq);  // src/evalobjgrad.jl:608
     if (nsamples < 1) return fail(h, JQ_EINVAL, "need at least one sample");
-    // grouped batch (jq_traceobjgrad_batch, jq_eval_f_g_grad_batch): G control vectors, pcof = their G coefficient blocks, nsamples = G x spg
-    // samples: per vector the grp_Q samples of the caller (eps, wgt: [grp_Q], the same nodes for every vector; without them one sample of
-    // weight 1) and the padding that ends its last column quad
-    const int G = h->grp_G, spg = h->grp_spg, Q = h->grp_Q;
+    // grouped batch (pcof_batch): G control vectors, pcof = their G coefficient blocks, nsamples = G x spg samples: per vector the Q samples
+    // of the caller (eps, wgt: [Q], the same nodes for every vector; without them one sample of weight 1) and the padding that ends its
+    // last column quad
+    const int G = rq.groups, spg = rq.spg, Q = rq.nodes;
     if (G > 0 && (nsamples != G * spg || Q < 1 || Q > spg || hist_r || d_packed)) return fail(h, JQ_EHIP, "internal error: grouped batch with a state history or a packed result");
     const int nvec = G > 0 ? G : 1;      // (coefficient blocks, tile streams, gradients of the launch)
     // Structure embedding (try_embed): batches that would run on the dense / band MFMA families go to the embedded twin,
@@ -136,9 +178,9 @@ static int run_eval_impl(jq_handle* h, const double* pcof, int ncoeff, int nsamp
         std::vector<double> sh(e->Ntot, 0.0);
         for (int i = 0; i < h->Ntot; ++i)   // (default: the reference's 0.01 * 10^(j-2) by the USER's level index, src/ipopt_interface.jl:41-44)
             sh[h->emb_row[i]] = shift ? shift[i] : (i >= 1 ? 0.01 * pow(10.0, (double)(i - 1)) : 0.0);
-        e->grp_G = G, e->grp_spg = spg, e->grp_Q = Q;      // (a grouped batch stays one)
-        const int rc = run_eval(e, pcof, ncoeff, nsamples, eps, wgt, sh.data(), adjoint, nullptr, nullptr, out, d_packed);
-        e->grp_G = 0, e->grp_spg = 1, e->grp_Q = 1;
+        EvalRequest er = rq;      // (a grouped batch stays one; eps, wgt: the caller's)
+        er.shift = sh.data();
+        const int rc = run_eval(e, er, out);
         if (rc != JQ_OK) h->err = e->err;
         h->timing = e->timing;
         return rc;

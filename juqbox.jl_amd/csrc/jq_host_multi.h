@@ -219,6 +219,32 @@ static int multi_forall(jq_handle* h, F f)
     return JQ_OK;
 }
 
+// The device fan-out of every multi-device call: one host thread per device runs body(sub, d, lo, hi) with [lo, hi) = the device's block of
+// n items (jq_shard_bounds; empty when there are fewer items than devices) after its handle's timing has been reset (a device without a
+// shard reports none).  Returns the first failure in device order, with that device's message.
+template <typename Body>
+static int multi_for_shards(jq_handle* h, int n, Body body)
+{
+    const int nd = (int)h->subs.size();
+    std::vector<int> rcs(nd, JQ_OK);
+    std::vector<std::thread> th;
+    for (int d = 0; d < nd; ++d)
+        th.emplace_back([&, d]() {
+            jq_handle* sub = h->subs[d];
+            int lo = 0, hi = 0;
+            jq_shard_bounds(n, d, nd, &lo, &hi);
+            sub->timing = jq_timing{};
+            rcs[d] = body(sub, d, lo, hi);
+        });
+    for (auto& t : th) t.join();
+    for (int d = 0; d < nd; ++d)
+        if (rcs[d] != JQ_OK) {
+            h->err = h->subs[d]->err;
+            return rcs[d];
+        }
+    return JQ_OK;
+}
+
 // timing of a multi-device call: the slowest device's times, work summed over the devices
 static void multi_timing(jq_handle* h, double ms_allreduce)
 {
@@ -281,40 +307,28 @@ static int multi_eval_f_g_grad(jq_handle* h, const double* pcof, int ncoeff, con
     DeviceGuard guard;
     const int nd = (int)h->subs.size();
     const size_t npk = 2 + 2 * (size_t)ncoeff;
-    std::vector<int> rcs(nd, JQ_OK);
     std::vector<std::vector<double>> hostpk(h->host_reduce ? nd : 0);
-    std::vector<std::thread> th;
-    for (int d = 0; d < nd; ++d)
-        th.emplace_back([&, d]() {
-            jq_handle* sub = h->subs[d];
-            int lo = 0, hi = 0;
-            jq_shard_bounds(nquad, d, nd, &lo, &hi);
-            sub->timing = jq_timing{};
-            auto body = [&]() -> int {
-                HIPCHK(sub, hipSetDevice(sub->device));
-                if (int rc = dev_grow(sub, &sub->d_pack, &sub->cap_pack, npk)) return rc;
-                if (hi > lo) {
-                    EvalOut o;
-                    if (int rc = run_eval(sub, pcof, ncoeff, hi - lo, nodes + lo, weights + lo, shift, adjoint, nullptr, nullptr, &o, sub->d_pack)) return rc;
-                } else {
-                    HIPCHK(sub, hipMemsetAsync(sub->d_pack, 0, npk * sizeof(double), sub->stream));   // no shard: contributes zeros
-                    HIPCHK(sub, hipStreamSynchronize(sub->stream));
-                }
-                if (h->host_reduce) {      // (test mode: the packed vector goes to the host instead of into an all-reduce)
-                    hostpk[d].resize(npk);
-                    HIPCHK(sub, hipMemcpyAsync(hostpk[d].data(), sub->d_pack, npk * sizeof(double), hipMemcpyDeviceToHost, sub->stream));
-                    HIPCHK(sub, hipStreamSynchronize(sub->stream));
-                }
-                return JQ_OK;
-            };
-            rcs[d] = body();
-        });
-    for (auto& t : th) t.join();
-    for (int d = 0; d < nd; ++d)
-        if (rcs[d] != JQ_OK) {
-            h->err = h->subs[d]->err;
-            return rcs[d];
+    const int rc_eval = multi_for_shards(h, nquad, [&](jq_handle* sub, int d, int lo, int hi) -> int {
+        HIPCHK(sub, hipSetDevice(sub->device));
+        if (int rc = dev_grow(sub, &sub->d_pack, &sub->cap_pack, npk)) return rc;
+        if (hi > lo) {
+            EvalRequest rq;
+            rq.pcof = pcof, rq.ncoeff = ncoeff, rq.nsamples = hi - lo, rq.eps = nodes + lo, rq.wgt = weights + lo, rq.shift = shift, rq.adjoint = adjoint;
+            rq.d_packed = sub->d_pack;
+            EvalOut o;
+            if (int rc = run_eval(sub, rq, &o)) return rc;
+        } else {
+            HIPCHK(sub, hipMemsetAsync(sub->d_pack, 0, npk * sizeof(double), sub->stream));   // no shard: contributes zeros
+            HIPCHK(sub, hipStreamSynchronize(sub->stream));
         }
+        if (h->host_reduce) {      // (test mode: the packed vector goes to the host instead of into an all-reduce)
+            hostpk[d].resize(npk);
+            HIPCHK(sub, hipMemcpyAsync(hostpk[d].data(), sub->d_pack, npk * sizeof(double), hipMemcpyDeviceToHost, sub->stream));
+            HIPCHK(sub, hipStreamSynchronize(sub->stream));
+        }
+        return JQ_OK;
+    });
+    if (rc_eval != JQ_OK) return rc_eval;
     std::vector<double> packed(npk, 0.0);
     // Self-check of the collective (the first 8-GPU run verifies itself): on the FIRST all-reduce of a handle the devices' packed
     // vectors are also copied to the host before the collective and their sum in device order is compared with what RCCL returns
@@ -410,27 +424,13 @@ static int multi_traceobj_sweep(jq_handle* h, const double* pcof, int ncoeff, co
                                 double* out)
 {
     DeviceGuard guard;
-    const int nd = (int)h->subs.size();
-    std::vector<int> rcs(nd, JQ_OK);
-    std::vector<std::thread> th;
-    for (int d = 0; d < nd; ++d)
-        th.emplace_back([&, d]() {
-            jq_handle* sub = h->subs[d];
-            int lo = 0, hi = 0;
-            jq_shard_bounds(nquad, d, nd, &lo, &hi);
-            sub->timing = jq_timing{};
-            if (hi > lo) rcs[d] = jq_traceobj_sweep(sub, pcof, ncoeff, nodes + lo, hi - lo, shift, out + (size_t)4 * lo);
-        });
-    for (auto& t : th) t.join();
-    for (int d = 0; d < nd; ++d)
-        if (rcs[d] != JQ_OK) {
-            h->err = h->subs[d]->err;
-            return rcs[d];
-        }
+    const int rc = multi_for_shards(h, nquad, [&](jq_handle* sub, int, int lo, int hi) {
+        return hi > lo ? jq_traceobj_sweep(sub, pcof, ncoeff, nodes + lo, hi - lo, shift, out + (size_t)4 * lo) : JQ_OK;
+    });
+    if (rc != JQ_OK) return rc;
     multi_timing(h, 0.0);
     return JQ_OK;
 }
-
 
 // jq_traceobjgrad_batch on a multi-device handle: the control vectors are block-partitioned over the devices (jq_shard_bounds); every
 // output column belongs to one vector, so there is nothing to reduce
@@ -438,31 +438,18 @@ static int multi_traceobjgrad_batch(jq_handle* h, const double* pcofs, int ncoef
                                     double* infidelgrad, double* leakgrad)
 {
     DeviceGuard guard;
-    const int nd = (int)h->subs.size();
     // (a refused call writes nothing: the coefficient count is checked before any device starts)
     if (int rc = check_ncoeff(h->subs[0], ncoeff)) {
         h->err = h->subs[0]->err;
         return rc;
     }
-    std::vector<int> rcs(nd, JQ_OK);
-    std::vector<std::thread> th;
-    for (int d = 0; d < nd; ++d)
-        th.emplace_back([&, d]() {
-            jq_handle* sub = h->subs[d];
-            int lo = 0, hi = 0;
-            jq_shard_bounds(npcof, d, nd, &lo, &hi);
-            sub->timing = jq_timing{};
-            const size_t off = (size_t)ncoeff * lo;
-            if (hi > lo)
-                rcs[d] = jq_traceobjgrad_batch(sub, pcofs + off, ncoeff, hi - lo, evaladjoint, out4 + (size_t)4 * lo, totalgrad ? totalgrad + off : nullptr,
-                                               infidelgrad ? infidelgrad + off : nullptr, leakgrad ? leakgrad + off : nullptr);
-        });
-    for (auto& t : th) t.join();
-    for (int d = 0; d < nd; ++d)
-        if (rcs[d] != JQ_OK) {
-            h->err = h->subs[d]->err;
-            return rcs[d];
-        }
+    const int rc = multi_for_shards(h, npcof, [&](jq_handle* sub, int, int lo, int hi) {
+        const size_t off = (size_t)ncoeff * lo;
+        if (hi <= lo) return JQ_OK;
+        return jq_traceobjgrad_batch(sub, pcofs + off, ncoeff, hi - lo, evaladjoint, out4 + (size_t)4 * lo, totalgrad ? totalgrad + off : nullptr,
+                                     infidelgrad ? infidelgrad + off : nullptr, leakgrad ? leakgrad + off : nullptr);
+    });
+    if (rc != JQ_OK) return rc;
     multi_timing(h, 0.0);
     return JQ_OK;
 }
@@ -473,32 +460,19 @@ static int multi_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int ncoe
                                      const double* shift, int compute_adjoint, double* out2, double* infid_grad, double* leak_grad, double* node_out)
 {
     DeviceGuard guard;
-    const int nd = (int)h->subs.size();
     // (a refused call writes nothing: the coefficient count is checked before any device starts)
     if (int rc = check_ncoeff(h->subs[0], ncoeff)) {
         h->err = h->subs[0]->err;
         return rc;
     }
-    std::vector<int> rcs(nd, JQ_OK);
-    std::vector<std::thread> th;
-    for (int d = 0; d < nd; ++d)
-        th.emplace_back([&, d]() {
-            jq_handle* sub = h->subs[d];
-            int lo = 0, hi = 0;
-            jq_shard_bounds(npcof, d, nd, &lo, &hi);
-            sub->timing = jq_timing{};
-            const size_t off = (size_t)ncoeff * lo;
-            if (hi > lo)
-                rcs[d] = jq_eval_f_g_grad_batch(sub, pcofs + off, ncoeff, hi - lo, nodes, weights, nquad, shift, compute_adjoint, out2 + (size_t)2 * lo,
-                                                infid_grad ? infid_grad + off : nullptr, leak_grad ? leak_grad + off : nullptr,
-                                                node_out ? node_out + (size_t)4 * nquad * lo : nullptr);
-        });
-    for (auto& t : th) t.join();
-    for (int d = 0; d < nd; ++d)
-        if (rcs[d] != JQ_OK) {
-            h->err = h->subs[d]->err;
-            return rcs[d];
-        }
+    const int rc = multi_for_shards(h, npcof, [&](jq_handle* sub, int, int lo, int hi) {
+        const size_t off = (size_t)ncoeff * lo;
+        if (hi <= lo) return JQ_OK;
+        return jq_eval_f_g_grad_batch(sub, pcofs + off, ncoeff, hi - lo, nodes, weights, nquad, shift, compute_adjoint, out2 + (size_t)2 * lo,
+                                      infid_grad ? infid_grad + off : nullptr, leak_grad ? leak_grad + off : nullptr,
+                                      node_out ? node_out + (size_t)4 * nquad * lo : nullptr);
+    });
+    if (rc != JQ_OK) return rc;
     multi_timing(h, 0.0);
     return JQ_OK;
 }

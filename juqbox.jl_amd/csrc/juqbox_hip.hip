@@ -90,7 +90,6 @@ struct jq_handle {
     bool force_plain = false;   // full leakage weights WITH the Jacobi solver on a 4 x 4 x n plan whose kernels do not combine the two (one tile row,
                                 // or seven / eight): the handle is planned without that structure (cooperative / slab kernels that do)
     bool replanned = false;     // jq_update_hconst re-planned this handle (a later drift plans again when it violates the plan or regains a better structure)
-    bool in_split = false;      // run_eval is evaluating one part of a split batch
     double* d_pk2 = nullptr;    // packed result of the first part of a split batch
     size_t cap_pk2 = 0;
     int dq_max_quads = 0;       // no structure, 17 .. 32 levels: batches of at most this many column quads on the DENSE cooperative-quad kernels (round 6)
@@ -157,11 +156,8 @@ struct jq_handle {
     size_t cap_pcof = 0, cap_slabs = 0, cap_traces = 0, cap_grad = 0, cap_res = 0, cap_state = 0, cap_colinfo = 0, cap_wq = 0, cap_pack = 0;
     int chunk_steps = 0;
     size_t cap_stream = 0, cap_pq = 0, cap_R = 0;      // doubles of d_stream, d_pq, d_R (jq_create sizes them for one control vector; a grouped batch may grow them)
-    // jq_traceobjgrad_batch: the grouped batch run_eval is evaluating -- grp_G control vectors (0: none; pcof then holds grp_G coefficient
-    // blocks), each padded to grp_spg samples (cooperative-quad kernels with N < 4: a column quad per vector, the other columns weigh 0) --
-    // of which the first grp_Q are the caller's (jq_eval_f_g_grad_batch: the nodes of its ensemble, the same for every vector) --
-    // and what the last call did (jq_plan_info "pcof_batch")
-    int grp_G = 0, grp_spg = 1, grp_Q = 1;
+    // what the last jq_traceobjgrad_batch / jq_eval_f_g_grad_batch did (pcof_batch; jq_plan_info "pcof_batch").  An evaluation's inputs are
+    // not kept here: they travel in its EvalRequest (jq_host_eval.h)
     std::string pb_mode, pb_why;
     int pb_family = -1, pb_per_launch = 0, pb_nodes = 1;
     // Structure embedding (try_embed): a second handle of the SAME problem with its two fastest Kronecker factors zero-padded
@@ -221,7 +217,7 @@ struct DeviceGuard {
 #include "jq_host_update.h"      // the mutations scripts apply to params after construction: solver / integrator, target, drift (re-planning), leakage weights
 #include "jq_host_select.h"      // the kernel instantiations (compiled in their own translation units) and the tables that pick one
 #include "jq_host_plan.h"      // plan_batch: how a batch is routed to a kernel family, its geometry and LDS layout
-#include "jq_host_eval.h"      // run_eval: a batch evaluated by its plan, chunk by chunk
+#include "jq_host_eval.h"      // run_eval: an EvalRequest evaluated by its plan, chunk by chunk
 extern "C" int jq_traceobjgrad(jq_handle* h, const double* pcof, int32_t ncoeff, int32_t evaladjoint, double* out4,
                                double* totalgrad, double* infidelgrad, double* leakgrad)
 {
@@ -230,28 +226,13 @@ extern "C" int jq_traceobjgrad(jq_handle* h, const double* pcof, int32_t ncoeff,
     if (evaladjoint && (!totalgrad || !infidelgrad || !leakgrad))
         return fail(h, JQ_EINVAL, "jq_traceobjgrad: gradient outputs are required when evaladjoint != 0");
     JQ_ON_FIRST(h, jq_traceobjgrad(s0_, pcof, ncoeff, evaladjoint, out4, totalgrad, infidelgrad, leakgrad))
+    EvalRequest rq;
+    rq.pcof = pcof, rq.ncoeff = ncoeff, rq.adjoint = evaladjoint != 0;
     EvalOut o;
-    int rc = run_eval(h, pcof, ncoeff, 1, nullptr, nullptr, nullptr, evaladjoint != 0, nullptr, nullptr, &o);
+    int rc = run_eval(h, rq, &o);
     if (rc) return rc;
-    const double primary = o.res[0], secondary = o.res[1];
-    out4[0] = primary + secondary;  // objfv (src/evalobjgrad.jl:765-766)
-    out4[1] = primary;
-    out4[2] = secondary;
-    out4[3] = primary;              // traceInfidelity == 1 - |s|^2 for pFidType 2 (:792)
-    if (evaladjoint) {
-        for (int i = 0; i < ncoeff; ++i) totalgrad[i] = o.grad0[i];
-        if (h->objFuncType != 1) {
-            for (int i = 0; i < ncoeff; ++i) {
-                infidelgrad[i] = o.grad1[i];
-                leakgrad[i] = o.grad0[i] - o.grad1[i];  // :947
-            }
-        } else {
-            for (int i = 0; i < ncoeff; ++i) {
-                infidelgrad[i] = o.grad0[i];  // :951
-                leakgrad[i] = 0.0;
-            }
-        }
-    }
+    out_record(out4, o.res.data());
+    if (evaladjoint) out_grads(h, ncoeff, o.grad0.data(), o.grad1.data(), totalgrad, infidelgrad, leakgrad);
     return JQ_OK;
 }
 
@@ -301,15 +282,38 @@ static int pcof_batch_per_launch(jq_handle* h, int npcof, int Q, bool adjoint, i
     return 0;
 }
 
-// timing of a batch call: sums over its launches; family, size, band, variant: those of the last one
-static void batch_add_timing(jq_timing& tsum, const jq_timing& t)
+// npcof control vectors over ONE set of nquad nodes (nodes == weights == NULL, nquad == 1: the unperturbed sample) on this (single-device)
+// handle: launches of at most `per` vectors as grouped batches where the plan allows (pcof_batch_per_launch; results do not depend on the
+// round a vector runs in), else -- every route without grouped streams -- one plain evaluation per vector, the very request of the single call.
+// put(i, res, g0, g1): column i of the caller's outputs from the records of its nquad samples and its gradients (g0: adjoint only, g1:
+// objFuncType != 1 as well).  Timing: sums over the launches; every other field is the last launch's.
+template <typename Put>
+static int pcof_batch(jq_handle* h, const double* pcofs, int ncoeff, int npcof, const double* nodes, const double* weights, int nquad,
+                      const double* shift, bool adjoint, Put&& put)
 {
-    const double keep[] = {tsum.ms_total, tsum.ms_propagate, tsum.ms_generate, tsum.ms_forward, tsum.ms_backward};
-    const long long keepn[] = {tsum.n_forward_launches, tsum.n_backward_launches, tsum.mfma_executed, tsum.mfma_backward, tsum.svts};
-    tsum = t;
-    tsum.ms_total += keep[0], tsum.ms_propagate += keep[1], tsum.ms_generate += keep[2], tsum.ms_forward += keep[3], tsum.ms_backward += keep[4];
-    tsum.n_forward_launches += keepn[0], tsum.n_backward_launches += keepn[1], tsum.mfma_executed += keepn[2], tsum.mfma_backward += keepn[3], tsum.svts += keepn[4];
-    tsum.ms_shard_min = tsum.ms_shard_max = tsum.ms_total;
+    int spg = 1, family = -1;
+    const char* why = "";
+    const int per = pcof_batch_per_launch(h, npcof, nquad, adjoint, &spg, &family, &why);
+    const int step = per > 0 ? per : 1;
+    h->pb_mode = per > 0 ? "grouped" : "sequential", h->pb_why = why, h->pb_family = family, h->pb_per_launch = step, h->pb_nodes = nquad;
+    EvalRequest rq;
+    rq.ncoeff = ncoeff, rq.nsamples = nquad, rq.eps = nodes, rq.wgt = weights, rq.shift = shift, rq.adjoint = adjoint;
+    if (per > 0) rq.spg = spg, rq.nodes = nquad;
+    jq_timing tsum = {};
+    for (int i0 = 0; i0 < npcof; i0 += step) {
+        const int G = std::min(step, npcof - i0);      // (sequential: one vector, spg == 1)
+        rq.pcof = pcofs + (size_t)ncoeff * i0;
+        if (per > 0) rq.groups = G, rq.nsamples = G * spg;
+        EvalOut o;
+        if (int rc = run_eval(h, rq, &o)) return rc;
+        for (int g = 0; g < G; ++g)
+            put(i0 + g, o.res.data() + (size_t)4 * g * spg, adjoint ? o.grad0.data() + (size_t)ncoeff * g : nullptr,
+                (adjoint && h->objFuncType != 1) ? o.grad1.data() + (size_t)ncoeff * g : nullptr);
+        timing_add(h->timing, tsum);      // (this launch's record + the sums so far)
+        tsum = h->timing;
+    }
+    h->timing.ms_shard_min = h->timing.ms_shard_max = h->timing.ms_total;
+    return JQ_OK;
 }
 
 extern "C" int jq_traceobjgrad_batch(jq_handle* h, const double* pcofs, int32_t ncoeff, int32_t npcof, int32_t evaladjoint, double* out4,
@@ -321,55 +325,12 @@ extern "C" int jq_traceobjgrad_batch(jq_handle* h, const double* pcofs, int32_t 
         return fail(h, JQ_EINVAL, "jq_traceobjgrad_batch: gradient outputs are required when evaladjoint != 0");
     if (npcof < 1) return fail(h, JQ_EINVAL, "jq_traceobjgrad_batch: npcof must be >= 1");
     if (!h->subs.empty()) return multi_traceobjgrad_batch(h, pcofs, ncoeff, npcof, evaladjoint, out4, totalgrad, infidelgrad, leakgrad);
-    int rc = check_ncoeff(h, ncoeff);      // (before anything is written)
-    if (rc) return rc;
-    const bool adjoint = evaladjoint != 0;
-    int spg = 1, family = -1;
-    const char* why = "";
-    const int per = pcof_batch_per_launch(h, npcof, 1, adjoint, &spg, &family, &why);
-    h->pb_mode = per > 0 ? "grouped" : "sequential", h->pb_why = why, h->pb_family = family, h->pb_per_launch = per > 0 ? per : 1, h->pb_nodes = 1;
-    // column i of the outputs from the evaluation's record
-    auto put = [&](int i, const double* res, const double* g0, const double* g1) {
-        const double primary = res[0], secondary = res[1];
-        double* o4 = out4 + (size_t)4 * i;
-        o4[0] = primary + secondary;  // objfv (src/evalobjgrad.jl:765-766)
-        o4[1] = primary;
-        o4[2] = secondary;
-        o4[3] = primary;              // traceInfidelity == 1 - |s|^2 for pFidType 2 (:792)
-        if (!adjoint) return;
-        double *tg = totalgrad + (size_t)ncoeff * i, *ig = infidelgrad + (size_t)ncoeff * i, *lg = leakgrad + (size_t)ncoeff * i;
-        for (int k = 0; k < ncoeff; ++k) {
-            tg[k] = g0[k];
-            ig[k] = h->objFuncType != 1 ? g1[k] : g0[k];             // :951
-            lg[k] = h->objFuncType != 1 ? g0[k] - g1[k] : 0.0;      // :947
-        }
-    };
-    jq_timing tsum = {};
-    auto add_timing = [&](const jq_timing& t) { batch_add_timing(tsum, t); };
-    if (per <= 0) {      // every route without grouped streams: the single evaluation, vector by vector
-        for (int i = 0; i < npcof; ++i) {
-            EvalOut o;
-            if ((rc = run_eval(h, pcofs + (size_t)ncoeff * i, ncoeff, 1, nullptr, nullptr, nullptr, adjoint, nullptr, nullptr, &o))) return rc;
-            put(i, o.res.data(), o.grad0.data(), o.grad1.data());
-            add_timing(h->timing);
-        }
-        h->timing = tsum;
-        return JQ_OK;
-    }
-    for (int i0 = 0; i0 < npcof; i0 += per) {      // rounds of at most `per` vectors (results do not depend on the round a vector runs in)
-        const int G = std::min(per, npcof - i0);
-        EvalOut o;
-        h->grp_G = G, h->grp_spg = spg, h->grp_Q = 1;
-        rc = run_eval(h, pcofs + (size_t)ncoeff * i0, ncoeff, G * spg, nullptr, nullptr, nullptr, adjoint, nullptr, nullptr, &o);
-        h->grp_G = 0, h->grp_spg = 1;
-        if (rc) return rc;
-        for (int g = 0; g < G; ++g)
-            put(i0 + g, o.res.data() + (size_t)4 * g * spg, adjoint ? o.grad0.data() + (size_t)ncoeff * g : nullptr,
-                (adjoint && h->objFuncType != 1) ? o.grad1.data() + (size_t)ncoeff * g : nullptr);
-        add_timing(h->timing);
-    }
-    h->timing = tsum;
-    return JQ_OK;
+    if (int rc = check_ncoeff(h, ncoeff)) return rc;      // (before anything is written)
+    return pcof_batch(h, pcofs, ncoeff, npcof, nullptr, nullptr, 1, nullptr, evaladjoint != 0, [&](int i, const double* res, const double* g0, const double* g1) {
+        const size_t off = (size_t)ncoeff * i;
+        out_record(out4 + (size_t)4 * i, res);
+        if (evaladjoint) out_grads(h, ncoeff, g0, g1, totalgrad + off, infidelgrad + off, leakgrad + off);
+    });
 }
 
 extern "C" int jq_state_history(jq_handle* h, const double* pcof, int32_t ncoeff, double* ur, double* ui)
@@ -393,7 +354,9 @@ extern "C" int jq_traceobj_verbose(jq_handle* h, const double* pcof, int32_t nco
     (void)hipMemset(d_r, 0, len * sizeof(double));
     (void)hipMemset(d_i, 0, len * sizeof(double));
     EvalOut o;
-    int rc = run_eval(h, pcof, ncoeff, 1, nullptr, nullptr, nullptr, false, d_r, d_i, &o);
+    EvalRequest rq;
+    rq.pcof = pcof, rq.ncoeff = ncoeff, rq.hist_r = d_r, rq.hist_i = d_i;
+    int rc = run_eval(h, rq, &o);
     if (rc == JQ_OK) {
         if (hipMemcpy(ur, d_r, len * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(ui, d_i, len * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
@@ -403,12 +366,7 @@ extern "C" int jq_traceobj_verbose(jq_handle* h, const double* pcof, int32_t nco
             ur[i] = h->Uinit[i];
             ui[i] = -0.0;
         }
-        if (out4 && rc == JQ_OK) {   // the objective of the same forward sweep (src/evalobjgrad.jl:759-792)
-            out4[0] = o.res[0] + o.res[1];
-            out4[1] = o.res[0];
-            out4[2] = o.res[1];
-            out4[3] = o.res[0];
-        }
+        if (out4 && rc == JQ_OK) out_record(out4, o.res.data());   // the objective of the same forward sweep (src/evalobjgrad.jl:759-792)
     }
     (void)hipFree(d_r);
     (void)hipFree(d_i);
@@ -450,7 +408,9 @@ extern "C" int jq_state_populations(jq_handle* h, const double* pcof, int32_t nc
     (void)hipMemset(d_r, 0, len * sizeof(double));
     (void)hipMemset(d_i, 0, len * sizeof(double));
     EvalOut o;
-    rc = run_eval(h, pcof, ncoeff, 1, nullptr, nullptr, nullptr, false, d_r, d_i, &o);
+    EvalRequest rq;
+    rq.pcof = pcof, rq.ncoeff = ncoeff, rq.hist_r = d_r, rq.hist_i = d_i;
+    rc = run_eval(h, rq, &o);
     if (rc == JQ_OK) {
         // usaver[:,:,1] = Uinit ; usavei[:,:,1] = 0 (src/evalobjgrad.jl:679-680)
         bool ok = hipMemcpy(d_r, h->Uinit.data(), (size_t)h->Ntot * h->N * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
@@ -483,8 +443,10 @@ extern "C" int jq_eval_f_g_grad(jq_handle* h, const double* pcof, int32_t ncoeff
         return fail(h, JQ_EINVAL, "jq_eval_f_g_grad: gradient outputs are required when compute_adjoint != 0");
     if (!h->subs.empty())
         return multi_eval_f_g_grad(h, pcof, ncoeff, nodes, weights, nquad, shift, compute_adjoint != 0, out2, infid_grad, leak_grad);
+    EvalRequest rq;
+    rq.pcof = pcof, rq.ncoeff = ncoeff, rq.nsamples = nquad, rq.eps = nodes, rq.wgt = weights, rq.shift = shift, rq.adjoint = compute_adjoint != 0;
     EvalOut o;
-    int rc = run_eval(h, pcof, ncoeff, nquad, nodes, weights, shift, compute_adjoint != 0, nullptr, nullptr, &o);
+    int rc = run_eval(h, rq, &o);
     if (rc) return rc;
     double inf = 0.0, leak = 0.0;
     for (int i = 0; i < nquad; ++i) {  // src/ipopt_interface.jl:58-59
@@ -493,19 +455,7 @@ extern "C" int jq_eval_f_g_grad(jq_handle* h, const double* pcof, int32_t ncoeff
     }
     out2[0] = inf;
     out2[1] = leak;
-    if (compute_adjoint) {
-        if (h->objFuncType != 1) {
-            for (int i = 0; i < ncoeff; ++i) {
-                infid_grad[i] = o.grad1[i];
-                leak_grad[i] = o.grad0[i] - o.grad1[i];
-            }
-        } else {
-            for (int i = 0; i < ncoeff; ++i) {
-                infid_grad[i] = o.grad0[i];  // "infidelgrad stores the totalgrad" (src/evalobjgrad.jl:949-951)
-                leak_grad[i] = 0.0;
-            }
-        }
-    }
+    if (compute_adjoint) out_grads(h, ncoeff, o.grad0.data(), o.grad1.data(), nullptr, infid_grad, leak_grad);
     return JQ_OK;
 }
 
@@ -537,8 +487,11 @@ extern "C" int jq_eval_f_g_grad_dev(jq_handle* h, const double* pcof, int32_t nc
         h->timing = jq_timing{};
         return JQ_OK;
     }
+    EvalRequest rq;
+    rq.pcof = pcof, rq.ncoeff = ncoeff, rq.nsamples = nquad, rq.eps = nodes, rq.wgt = weights, rq.shift = shift, rq.adjoint = compute_adjoint != 0;
+    rq.d_packed = (double*)d_packed;
     EvalOut o;
-    return run_eval(h, pcof, ncoeff, nquad, nodes, weights, shift, compute_adjoint != 0, nullptr, nullptr, &o, (double*)d_packed);
+    return run_eval(h, rq, &o);
 }
 
 extern "C" int jq_traceobj_sweep(jq_handle* h, const double* pcof, int32_t ncoeff, const double* nodes, int32_t nquad,
@@ -548,19 +501,16 @@ extern "C" int jq_traceobj_sweep(jq_handle* h, const double* pcof, int32_t ncoef
     if (!pcof || !nodes || !out) return fail(h, JQ_EINVAL, "jq_traceobj_sweep: NULL pointer");
     if (nquad < 1) return fail(h, JQ_EINVAL, "jq_traceobj_sweep: nquad must be >= 1");
     if (!h->subs.empty()) return multi_traceobj_sweep(h, pcof, ncoeff, nodes, nquad, shift, out);
+    EvalRequest rq;
+    rq.pcof = pcof, rq.ncoeff = ncoeff, rq.nsamples = nquad, rq.eps = nodes, rq.shift = shift;
     EvalOut o;
-    int rc = run_eval(h, pcof, ncoeff, nquad, nodes, nullptr, shift, false, nullptr, nullptr, &o);
+    int rc = run_eval(h, rq, &o);
     if (rc) return rc;
-    for (int i = 0; i < nquad; ++i) {
-        const double primary = o.res[(size_t)i * 4 + 0], secondary = o.res[(size_t)i * 4 + 1];
-        out[(size_t)i * 4 + 0] = primary + secondary;
-        out[(size_t)i * 4 + 1] = primary;
-        out[(size_t)i * 4 + 2] = secondary;
-        out[(size_t)i * 4 + 3] = primary;
-    }
+    for (int i = 0; i < nquad; ++i) out_record(out + (size_t)i * 4, o.res.data() + (size_t)i * 4);
     return JQ_OK;
 }
 
+// jq_eval_f_g_grad for npcof control vectors and ONE set of nodes (pcof_batch)
 // jq_eval_f_g_grad for npcof control vectors and ONE set of nodes: grouped launches of G vectors x nquad nodes where the plan allows
 // (pcof_batch_per_launch), else one ensemble evaluation per vector -- the very calls jq_eval_f_g_grad makes.
 extern "C" int jq_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int32_t ncoeff, int32_t npcof, const double* nodes,
@@ -575,58 +525,18 @@ extern "C" int jq_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int32_t
         return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_batch: gradient outputs are required when compute_adjoint != 0");
     if (!h->subs.empty())
         return multi_eval_f_g_grad_batch(h, pcofs, ncoeff, npcof, nodes, weights, nquad, shift, compute_adjoint, out2, infid_grad, leak_grad, node_out);
-    int rc = check_ncoeff(h, ncoeff);      // (before anything is written)
-    if (rc) return rc;
-    const bool adjoint = compute_adjoint != 0;
-    int spg = 1, family = -1;
-    const char* why = "";
-    const int per = pcof_batch_per_launch(h, npcof, nquad, adjoint, &spg, &family, &why);
-    h->pb_mode = per > 0 ? "grouped" : "sequential", h->pb_why = why, h->pb_family = family, h->pb_per_launch = per > 0 ? per : 1, h->pb_nodes = nquad;
+    if (int rc = check_ncoeff(h, ncoeff)) return rc;      // (before anything is written)
     // column i of the outputs from the records of its nquad samples (the sums in node order: src/ipopt_interface.jl:58-59)
-    auto put = [&](int i, const double* res, const double* g0, const double* g1) {
+    return pcof_batch(h, pcofs, ncoeff, npcof, nodes, weights, nquad, shift, compute_adjoint != 0, [&](int i, const double* res, const double* g0, const double* g1) {
         double inf = 0.0, leak = 0.0;
         for (int q = 0; q < nquad; ++q) {
-            const double primary = res[(size_t)q * 4 + 0], secondary = res[(size_t)q * 4 + 1];
-            inf += primary * weights[q];
-            leak += secondary * weights[q];
-            if (node_out) {      // (the record of jq_traceobj_sweep)
-                double* o4 = node_out + ((size_t)i * nquad + q) * 4;
-                o4[0] = primary + secondary, o4[1] = primary, o4[2] = secondary, o4[3] = primary;
-            }
+            inf += res[(size_t)q * 4 + 0] * weights[q];
+            leak += res[(size_t)q * 4 + 1] * weights[q];
+            if (node_out) out_record(node_out + ((size_t)i * nquad + q) * 4, res + (size_t)q * 4);      // (the record of jq_traceobj_sweep)
         }
         out2[(size_t)2 * i] = inf, out2[(size_t)2 * i + 1] = leak;
-        if (!adjoint) return;
-        double *ig = infid_grad + (size_t)ncoeff * i, *lg = leak_grad + (size_t)ncoeff * i;
-        for (int k = 0; k < ncoeff; ++k) {
-            ig[k] = h->objFuncType != 1 ? g1[k] : g0[k];             // "infidelgrad stores the totalgrad" (src/evalobjgrad.jl:949-951)
-            lg[k] = h->objFuncType != 1 ? g0[k] - g1[k] : 0.0;
-        }
-    };
-    jq_timing tsum = {};
-    if (per <= 0) {      // every route without grouped streams: one ensemble evaluation per vector
-        for (int i = 0; i < npcof; ++i) {
-            EvalOut o;
-            if ((rc = run_eval(h, pcofs + (size_t)ncoeff * i, ncoeff, nquad, nodes, weights, shift, adjoint, nullptr, nullptr, &o))) return rc;
-            put(i, o.res.data(), o.grad0.data(), o.grad1.data());
-            batch_add_timing(tsum, h->timing);
-        }
-        h->timing = tsum;
-        return JQ_OK;
-    }
-    for (int i0 = 0; i0 < npcof; i0 += per) {      // rounds of at most `per` vectors (results do not depend on the round a vector runs in)
-        const int G = std::min(per, npcof - i0);
-        EvalOut o;
-        h->grp_G = G, h->grp_spg = spg, h->grp_Q = nquad;
-        rc = run_eval(h, pcofs + (size_t)ncoeff * i0, ncoeff, G * spg, nodes, weights, shift, adjoint, nullptr, nullptr, &o);
-        h->grp_G = 0, h->grp_spg = 1, h->grp_Q = 1;
-        if (rc) return rc;
-        for (int g = 0; g < G; ++g)
-            put(i0 + g, o.res.data() + (size_t)4 * g * spg, adjoint ? o.grad0.data() + (size_t)ncoeff * g : nullptr,
-                (adjoint && h->objFuncType != 1) ? o.grad1.data() + (size_t)ncoeff * g : nullptr);
-        batch_add_timing(tsum, h->timing);
-    }
-    h->timing = tsum;
-    return JQ_OK;
+        if (compute_adjoint) out_grads(h, ncoeff, g0, g1, nullptr, infid_grad + (size_t)ncoeff * i, leak_grad + (size_t)ncoeff * i);
+    });
 }
 
 #include "jq_host_multi.h"      // multi-device handles: one process, N GPUs, one RCCL all-reduce

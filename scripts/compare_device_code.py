@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Is the device code of two builds of the library the same?  For refactors of the kernel headers that must not change a kernel.
 
-usage: compare_device_code.py <csrc before> <csrc after> [object directory ...]      (default: build build_df)
+usage: compare_device_code.py <csrc before> <csrc after> [object directory | object.o ...]      (default: build build_df)
 
 Both trees have been built (`make` and `make check-forms-lib` in juqbox.jl_amd/csrc).  For every <tag>.flags of an object directory
 the gfx950 code object is taken out of <tag>.o of either tree and three things are compared:
@@ -9,7 +9,8 @@ the gfx950 code object is taken out of <tag>.o of either tree and three things a
   rodata  llvm-objdump -s -j .rodata (the kernel descriptors: registers, scratch, LDS, ...)
   usage   the per-kernel remarks of <tag>.log (registers, spills, scratch, LDS, occupancy) without their source locations
 plus the flags themselves, and per object directory manifest.json (keys that hold a hash aside).  The whole ELF is no use: two compiles
-of one source differ in a per-compile identifier of the symbol tables.  Prints one row per object -- the SHA-256 prefix over text and
+of one source differ in a per-compile identifier of the symbol tables.  An argument that ends in .o names a single object of both trees
+that has no .flags / .log (build/host.o: the auxiliary kernels): text and rodata only.  Prints one row per object -- the SHA-256 prefix over text and
 rodata before and after -- and exits 1 unless everything is equal."""
 import hashlib
 import json
@@ -63,6 +64,12 @@ def main():
     print("# object  sha256(text + rodata) before  after  verdict")
     with tempfile.TemporaryDirectory() as tmp:
         for d in dirs:
+            if d.endswith(".o"):
+                dumps = [device_dumps(os.path.join(t, d), tmp) for t in (before, after)]
+                diff = [what for i, what in enumerate(("text", "rodata")) if dumps[0][i] != dumps[1][i]]
+                print("%s  %s  %s  %s" % (d, sha(*dumps[0]), sha(*dumps[1]), "DIFFERS: " + " ".join(diff) if diff else "same"))
+                bad += bool(diff)
+                continue
             tags = sorted(f[:-6] for f in os.listdir(os.path.join(before, d)) if f.endswith(".flags"))
             tags_after = sorted(f[:-6] for f in os.listdir(os.path.join(after, d)) if f.endswith(".flags"))
             if tags != tags_after:

@@ -18,6 +18,7 @@ import sys
 import numpy as np
 import pytest
 from conftest import ROOT, case_inputs
+from kronecker_problem import random_kronecker_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -333,38 +334,9 @@ def test_random_kronecker_problems_take_the_embedded_kernels(hip, dims, N, nq):
     go to the embedded twin by default (family 6 or 0 with band 7 / 8), results against the oracle; with JQ_EMBED=0 the same
     problem runs on the generic kernels and must agree."""
     jq = hip
-    d1, d2, d3 = dims
-    Ntot = d1 * d2 * d3
-    rng = np.random.default_rng(77 + Ntot)
-    def op(anti, parts):
-        a = np.zeros((Ntot, Ntot))
-        if parts & 1:       # fastest factor: dense d1 x d1 blocks (different per block)
-            for b in range(0, Ntot, d1):
-                blk = rng.standard_normal((d1, d1))
-                a[b:b + d1, b:b + d1] = blk - blk.T if anti else blk + blk.T
-        for stride, bit, period in ((d1, 2, d1 * d2), (d1 * d2, 4, Ntot)):
-            if parts & bit:
-                for i in range(Ntot - stride):
-                    if i // period != (i + stride) // period:
-                        continue
-                    a[i, i + stride] = rng.standard_normal()
-                    a[i + stride, i] = -a[i, i + stride] if anti else a[i, i + stride]
-        return a
-    Nc = 3
-    Hs = [op(False, (7, 2, 4)[q]) for q in range(Nc)]
-    Ha = [op(True, (7, 2, 4)[q]) for q in range(Nc)]
-    H0 = op(False, 7)
-    scale = 2.0 / max(1.0, max(np.abs(np.linalg.eigvalsh(h)).max() for h in Hs + [H0]))
-    nsteps, m = 14, 3
-    U0 = np.linalg.qr(rng.standard_normal((Ntot, N)))[0]
-    Ut = np.linalg.qr(rng.standard_normal((Ntot, N)) + 1j * rng.standard_normal((Ntot, N)))[0]
-    p = jq.objparams([N], [Ntot - N], 1.3, nsteps, Uinit=U0, Utarget=Ut, Cfreq=rng.standard_normal((Nc, 2)), Rfreq=np.zeros(Nc),
-                     Hconst=H0 * scale, Hsym_ops=[h * scale for h in Hs], Hanti_ops=[h * scale for h in Ha], objFuncType=3,
-                     linear_solver=jq.lsolver_object(max_iter=m))
-    p.wmat_real = rng.random(Ntot) * (np.arange(Ntot) >= N)
-    pcof = 0.3 * rng.standard_normal(2 * Nc * 2 * 4)
+    p, pcof, rng = random_kronecker_problem(jq, dims, N)
     nodes, weights = 0.05 * rng.standard_normal(nq), rng.random(nq)
-    shift = 0.05 * rng.standard_normal(Ntot)
+    shift = 0.05 * rng.standard_normal(p.Ntot)
     out = {}
     for mode in ("2", "0"):
         # (a space that has the structure natively, 2 x 2 x 3, must use it too: no lane kernels)
