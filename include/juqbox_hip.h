@@ -43,7 +43,8 @@ extern "C" {
  *     the rank of a full weight matrix; full leakage weights with the Jacobi solver;
  * 6 = continuation adjoints: jq_update_dvds, jq_set_sv_type, jq_get_sv_type (params.dVds_r / dVds_i / sv_type); later, with no
  *     change of a layout or of an existing entry point: jq_s_uniform (host-only structure test), jq_traceobjgrad_batch (many control
- *     vectors of one problem in one call), jq_eval_f_g_grad_batch (many control vectors x the nodes of one ensemble in one call). */
+ *     vectors of one problem in one call), jq_eval_f_g_grad_batch (many control vectors x the nodes of one ensemble in one call),
+ *     jq_traceobjgrad_drifts / jq_eval_f_g_grad_drifts (one control vector over an ensemble of arbitrary drift Hamiltonians in one call). */
 #define JQ_ABI_VERSION 6
 
 #define JQ_MAX_CONTROLS 16 /* control Hamiltonians the fast kernels hold in registers; more: cooperative kernels (no limit)    */
@@ -396,6 +397,47 @@ int jq_eval_f_g_grad(jq_handle *h, const double *pcof, int32_t ncoeff, const dou
 int jq_eval_f_g_grad_batch(jq_handle *h, const double *pcofs, int32_t ncoeff, int32_t npcof, const double *nodes,
                            const double *weights, int32_t nquad, const double *shift, int32_t compute_adjoint, double *out2,
                            double *infid_grad, double *leak_grad, double *node_out);
+
+/*
+ * Ensembles over ARBITRARY drift Hamiltonians: ndrift evaluations traceobjgrad(pcof, params with Hconst = Hconsts[:, :, i], wa, false,
+ * evaladjoint) of ONE control vector -- what the reference's scripts get by mutating params.Hconst in a loop (examples/Risk_Neutral/
+ * run_all.jl:13-15): two uncertain transition frequencies on a tensor quadrature grid, an uncertain anharmonicity or cross-Kerr term, an
+ * uncertain coupling strength (off-diagonal entries).  jq_eval_f_g_grad serves only Hconst + ep * diag(shift).
+ * Hconsts: [Ntot x Ntot x ndrift] column-major, every member under the contract of jq_update_hconst's argument.  out4: [4 x ndrift],
+ * totalgrad / infidelgrad / leakgrad: [ncoeff x ndrift] (laid out like jq_traceobjgrad_batch's; conventions per column exactly those of
+ * jq_traceobjgrad; NULL allowed when evaladjoint == 0).
+ * Column i equals what the handle returns after jq_update_hconst(h, Hconsts[:, :, i]) followed by jq_traceobjgrad(h, pcof, ...) under the
+ * handle's current settings (sv_type, weights, solver, target, objFuncType) -- bit for bit on the same kernel variant and chunk length.
+ * After the call the handle's own drift is what it was: a jq_traceobjgrad before the call and one after it return the same bits (the
+ * re-plan below excepted).
+ * Grouped ensembles: Stormer-Verlet with the Neumann solver on the row-lane (family 3) and cooperative-quad kernels (family 8, its dense
+ * policy included) -- the members SHARE launches: every workgroup belongs to one member and reads the operator tile stream generated
+ * from that member's drift (the time-loop kernels are those of jq_traceobjgrad_batch).  At most one member's workgroups per compute unit
+ * go into a launch (option pcof_batch_max: fewer), larger ensembles run in rounds.  Everything else -- the implicit-midpoint integrator,
+ * the Jacobi solver, the lane, quad-layout, slab, cooperative and run-time-size kernels, handles whose options select one of those,
+ * ndrift == 1 -- makes member after member the handle's drift inside the call and runs the single evaluation: correct and bit-identical
+ * to the loop a caller writes, but no faster.  jq_plan_info reports what the last call did ("drift_batch": mode, family,
+ * members_per_launch, reason).
+ * Planning: before anything runs every member is tested against the structure the handle was planned for.  When a member lies outside
+ * it, the handle is re-planned ONCE for the union of the members' and its own nonzero pattern (as jq_update_hconst re-plans for such a
+ * drift: same pointer, settings kept; slower kernels may result, never an error) and its own drift is restored; later evaluations of
+ * the handle run on that more general plan until a jq_update_hconst plans back.  A member that breaks the structure of the handle's
+ * embedded twin makes the handle work on without the twin, as jq_update_hconst does.
+ * Errors: JQ_EINVAL for NULL required pointers and ndrift < 1, the single call's codes for the coefficient count (JQ_EINVAL / JQ_EDIM);
+ * a refused call writes nothing.  Multi-device handles shard the MEMBERS (jq_shard_bounds).
+ */
+int jq_traceobjgrad_drifts(jq_handle *h, const double *pcof, int32_t ncoeff, const double *Hconsts, int32_t ndrift,
+                           int32_t evaladjoint, double *out4, double *totalgrad, double *infidelgrad, double *leakgrad);
+/*
+ * The weighted sums eval_f_g_grad! forms (src/ipopt_interface.jl:48-59), over the members of a drift ensemble instead of over eps-nodes:
+ * out2 = { sum_i w_i infidelity_i, sum_i w_i leak_i }, infid_grad / leak_grad: [ncoeff] the weighted sums of the members' infidelgrad /
+ * leakgrad (leak_grad zero-filled for objFuncType == 1; may be NULL when compute_adjoint == 0), formed on the host in member order.
+ * member_out: [4 x ndrift] or NULL -- the per-member record, bit-identical to out4 of jq_traceobjgrad_drifts.  weights: [ndrift].
+ * Routing, planning, errors and multi-device behaviour: those of jq_traceobjgrad_drifts.
+ */
+int jq_eval_f_g_grad_drifts(jq_handle *h, const double *pcof, int32_t ncoeff, const double *Hconsts, const double *weights,
+                            int32_t ndrift, int32_t compute_adjoint, double *out2, double *infid_grad, double *leak_grad,
+                            double *member_out);
 
 /*
  * The same evaluation with the result left ON THE DEVICE for a caller that runs its own collective (one process per GPU:

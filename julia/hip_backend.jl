@@ -366,6 +366,55 @@ function eval_f_g_grad_batch(pcofs::Matrix{Float64}, params::objparams, wa::Abst
     return per_node ? (res..., node_out) : res
 end
 
+# ONE control vector over an ensemble of arbitrary drift Hamiltonians in one call (jq_traceobjgrad_drifts): column i of every result is
+# what traceobjgrad(pcof, params, wa, false, evaladjoint) returns with params.Hconst = Hconsts[:, :, i] -- the loop of
+# examples/Risk_Neutral/run_all.jl:13-15.  On the latency kernels (row-lane, cooperative quad; Stormer-Verlet, Neumann) the members share
+# launches, elsewhere the handle's drift is swapped per member inside the call; params.Hconst and the handle's drift stay what they were.
+# Returns what traceobjgrad_batch returns, one column per member.
+function traceobjgrad_drifts(pcof::Vector{Float64}, params::objparams, wa::AbstractWorkingArraysHIP, Hconsts::Array{Float64,3},
+                             evaladjoint::Bool = true)
+    Ntot = params.N + params.Nguard
+    n = size(Hconsts, 3)
+    n >= 1 || throw(ArgumentError("traceobjgrad_drifts: need at least one member drift"))
+    (size(Hconsts, 1) == Ntot && size(Hconsts, 2) == Ntot) || throw(ArgumentError("traceobjgrad_drifts: members must be Ntot x Ntot"))
+    sync!(wa, params)
+    ncoeff = length(pcof)
+    out4 = zeros(4, n)
+    tg = zeros(ncoeff, evaladjoint ? n : 0); ig = similar(tg); lg = similar(tg)
+    jqcheck(wa, ccall((:jq_traceobjgrad_drifts, libjq), Cint,
+                      (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                      wa.handle, pcof, ncoeff, Hconsts, n, evaladjoint ? 1 : 0, out4,
+                      evaladjoint ? pointer(tg) : C_NULL, evaladjoint ? pointer(ig) : C_NULL, evaladjoint ? pointer(lg) : C_NULL))
+    evaladjoint || return out4[1, :], out4[2, :], out4[3, :]
+    return out4[1, :], tg, out4[2, :], out4[3, :], out4[4, :], ig, (params.objFuncType == 1 ? zeros(0, n) : lg)
+end
+
+# eval_f_g_grad! over the members of a drift ensemble instead of over eps-nodes (jq_eval_f_g_grad_drifts): the weighted sums land in
+# params.last_* exactly as eval_f_g_grad! leaves them; per_member = true also returns the 4 x ndrift array of the members' records.
+function eval_f_g_grad_drifts!(pcof::Vector{Float64}, params::objparams, wa::AbstractWorkingArraysHIP, Hconsts::Array{Float64,3},
+                               weights::AbstractArray, compute_adjoint::Bool = true; per_member::Bool = false)
+    Ntot = params.N + params.Nguard
+    nm = size(Hconsts, 3)
+    wt = collect(Float64, weights)
+    nm >= 1 || throw(ArgumentError("eval_f_g_grad_drifts!: need at least one member drift"))
+    (size(Hconsts, 1) == Ntot && size(Hconsts, 2) == Ntot) || throw(ArgumentError("eval_f_g_grad_drifts!: members must be Ntot x Ntot"))
+    length(wt) == nm || throw(ArgumentError("eval_f_g_grad_drifts!: need one weight per member drift"))
+    sync!(wa, params)
+    n = length(pcof)
+    out2 = zeros(2); ig = zeros(n); lg = zeros(n)
+    member_out = zeros(4, per_member ? nm : 0)
+    jqcheck(wa, ccall((:jq_eval_f_g_grad_drifts, libjq), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        wa.handle, pcof, n, Hconsts, wt, nm, compute_adjoint ? 1 : 0, out2, ig, lg, per_member ? pointer(member_out) : C_NULL))
+    params.last_pcof .= pcof
+    params.last_infidelity, params.last_leak = out2
+    params.last_infidelity_grad .= compute_adjoint ? ig : 0.0
+    length(params.last_leak_grad) > 0 && (params.last_leak_grad .= compute_adjoint ? lg : 0.0)
+    params.lastTraceInfidelity = params.last_infidelity
+    params.lastLeakIntegral = params.last_leak
+    return per_member ? member_out : nothing
+end
+
 # One process per GPU (MPI.jl): each rank evaluates its shard and leaves the packed sums on its device; the caller
 # all-reduces `d_packed` (2 + 2 nCoeff doubles on the GPU, e.g. a ROCArray) over the ranks.
 function shard_bounds(nquad::Integer, rank::Integer, world::Integer)

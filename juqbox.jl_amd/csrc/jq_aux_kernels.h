@@ -97,15 +97,19 @@ __global__ void k_ctrl(SplineArgs s, const double* tt, int n0, int ntp, double h
 // (jq_kernels.h): with c = h/2, K -> +c K at the half time points (odd j), -c K at the integer
 // time points (even j); S -> c S.   grid = (mat_elems/256, ntp, control vectors)
 // (grouped batch: vector g = blockIdx.z reads the pq block g and writes its own stream, gstride doubles behind the one before)
-__global__ void k_stream(const double* __restrict__ himg, const double* __restrict__ pq, int Ncoupled, long long mat_elems,
-                         double c, double* __restrict__ stream, long long gstride)
+// h0: the drift image (image 0) of group 0, group g's h0_gstride doubles behind it -- himg and 0 for every launch whose groups share the
+// handle's drift (the launch it always was); a drift ensemble (jq_traceobjgrad_drifts) passes its members' images [groups][mat_elems].
+// The control images 1 .. 2 Ncoupled are read from himg in either case.
+__global__ void k_stream(const double* __restrict__ himg, const double* __restrict__ h0, long long h0_gstride, const double* __restrict__ pq,
+                         int Ncoupled, long long mat_elems, double c, double* __restrict__ stream, long long gstride)
 {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int j = blockIdx.y;
     if (e >= mat_elems) return;
     stream += (size_t)blockIdx.z * (size_t)gstride;
+    h0 += (size_t)blockIdx.z * (size_t)h0_gstride;
     const double* ctl = pq + ((size_t)blockIdx.z * gridDim.y + j) * 2 * Ncoupled;
-    double K = himg[e], S = 0.0;
+    double K = h0[e], S = 0.0;
     for (int q = 0; q < Ncoupled; ++q) {
         K += ctl[2 * q] * himg[(size_t)(1 + q) * mat_elems + e];
         S += ctl[2 * q + 1] * himg[(size_t)(1 + Ncoupled + q) * mat_elems + e];

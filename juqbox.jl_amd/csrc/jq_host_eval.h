@@ -14,6 +14,9 @@ struct EvalRequest {
     // grouped batch (pcof_batch): `groups` control vectors (0: none), each padded to `spg` samples (cooperative-quad kernels with N < 4: a column
     // quad per vector, the other columns weigh 0), of which the first `nodes` are the caller's
     int groups = 0, spg = 1, nodes = 1;
+    // drift ensemble (jq_traceobjgrad_drifts): HOST array [Ntot x Ntot x groups] of member drifts (NULL: none), a grouped batch whose groups
+    // share ONE control vector (pcof: ncoeff coefficients) and differ in image 0 of their tile stream
+    const double* drifts = nullptr;
     bool split_part = false;        // one part of a split batch: not split again
 };
 struct EvalOut {
@@ -169,6 +172,7 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     // last column quad
     const int G = rq.groups, spg = rq.spg, Q = rq.nodes;
     if (G > 0 && (nsamples != G * spg || Q < 1 || Q > spg || hist_r || d_packed)) return fail(h, JQ_EHIP, "internal error: grouped batch with a state history or a packed result");
+    if (rq.drifts && G == 0) return fail(h, JQ_EHIP, "internal error: member drifts outside a grouped batch");
     const int nvec = G > 0 ? G : 1;      // (coefficient blocks, tile streams, gradients of the launch)
     // Structure embedding (try_embed): batches that would run on the dense / band MFMA families go to the embedded twin,
     // whose operators have the JQ_BW_T4 structure (quad-layout / JQ_BW_T4 slab kernels).  State histories stay here (their
@@ -180,6 +184,13 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
             sh[h->emb_row[i]] = shift ? shift[i] : (i >= 1 ? 0.01 * pow(10.0, (double)(i - 1)) : 0.0);
         EvalRequest er = rq;      // (a grouped batch stays one; eps, wgt: the caller's)
         er.shift = sh.data();
+        std::vector<double> ed;      // (member drifts in the twin's rows, like jq_update_hconst embeds the handle's)
+        if (rq.drifts) {
+            const size_t nn = (size_t)h->Ntot * h->Ntot, ne = (size_t)e->Ntot * e->Ntot;
+            ed.assign((size_t)G * ne, 0.0);
+            for (int g = 0; g < G; ++g) embed_matrix(rq.drifts + (size_t)g * nn, h->Ntot, h->emb_row, e->Ntot, ed.data() + (size_t)g * ne);
+            er.drifts = ed.data();
+        }
         const int rc = run_eval(e, er, out);
         if (rc != JQ_OK) h->err = e->err;
         h->timing = e->timing;
@@ -241,7 +252,27 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
 
     // ---- inputs --------------------------------------------------------------------------------
     hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(h->d_pcof, pcof, (size_t)nvec * ncoeff * sizeof(double), hipMemcpyHostToDevice, s));
+    std::vector<double> gpcof, dimg;
+    if (rq.drifts) {
+        // one control vector for every group: its block replicated (k_ctrl, k_gradacc stay the launches of a control-vector batch), and the
+        // members' drift images in the planned family's layout -- the builders and the bits of upload_operators' image 0
+        for (int g = 0; g < G; ++g) gpcof.insert(gpcof.end(), pcof, pcof + ncoeff);
+        const size_t nn = (size_t)h->Ntot * h->Ntot;
+        dimg.assign((size_t)G * (size_t)p.stride, 0.0);
+        for (int g = 0; g < G; ++g) {
+            const double* M = rq.drifts + (size_t)g * nn;
+            double* img = dimg.data() + (size_t)g * (size_t)p.stride;
+            if (p.dense) dq_image(M, h->Ntot, img);
+            else if (p.family == KF_ROWLANE) rowlane_image(M, h->Ntot, h->rl_npj, img);
+            else if (p.family == KF_CQ && !h->big) tile_image(M, h->Ntot, h->NT, h->BW, img);
+            else return fail(h, JQ_EHIP, "internal error: drift ensemble on a kernel family without grouped streams");
+        }
+        if ((rc = dev_grow(h, &h->d_drift, &h->cap_drift, dimg.size()))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->d_drift, dimg.data(), dimg.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    const double* const h0img = rq.drifts ? h->d_drift : p.himg;      // image 0 of group 0 and the stride to the next group's
+    const long long h0_gstride = rq.drifts ? p.stride : 0;
+    HIPCHK(h, hipMemcpyAsync(h->d_pcof, rq.drifts ? gpcof.data() : pcof, (size_t)nvec * ncoeff * sizeof(double), hipMemcpyHostToDevice, s));
     bool use_shift = false;
     std::vector<double> colinfo(p.colinfo_doubles, 0.0);
     if (p.layout != SL_SLABS) {   // [eps per column slot | weight per column slot]  (lane kernels: cpw = 4, one slot per column)
@@ -328,8 +359,8 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
         const int nc = std::min(p.cs, h->nsteps - n0);
         const int ntp = 2 * nc + 1;
         hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, sp, h->d_tf, n0, ntp, dt, h->d_pq);
-        hipLaunchKernelGGL(k_stream, dim3((unsigned)((p.stride + 255) / 256), ntp, nvec), dim3(256), 0, s, p.himg, h->d_pq,
-                           h->Nc, p.stride, 0.5 * dt, h->d_stream, (long long)gstride);
+        hipLaunchKernelGGL(k_stream, dim3((unsigned)((p.stride + 255) / 256), ntp, nvec), dim3(256), 0, s, p.himg, h0img, h0_gstride,
+                           h->d_pq, h->Nc, p.stride, 0.5 * dt, h->d_stream, (long long)gstride);
         a.nsteps_chunk = nc; a.step0 = n0; a.first_chunk = (n0 == 0); a.h = dt; a.forced = 1;
         a.hist_r = hist_r; a.hist_i = hist_i;
         a.wlr_lds = p.fwd.wlr;
@@ -396,8 +427,8 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
                 const int nc = std::min(p.cs, h->nsteps - n0);
                 const int ntp = 2 * nc + 1;
                 hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, sp, h->d_tb, n0, ntp, -dt, h->d_pq);
-                hipLaunchKernelGGL(k_stream, dim3((unsigned)((p.stride + 255) / 256), ntp, nvec), dim3(256), 0, s, p.himg,
-                                   h->d_pq, h->Nc, p.stride, -0.5 * dt, h->d_stream, (long long)gstride);
+                hipLaunchKernelGGL(k_stream, dim3((unsigned)((p.stride + 255) / 256), ntp, nvec), dim3(256), 0, s, p.himg, h0img,
+                                   h0_gstride, h->d_pq, h->Nc, p.stride, -0.5 * dt, h->d_stream, (long long)gstride);
                 a.nsteps_chunk = nc; a.step0 = n0; a.first_chunk = (n0 == 0); a.h = -dt; a.forced = (pass == 0);
                 a.hist_r = nullptr; a.hist_i = nullptr;
                 a.wlr_lds = p.bwd.wlr;

@@ -154,6 +154,10 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
     // the tile stream of its own) or "sequential" (the single evaluation per vector), and why
     kv("pcof_batch", std::string("{\"mode\": \"") + (h->pb_mode.empty() ? "none yet" : h->pb_mode) + "\", \"family\": " + num(h->pb_family) + ", \"vectors_per_launch\": " + num(h->pb_per_launch) +
                          ", \"nodes_per_vector\": " + num(h->pb_nodes) + ", \"reason\": \"" + h->pb_why + "\"}");
+    // jq_traceobjgrad_drifts / jq_eval_f_g_grad_drifts: what the last call did with its members -- "grouped" (every workgroup reads the tile
+    // stream of its own member's drift) or "sequential" (the handle's operator images swapped per member for the single evaluation), and why
+    kv("drift_batch", std::string("{\"mode\": \"") + (h->db_mode.empty() ? "none yet" : h->db_mode) + "\", \"family\": " + num(h->db_family) + ", \"members_per_launch\": " + num(h->db_per_launch) +
+                          ", \"reason\": \"" + h->db_why + "\"}");
     o += "}";
     if (buflen > 0) {
         const size_t n = std::min(o.size(), (size_t)buflen - 1);

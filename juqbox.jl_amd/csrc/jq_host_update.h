@@ -10,6 +10,8 @@ static int multi_traceobjgrad_batch(jq_handle* h, const double* pcofs, int ncoef
                                     double* infidelgrad, double* leakgrad);
 static int multi_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int ncoeff, int npcof, const double* nodes, const double* weights, int nquad,
                                      const double* shift, int compute_adjoint, double* out2, double* infid_grad, double* leak_grad, double* node_out);
+static int multi_traceobjgrad_drifts(jq_handle* h, const double* pcof, int ncoeff, const double* Hconsts, int ndrift, int evaladjoint, double* out4,
+                                     double* totalgrad, double* infidelgrad, double* leakgrad);
 // a single evaluation cannot be sharded: multi-device handles run it on their first device
 #define JQ_ON_FIRST(h, call)                         \
     if (!(h)->subs.empty()) {                        \
@@ -242,6 +244,29 @@ static int replan(jq_handle* h, const double* Hconst)
     return JQ_OK;
 }
 
+// Does this drift fit the structure the handle's kernels, operator images and LDS plan were chosen for?  (jq_update_hconst, and every member
+// of a drift ensemble before anything runs: drifts_prepare.)  A property of the nonzero pattern alone, and a pattern inside a fitting one fits.
+static bool hconst_fits_plan(const jq_handle* h, const double* Hconst)
+{
+    return (h->BW == JQ_BW_T4) ? t4_structure(Hconst, h->Ntot)
+           : (h->BW == JQ_BW_OD) ? offdiag_blocks_diagonal(Hconst, h->Ntot) : (h->huge || block_band(Hconst, h->Ntot) <= (h->big ? h->BWc : h->BW));
+}
+// A drift that fits the plan becomes the handle's: host copy, the embedded twin's (a drift that breaks the twin's structure: the handle works
+// on without the twin), operator images of every family.  Hconst must not alias h->Hconst.
+static int apply_hconst(jq_handle* h, const double* Hconst)
+{
+    h->Hconst.assign(Hconst, Hconst + (size_t)h->Ntot * h->Ntot);
+    if (h->emb) {
+        jq_handle* e = h->emb;
+        embed_matrix(Hconst, h->Ntot, h->emb_row, e->Ntot, e->Hconst.data());
+        if (!t4_structure(e->Hconst.data(), e->Ntot) || upload_operators(e) != JQ_OK) {   // the new drift breaks the structure:
+            jq_destroy(e);                                                                // work without the embedded twin
+            h->emb = nullptr;
+        }
+    }
+    return upload_operators(h);
+}
+
 extern "C" int jq_update_hconst(jq_handle* h, const double* Hconst)
 {
     if (!h) return JQ_EINVAL;
@@ -255,8 +280,7 @@ extern "C" int jq_update_hconst(jq_handle* h, const double* Hconst)
     //  iteration, like eval_f_g_grad!'s loop, must not pay a full re-creation per call; it plans again only when a drift violates
     //  the current structure, or when the drift has regained a structure that admits a strictly better kernel family than the
     //  current plan's: 4 x 4 x n when the plan is not JQ_BW_T4, diagonal off-diagonal blocks when it is a plain band.)
-    const bool fits = (h->BW == JQ_BW_T4) ? t4_structure(Hconst, h->Ntot)
-                      : (h->BW == JQ_BW_OD) ? offdiag_blocks_diagonal(Hconst, h->Ntot) : (h->huge || block_band(Hconst, h->Ntot) <= (h->big ? h->BWc : h->BW));
+    const bool fits = hconst_fits_plan(h, Hconst);
     bool better = false;
     if (fits && h->replanned && h->BW != JQ_BW_T4 && !h->huge) {
         const size_t nn = (size_t)h->Ntot * h->Ntot;
@@ -279,16 +303,43 @@ extern "C" int jq_update_hconst(jq_handle* h, const double* Hconst)
         better = t4 || od || narrower;
     }
     if (!fits || better) return replan(h, Hconst);
-    h->Hconst.assign(Hconst, Hconst + (size_t)h->Ntot * h->Ntot);
+    if (Hconst == h->Hconst.data()) return upload_operators(h);
+    return apply_hconst(h, Hconst);
+}
+
+// Before a drift ensemble runs (jq_traceobjgrad_drifts): every member is tested against the plan.  When one lies outside it the handle is
+// re-planned ONCE, for the union of the members' and its own nonzero pattern (replan: what jq_update_hconst does with such a drift), and its
+// own drift is put back -- slower kernels may result, never an error; a later jq_update_hconst may plan back.  Members that break the
+// structure of the embedded twin: the handle works on without the twin (apply_hconst's rule).  Nothing of this happens between two members.
+static int drifts_prepare(jq_handle* h, const double* Hconsts, int ndrift)
+{
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t nn = (size_t)h->Ntot * h->Ntot;
+    bool fit = true;
+    for (int i = 0; i < ndrift && fit; ++i) fit = hconst_fits_plan(h, Hconsts + i * nn);
+    if (!fit) {
+        const std::vector<double> own = h->Hconst;
+        std::vector<double> uni = own;
+        for (int i = 0; i < ndrift; ++i)
+            for (size_t e = 0; e < nn; ++e)
+                if (uni[e] == 0.0) uni[e] = Hconsts[i * nn + e];
+        if (int rc = replan(h, uni.data())) return rc;
+        if (int rc = apply_hconst(h, own.data())) return rc;
+        for (int i = 0; i < ndrift; ++i)
+            if (!hconst_fits_plan(h, Hconsts + i * nn)) return fail(h, JQ_EHIP, "internal error: a member drift lies outside the plan made for the union of the members");
+    }
     if (h->emb) {
         jq_handle* e = h->emb;
-        embed_matrix(Hconst, h->Ntot, h->emb_row, e->Ntot, e->Hconst.data());
-        if (!t4_structure(e->Hconst.data(), e->Ntot) || upload_operators(e) != JQ_OK) {   // the new drift breaks the structure:
-            jq_destroy(e);                                                                // work without the embedded twin
-            h->emb = nullptr;
+        std::vector<double> em((size_t)e->Ntot * e->Ntot);
+        for (int i = 0; i < ndrift && h->emb; ++i) {
+            embed_matrix(Hconsts + i * nn, h->Ntot, h->emb_row, e->Ntot, em.data());
+            if (!t4_structure(em.data(), e->Ntot)) {
+                jq_destroy(e);
+                h->emb = nullptr;
+            }
         }
     }
-    return upload_operators(h);
+    return JQ_OK;
 }
 
 extern "C" int jq_update_hconst_csc(jq_handle* h, const jq_csc* Hconst)

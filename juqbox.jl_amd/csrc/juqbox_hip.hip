@@ -150,6 +150,8 @@ struct jq_handle {
     double *d_himg = nullptr, *d_uimg = nullptr, *d_vtr = nullptr, *d_vti = nullptr, *d_tabs = nullptr;
     double *d_tf = nullptr, *d_tb = nullptr, *d_cfreq = nullptr, *d_pcof = nullptr;
     double *d_stream = nullptr, *d_pq = nullptr;
+    double* d_drift = nullptr;  // drift images of the members of a drift ensemble's launch, [groups][stride of the planned family] (run_eval)
+    size_t cap_drift = 0;
     double *d_state = nullptr, *d_state_save = nullptr, *d_colinfo = nullptr, *d_traces = nullptr, *d_R = nullptr;
     double *d_grad = nullptr, *d_res = nullptr;
     double *d_wq = nullptr, *d_pack = nullptr;   // ensemble weights per sample; packed result [2 + 2 nCoeff] (multi-device all-reduce)
@@ -160,6 +162,9 @@ struct jq_handle {
     // not kept here: they travel in its EvalRequest (jq_host_eval.h)
     std::string pb_mode, pb_why;
     int pb_family = -1, pb_per_launch = 0, pb_nodes = 1;
+    // ... and the last jq_traceobjgrad_drifts / jq_eval_f_g_grad_drifts with its members (jq_plan_info "drift_batch")
+    std::string db_mode, db_why;
+    int db_family = -1, db_per_launch = 0;
     // Structure embedding (try_embed): a second handle of the SAME problem with its two fastest Kronecker factors zero-padded
     // to 4 levels each (row i1 + d1 i2 + d1 d2 i3 -> i1 + 4 i2 + 16 i3), under which the operators have the JQ_BW_T4 structure;
     // batches that would otherwise run on the dense / band MFMA kernels go there (quad-layout / JQ_BW_T4 slab kernels).
@@ -287,23 +292,39 @@ static int pcof_batch_per_launch(jq_handle* h, int npcof, int Q, bool adjoint, i
 // round a vector runs in), else -- every route without grouped streams -- one plain evaluation per vector, the very request of the single call.
 // put(i, res, g0, g1): column i of the caller's outputs from the records of its nquad samples and its gradients (g0: adjoint only, g1:
 // objFuncType != 1 as well).  Timing: sums over the launches; every other field is the last launch's.
+// What differs between the groups is the parameter: control vectors (drifts == NULL: pcofs holds npcof of them) or drift Hamiltonians
+// (drifts: [Ntot x Ntot x npcof] members that drifts_prepare has tested against the plan, pcofs: ONE vector, nquad == 1).  A grouped launch
+// of members hands run_eval their drifts; the sequential routes make member after member the handle's drift (apply_hconst: operator images
+// only, no re-plan) for the single call's request and put the handle's own drift back at the end.
 template <typename Put>
-static int pcof_batch(jq_handle* h, const double* pcofs, int ncoeff, int npcof, const double* nodes, const double* weights, int nquad,
-                      const double* shift, bool adjoint, Put&& put)
+static int pcof_batch(jq_handle* h, const double* pcofs, int ncoeff, int npcof, const double* drifts, const double* nodes, const double* weights,
+                      int nquad, const double* shift, bool adjoint, Put&& put)
 {
     int spg = 1, family = -1;
     const char* why = "";
     const int per = pcof_batch_per_launch(h, npcof, nquad, adjoint, &spg, &family, &why);
     const int step = per > 0 ? per : 1;
-    h->pb_mode = per > 0 ? "grouped" : "sequential", h->pb_why = why, h->pb_family = family, h->pb_per_launch = step, h->pb_nodes = nquad;
+    if (drifts) h->db_mode = per > 0 ? "grouped" : "sequential", h->db_why = why, h->db_family = family, h->db_per_launch = step;
+    else h->pb_mode = per > 0 ? "grouped" : "sequential", h->pb_why = why, h->pb_family = family, h->pb_per_launch = step, h->pb_nodes = nquad;
     EvalRequest rq;
     rq.ncoeff = ncoeff, rq.nsamples = nquad, rq.eps = nodes, rq.wgt = weights, rq.shift = shift, rq.adjoint = adjoint;
     if (per > 0) rq.spg = spg, rq.nodes = nquad;
+    const size_t nn = (size_t)h->Ntot * h->Ntot;
+    const bool swap = drifts && per == 0;
+    const std::vector<double> own = swap ? h->Hconst : std::vector<double>();
+    struct Restore {      // (also when a member's evaluation fails)
+        jq_handle* h;
+        const std::vector<double>* own;
+        ~Restore() { if (own) (void)apply_hconst(h, own->data()); }
+    } restore{h, swap ? &own : nullptr};
     jq_timing tsum = {};
     for (int i0 = 0; i0 < npcof; i0 += step) {
         const int G = std::min(step, npcof - i0);      // (sequential: one vector, spg == 1)
-        rq.pcof = pcofs + (size_t)ncoeff * i0;
+        rq.pcof = drifts ? pcofs : pcofs + (size_t)ncoeff * i0;
         if (per > 0) rq.groups = G, rq.nsamples = G * spg;
+        if (drifts && per > 0) rq.drifts = drifts + nn * i0;
+        if (swap)
+            if (int rc = apply_hconst(h, drifts + nn * i0)) return rc;
         EvalOut o;
         if (int rc = run_eval(h, rq, &o)) return rc;
         for (int g = 0; g < G; ++g)
@@ -326,10 +347,78 @@ extern "C" int jq_traceobjgrad_batch(jq_handle* h, const double* pcofs, int32_t 
     if (npcof < 1) return fail(h, JQ_EINVAL, "jq_traceobjgrad_batch: npcof must be >= 1");
     if (!h->subs.empty()) return multi_traceobjgrad_batch(h, pcofs, ncoeff, npcof, evaladjoint, out4, totalgrad, infidelgrad, leakgrad);
     if (int rc = check_ncoeff(h, ncoeff)) return rc;      // (before anything is written)
-    return pcof_batch(h, pcofs, ncoeff, npcof, nullptr, nullptr, 1, nullptr, evaladjoint != 0, [&](int i, const double* res, const double* g0, const double* g1) {
+    return pcof_batch(h, pcofs, ncoeff, npcof, nullptr, nullptr, nullptr, 1, nullptr, evaladjoint != 0, [&](int i, const double* res, const double* g0, const double* g1) {
         const size_t off = (size_t)ncoeff * i;
         out_record(out4 + (size_t)4 * i, res);
         if (evaladjoint) out_grads(h, ncoeff, g0, g1, totalgrad + off, infidelgrad + off, leakgrad + off);
+    });
+}
+
+// jq_traceobjgrad_drifts on a single-device handle whose plan holds every member (prepared: by the caller -- a multi-device handle tests
+// ALL members on every device before it shards them, so that the devices keep one plan)
+static int traceobjgrad_drifts_single(jq_handle* h, const double* pcof, int ncoeff, const double* Hconsts, int ndrift, int evaladjoint, bool prepared,
+                                      double* out4, double* totalgrad, double* infidelgrad, double* leakgrad)
+{
+    if (int rc = check_ncoeff(h, ncoeff)) return rc;      // (before anything is written or re-planned)
+    if (!prepared)
+        if (int rc = drifts_prepare(h, Hconsts, ndrift)) return rc;
+    return pcof_batch(h, pcof, ncoeff, ndrift, Hconsts, nullptr, nullptr, 1, nullptr, evaladjoint != 0, [&](int i, const double* res, const double* g0, const double* g1) {
+        const size_t off = (size_t)ncoeff * i;
+        out_record(out4 + (size_t)4 * i, res);
+        if (evaladjoint) out_grads(h, ncoeff, g0, g1, totalgrad + off, infidelgrad + off, leakgrad + off);
+    });
+}
+
+extern "C" int jq_traceobjgrad_drifts(jq_handle* h, const double* pcof, int32_t ncoeff, const double* Hconsts, int32_t ndrift, int32_t evaladjoint,
+                                      double* out4, double* totalgrad, double* infidelgrad, double* leakgrad)
+{
+    if (!h) return JQ_EINVAL;
+    return abi_guard(h, "jq_traceobjgrad_drifts", [&]() -> int {
+        if (!pcof || !Hconsts || !out4) return fail(h, JQ_EINVAL, "jq_traceobjgrad_drifts: NULL pointer");
+        if (evaladjoint && (!totalgrad || !infidelgrad || !leakgrad))
+            return fail(h, JQ_EINVAL, "jq_traceobjgrad_drifts: gradient outputs are required when evaladjoint != 0");
+        if (ndrift < 1) return fail(h, JQ_EINVAL, "jq_traceobjgrad_drifts: ndrift must be >= 1");
+        if (!h->subs.empty()) return multi_traceobjgrad_drifts(h, pcof, ncoeff, Hconsts, ndrift, evaladjoint, out4, totalgrad, infidelgrad, leakgrad);
+        return traceobjgrad_drifts_single(h, pcof, ncoeff, Hconsts, ndrift, evaladjoint, false, out4, totalgrad, infidelgrad, leakgrad);
+    });
+}
+
+// the weighted sums of eval_f_g_grad! (src/ipopt_interface.jl:48-59) over the members of a drift ensemble instead of over eps-nodes: the
+// members' columns from jq_traceobjgrad_drifts, summed on the host in member order
+extern "C" int jq_eval_f_g_grad_drifts(jq_handle* h, const double* pcof, int32_t ncoeff, const double* Hconsts, const double* weights, int32_t ndrift,
+                                       int32_t compute_adjoint, double* out2, double* infid_grad, double* leak_grad, double* member_out)
+{
+    if (!h) return JQ_EINVAL;
+    return abi_guard(h, "jq_eval_f_g_grad_drifts", [&]() -> int {
+        if (!pcof || !Hconsts || !weights || !out2) return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_drifts: NULL pointer");
+        if (compute_adjoint && (!infid_grad || !leak_grad))
+            return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_drifts: gradient outputs are required when compute_adjoint != 0");
+        if (ndrift < 1) return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_drifts: ndrift must be >= 1");
+        if (int rc = check_ncoeff(h->subs.empty() ? h : h->subs[0], ncoeff)) {      // (before the temporaries are sized by it)
+            if (!h->subs.empty()) h->err = h->subs[0]->err;
+            return rc;
+        }
+        const size_t ng = compute_adjoint ? (size_t)ncoeff * ndrift : 0;
+        std::vector<double> rec((size_t)4 * ndrift), tg(ng), ig(ng), lg(ng);
+        const int rc = jq_traceobjgrad_drifts(h, pcof, ncoeff, Hconsts, ndrift, compute_adjoint, rec.data(), tg.data(), ig.data(), lg.data());
+        if (rc) return rc;
+        double inf = 0.0, leak = 0.0;
+        for (int i = 0; i < ndrift; ++i) {
+            inf += rec[(size_t)4 * i + 1] * weights[i];      // (primaryobjf, secondaryobjf of the member's record)
+            leak += rec[(size_t)4 * i + 2] * weights[i];
+        }
+        out2[0] = inf, out2[1] = leak;
+        if (member_out) std::copy(rec.begin(), rec.end(), member_out);
+        if (compute_adjoint) {
+            std::fill_n(infid_grad, ncoeff, 0.0);
+            std::fill_n(leak_grad, ncoeff, 0.0);
+            for (int i = 0; i < ndrift; ++i)
+                for (int k = 0; k < ncoeff; ++k) {
+                    infid_grad[k] += weights[i] * ig[(size_t)ncoeff * i + k];
+                    leak_grad[k] += weights[i] * lg[(size_t)ncoeff * i + k];
+                }
+        }
+        return JQ_OK;
     });
 }
 
@@ -527,7 +616,7 @@ extern "C" int jq_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int32_t
         return multi_eval_f_g_grad_batch(h, pcofs, ncoeff, npcof, nodes, weights, nquad, shift, compute_adjoint, out2, infid_grad, leak_grad, node_out);
     if (int rc = check_ncoeff(h, ncoeff)) return rc;      // (before anything is written)
     // column i of the outputs from the records of its nquad samples (the sums in node order: src/ipopt_interface.jl:58-59)
-    return pcof_batch(h, pcofs, ncoeff, npcof, nodes, weights, nquad, shift, compute_adjoint != 0, [&](int i, const double* res, const double* g0, const double* g1) {
+    return pcof_batch(h, pcofs, ncoeff, npcof, nullptr, nodes, weights, nquad, shift, compute_adjoint != 0, [&](int i, const double* res, const double* g0, const double* g1) {
         double inf = 0.0, leak = 0.0;
         for (int q = 0; q < nquad; ++q) {
             inf += res[(size_t)q * 4 + 0] * weights[q];

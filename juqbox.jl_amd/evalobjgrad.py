@@ -11,6 +11,9 @@
   traceobjgrad_batch(pcofs, params, wa, evaladjoint=True)
                                         many control vectors of ONE problem in one library call
                                         (jq_traceobjgrad_batch): column i = traceobjgrad of vector i.
+  traceobjgrad_drifts(pcof, params, wa, Hconsts, evaladjoint=True)
+                                        ONE control vector over an ensemble of drift Hamiltonians in one library
+                                        call (jq_traceobjgrad_drifts): column i = traceobjgrad with Hconst = member i.
   gradient_check(pcof0, params, wa, kpars, h=1e-6)
                                         adjoint gradient entries against central differences, from one batch.
 """
@@ -398,6 +401,65 @@ def traceobjgrad_batch(pcofs, params: objparams, wa: Working_Arrays_HIP, evaladj
         return out4[:, 0].copy(), out4[:, 1].copy(), out4[:, 2].copy()
     tg, ig, lg = np.zeros((n, ncoeff)), np.zeros((n, ncoeff)), np.zeros((n, ncoeff))
     _lib.check(L.jq_traceobjgrad_batch(h, _ptr(P), ncoeff, n, 1, _ptr(out4), _ptr(tg), _ptr(ig), _ptr(lg)), h)
+    leak = np.zeros((0, n)) if params.objFuncType == 1 else np.ascontiguousarray(lg.T)
+    return (out4[:, 0].copy(), np.ascontiguousarray(tg.T), out4[:, 1].copy(), out4[:, 2].copy(), out4[:, 3].copy(),
+            np.ascontiguousarray(ig.T), leak)
+
+
+def _drift_members(Hconsts, Ntot, who):
+    """Hconsts -> contiguous [ndrift, Ntot * Ntot] array, member i column-major in row i (= the C ABI's Ntot x Ntot x ndrift).  An
+    Ntot x Ntot x ndrift array holds one member per slice [:, :, i], a sequence one matrix per element, a 2-D array is one member.
+    ValueError for everything else."""
+    if isinstance(Hconsts, np.ndarray):
+        if Hconsts.ndim == 2:
+            mats = [Hconsts]
+        elif Hconsts.ndim == 3:
+            mats = [Hconsts[:, :, i] for i in range(Hconsts.shape[2])]
+        else:
+            raise ValueError("%s: Hconsts must be an Ntot x Ntot x ndrift array or a sequence of matrices, not %d-dimensional" % (who, Hconsts.ndim))
+    else:
+        try:
+            mats = [np.asarray(M, dtype=np.float64) for M in Hconsts]
+        except (TypeError, ValueError) as e:
+            raise ValueError("%s: Hconsts must be an Ntot x Ntot x ndrift array or a sequence of matrices (%s)" % (who, e))
+    if len(mats) == 0:
+        raise ValueError("%s: need at least one member drift" % who)
+    for i, M in enumerate(mats):
+        if np.ndim(M) != 2 or np.shape(M) != (Ntot, Ntot):
+            raise ValueError("%s: member %d has shape %r, expected (%d, %d) (params.Ntot)" % (who, i, np.shape(M), Ntot, Ntot))
+    return np.ascontiguousarray(np.stack([_f64(M) for M in mats]))
+
+
+def traceobjgrad_drifts(pcof, params: objparams, wa: Working_Arrays_HIP, Hconsts, evaladjoint: bool = True):
+    """ndrift evaluations traceobjgrad(pcof, params with Hconst = Hconsts[:, :, i], wa, False, evaladjoint) of ONE control vector in one
+    library call (jq_traceobjgrad_drifts) -- the loop `params.Hconst = H_i; traceobjgrad(...)` of the reference's scripts.  On the row-lane
+    and cooperative-quad (latency) kernels with the Stormer-Verlet integrator and the Neumann solver the members share launches -- every
+    workgroup reads the operator stream of its own member's drift --, everywhere else the handle's drift is swapped per member inside the
+    call (wa.plan_info()["drift_batch"] says which).  Column i is bit-identical to that loop on the same kernel variant and chunk length;
+    params.Hconst and the handle's drift are what they were afterwards.  A member outside the structure the handle was planned for
+    re-plans it once, for the union of all patterns (see include/juqbox_hip.h).
+
+    Hconsts: an Ntot x Ntot x ndrift array or a sequence of Ntot x Ntot matrices.
+    Returns the arrays of traceobjgrad_batch, one column per member.  Shape errors raise ValueError before any library call."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("traceobjgrad_drifts: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("traceobjgrad_drifts: wa was allocated for a different objparams")
+    ncoeff = int(wa.nCoeff)
+    H = _drift_members(Hconsts, int(params.Ntot), "traceobjgrad_drifts")
+    p = np.asarray(pcof, dtype=np.float64)
+    if p.ndim != 1 or p.size != ncoeff:
+        raise ValueError("traceobjgrad_drifts: pcof has shape %r, expected (%d,) (wa.nCoeff)" % (p.shape, ncoeff))
+    p = _f64(p)
+    n = H.shape[0]
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    out4 = np.zeros((n, 4))
+    if not evaladjoint:
+        _lib.check(L.jq_traceobjgrad_drifts(h, _ptr(p), ncoeff, _ptr(H), n, 0, _ptr(out4), None, None, None), h)
+        return out4[:, 0].copy(), out4[:, 1].copy(), out4[:, 2].copy()
+    tg, ig, lg = np.zeros((n, ncoeff)), np.zeros((n, ncoeff)), np.zeros((n, ncoeff))
+    _lib.check(L.jq_traceobjgrad_drifts(h, _ptr(p), ncoeff, _ptr(H), n, 1, _ptr(out4), _ptr(tg), _ptr(ig), _ptr(lg)), h)
     leak = np.zeros((0, n)) if params.objFuncType == 1 else np.ascontiguousarray(lg.T)
     return (out4[:, 0].copy(), np.ascontiguousarray(tg.T), out4[:, 1].copy(), out4[:, 2].copy(), out4[:, 3].copy(),
             np.ascontiguousarray(ig.T), leak)

@@ -5,7 +5,7 @@ signatures, so any L-BFGS driver can call them)."""
 import numpy as np
 
 from . import _lib
-from .evalobjgrad import Working_Arrays_HIP, _f64, _pcof_columns, _ptr
+from .evalobjgrad import Working_Arrays_HIP, _drift_members, _f64, _pcof_columns, _ptr
 from .setup_utils import tikhonov_grad, tikhonov_pen
 
 
@@ -198,33 +198,96 @@ def eval_f_g_grad_batch(pcofs, params, wa, nodes, weights, compute_adjoint=True,
     return res
 
 
+def _drift_ensemble(params, Hconsts, weights, who):
+    """(members [ndrift, Ntot * Ntot], weights [ndrift]) of a drift ensemble; ValueError for wrong shapes"""
+    H = _drift_members(Hconsts, int(params.Ntot), who)
+    try:
+        w = np.asarray(weights, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("%s: weights must be a vector of numbers (%s)" % (who, e))
+    if w.ndim != 1 or w.size != H.shape[0]:
+        raise ValueError("%s: need one weight per member drift (%d), not shape %r" % (who, H.shape[0], w.shape))
+    return H, _f64(w)
+
+
+def eval_f_g_grad_drifts(pcof, params, wa, Hconsts, weights, compute_adjoint=True, per_member=False):
+    """eval_f_g_grad over an ensemble of ARBITRARY drift Hamiltonians in one library call (jq_eval_f_g_grad_drifts): the weighted sums
+    sum_i w_i infidelity_i, sum_i w_i leak_i and, with compute_adjoint, of the members' gradients, member i being the evaluation with
+    params.Hconst = Hconsts[:, :, i] -- uncertain frequencies on a tensor grid, an uncertain anharmonicity, cross-Kerr or coupling term.
+    Routing as traceobjgrad_drifts (wa.plan_info()["drift_batch"]).  Results land in params.last_* exactly as eval_f_g_grad leaves them.
+
+    Hconsts: an Ntot x Ntot x ndrift array or a sequence of Ntot x Ntot matrices; weights: one per member.
+    Returns (last_infidelity, last_leak), with per_member=True also the array [4, ndrift] of (objfv, primaryobjf, secondaryobjf,
+    traceInfidelity) per member -- the bits of traceobjgrad_drifts.  Shape errors raise ValueError before any library call."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("eval_f_g_grad_drifts: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("eval_f_g_grad_drifts: wa was allocated for a different objparams")
+    H, w = _drift_ensemble(params, Hconsts, weights, "eval_f_g_grad_drifts")
+    p = np.asarray(pcof, dtype=np.float64)
+    n = int(wa.nCoeff)
+    if p.ndim != 1 or p.size != n:
+        raise ValueError("eval_f_g_grad_drifts: pcof has shape %r, expected (%d,) (wa.nCoeff)" % (p.shape, n))
+    p = _f64(p)
+    nd = H.shape[0]
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    # (the memoised gradients are reset like eval_f_g_grad resets them: src/ipopt_interface.jl:27-31)
+    params.last_infidelity_grad = np.zeros(n)
+    params.last_leak_grad = np.zeros(n) if params.objFuncType != 1 else np.zeros(0)
+    out2 = np.zeros(2)
+    ig, lg = np.zeros(n), np.zeros(n)
+    member_out = np.zeros((nd, 4)) if per_member else None
+    _lib.check(L.jq_eval_f_g_grad_drifts(h, _ptr(p), n, _ptr(H), _ptr(w), nd, 1 if compute_adjoint else 0, _ptr(out2), _ptr(ig), _ptr(lg),
+                                         _ptr(member_out)), h)
+    params.last_pcof = p.copy()
+    params.last_infidelity = float(out2[0])
+    params.last_leak = float(out2[1])
+    if compute_adjoint:
+        params.last_infidelity_grad = ig.copy()
+        params.last_leak_grad = lg.copy() if params.objFuncType != 1 else np.zeros(0)
+    params.lastTraceInfidelity = params.last_infidelity
+    params.lastLeakIntegral = params.last_leak
+    if per_member:
+        return params.last_infidelity, params.last_leak, np.ascontiguousarray(member_out.T)
+    return params.last_infidelity, params.last_leak
+
+
 def _stale(pcof, params):
     # memoisation on ||pcof - last_pcof|| > 1e-15 (src/ipopt_interface.jl:83-84)
     last = params.last_pcof
     return last.size != np.size(pcof) or np.linalg.norm(np.asarray(pcof, dtype=np.float64) - last) > 1.0e-15
 
 
-def eval_f_par(pcof, params, wa, nodes=(0.0,), weights=(1.0,)):
+def _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights):
+    """the evaluation the callbacks memoise: eval_f_g_grad over the eps-nodes, or (drifts given) eval_f_g_grad_drifts over the members"""
+    if drifts is not None:
+        eval_f_g_grad_drifts(pcof, params, wa, drifts, drift_weights, True)
+    else:
+        eval_f_g_grad(pcof, params, wa, nodes, weights, True)
+
+
+def eval_f_par(pcof, params, wa, nodes=(0.0,), weights=(1.0,), drifts=None, drift_weights=None):
     """src/ipopt_interface.jl:77-99"""
     if _stale(pcof, params):
-        eval_f_g_grad(pcof, params, wa, nodes, weights, True)
+        _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights)
     f = params.last_infidelity + params.last_leak if params.objFuncType == 1 else params.last_infidelity
     prior = params.priorCoeffs if params.usingPriorCoeffs else None
     return f + tikhonov_pen(pcof, params.tik0, prior)
 
 
-def eval_g_par(pcof, g, params, wa, nodes=(0.0,), weights=(1.0,)):
+def eval_g_par(pcof, g, params, wa, nodes=(0.0,), weights=(1.0,), drifts=None, drift_weights=None):
     """src/ipopt_interface.jl:104-118"""
     if _stale(pcof, params):
-        eval_f_g_grad(pcof, params, wa, nodes, weights, True)
+        _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights)
     g[0] = params.last_leak
     return g[0]
 
 
-def eval_grad_f_par(pcof, grad_f, params, wa, nodes=(0.0,), weights=(1.0,)):
+def eval_grad_f_par(pcof, grad_f, params, wa, nodes=(0.0,), weights=(1.0,), drifts=None, drift_weights=None):
     """src/ipopt_interface.jl:124-148"""
     if _stale(pcof, params):
-        eval_f_g_grad(pcof, params, wa, nodes, weights, True)
+        _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights)
     grad_f[:] = params.last_infidelity_grad
     prior = params.priorCoeffs if params.usingPriorCoeffs else None
     wa.gr[:] = tikhonov_grad(pcof, params.tik0, prior)
@@ -233,7 +296,7 @@ def eval_grad_f_par(pcof, grad_f, params, wa, nodes=(0.0,), weights=(1.0,)):
         params.pcof_hist.append(np.array(pcof, dtype=np.float64))
 
 
-def eval_jac_g_par(pcof, rows, cols, jac_g, params, wa, nodes=(0.0,), weights=(1.0,)):
+def eval_jac_g_par(pcof, rows, cols, jac_g, params, wa, nodes=(0.0,), weights=(1.0,), drifts=None, drift_weights=None):
     """src/ipopt_interface.jl:153-179 (including its quirk: when it has to recompute it returns
     without filling jac_g, :169-173)."""
     if jac_g is None:
@@ -243,7 +306,7 @@ def eval_jac_g_par(pcof, rows, cols, jac_g, params, wa, nodes=(0.0,), weights=(1
                 cols[i] = i + 1
         return
     if _stale(pcof, params):
-        eval_f_g_grad(pcof, params, wa, nodes, weights, True)
+        _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights)
         return
     jac_g[:] = params.last_leak_grad
 
@@ -300,8 +363,18 @@ class OptimProblem:
 
 def setup_ipopt_problem(params, wa, nCoeff, minCoeff, maxCoeff, maxIter=50, lbfgsMax=10, startFromScratch=True,
                         ipTol=1.0e-5, acceptTol=1.0e-5, acceptIter=15, nodes=(0.0,), weights=(1.0,),
-                        jacob_approx="exact"):
-    """src/ipopt_interface.jl:262-415."""
+                        jacob_approx="exact", drifts=None, drift_weights=None):
+    """src/ipopt_interface.jl:262-415.
+    drifts (an Ntot x Ntot x ndrift array or a sequence of matrices) with drift_weights (one per member): the callbacks memoise through
+    eval_f_g_grad_drifts instead of eval_f_g_grad, so run_optimizer optimises the risk-neutral objective over that drift ensemble
+    (nodes / weights are then not used).  Shape errors raise ValueError before any library call."""
+    if drifts is not None:
+        if drift_weights is None:
+            raise ValueError("setup_ipopt_problem: drifts needs drift_weights (one weight per member)")
+        drifts, drift_weights = _drift_ensemble(params, drifts, drift_weights, "setup_ipopt_problem")
+        drifts = [M.reshape((int(params.Ntot), int(params.Ntot)), order="F") for M in drifts]
+    elif drift_weights is not None:
+        raise ValueError("setup_ipopt_problem: drift_weights without drifts")
     minCoeff = np.asarray(minCoeff, dtype=np.float64)
     maxCoeff = np.asarray(maxCoeff, dtype=np.float64)
     if minCoeff.size != nCoeff or maxCoeff.size != nCoeff:
@@ -317,11 +390,12 @@ def setup_ipopt_problem(params, wa, nCoeff, minCoeff, maxCoeff, maxIter=50, lbfg
     prob = OptimProblem()
     prob.params, prob.wa, prob.nCoeff = params, wa, int(nCoeff)
     prob.x_L, prob.x_U = minCoeff, maxCoeff
-    prob.eval_f = lambda pcof: eval_f_par(pcof, params, wa, nodes, weights)
+    ens = dict(drifts=drifts, drift_weights=drift_weights)
+    prob.eval_f = lambda pcof: eval_f_par(pcof, params, wa, nodes, weights, **ens)
 
     def _grad(pcof):
         g = np.zeros(nCoeff)
-        eval_grad_f_par(pcof, g, params, wa, nodes, weights)
+        eval_grad_f_par(pcof, g, params, wa, nodes, weights, **ens)
         return g
     prob.eval_grad_f = _grad
     if params.objFuncType == 3:                               # :299-306: leakage as an inequality constraint
@@ -333,14 +407,14 @@ def setup_ipopt_problem(params, wa, nCoeff, minCoeff, maxCoeff, maxIter=50, lbfg
 
     def _g(pcof):
         g = np.zeros(1)
-        eval_g_par(pcof, g, params, wa, nodes, weights)
+        eval_g_par(pcof, g, params, wa, nodes, weights, **ens)
         return g
 
     def _jac_g(pcof):
         jac = np.zeros(nCoeff)
         if _stale(pcof, params):     # the reference's callback returns unfilled in this case (:169-173); Ipopt
-            eval_f_g_grad(pcof, params, wa, nodes, weights, True)   # always calls eval_g first -- here we recompute
-        eval_jac_g_par(pcof, [], [], jac, params, wa, nodes, weights)
+            _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights)   # always calls eval_g first -- here we recompute
+        eval_jac_g_par(pcof, [], [], jac, params, wa, nodes, weights, **ens)
         return jac
     prob.eval_g, prob.eval_jac_g = _g, _jac_g
     prob.intermediate = lambda it, obj, inf_du: intermediate_par(0, it, obj, 0.0, inf_du, 0.0, 0.0, 0.0, 0.0, 0.0, 0,
