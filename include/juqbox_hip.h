@@ -465,7 +465,13 @@ int jq_traceobj_sweep(jq_handle *h, const double *pcof, int32_t ncoeff, const do
  * Kronecker structure, "od" = diagonal off-diagonal blocks, "band" / "dense"), the embedded twin if any, the control groups, the
  * integrator / solver settings and -- the part a caller sizing an ensemble needs -- the batch-size thresholds of the kernel
  * families: "families" lists, in the order run_eval tries them, {family, name, max_columns / max_slabs / max_quads} for the
- * current settings.  jq_last_timing() reports which one actually ran.
+ * current settings.  jq_last_timing() reports which one actually ran, and "last_kernels" which instantiation of it: null before the
+ * first evaluation (and after a re-plan), then {"object", "forward_object": the kernel objects of the backward and the forward sweep
+ * as csrc/Makefile names them (k_6_7, s_6_7, p_6_7, u_6_7, k_6_8, c_6_9, ...; "host": the run-time-size kernels), "slabs_per_workgroup"
+ * (quad layout, else 0), "quads_per_workgroup" (split quad backward sweep: 4 / 2, else 0), "backward_workgroups" (cooperative quad: 1 /
+ * 2 / 3 workgroups per column quad, else 0), and the compile-time variant as booleans "uni", "ord", "sc_forward", "sc_backward", "ride",
+ * "modd", "fwd2", "wlr", "imr_two_sets"} -- recorded by the tables that pick the kernel (csrc/jq_host_select.h), for the first (larger)
+ * part of a batch that was split into two launches.  The key is additive: no ABI version change.
  */
 int jq_plan_info(const jq_handle *h, char *buf, int32_t buflen);
 

@@ -188,7 +188,7 @@ function get_option(wa::AbstractWorkingArraysHIP, name::AbstractString)
     return v[] == typemin(Int64) ? nothing : v[]
 end
 num_compute_units(wa::AbstractWorkingArraysHIP) = ccall((:jq_num_compute_units, libjq), Cint, (Ptr{Cvoid},), wa.handle)
-function plan_info(wa::AbstractWorkingArraysHIP)      # JSON text: structure, control groups, batch-size thresholds of the kernel families
+function plan_info(wa::AbstractWorkingArraysHIP)      # JSON text: structure, control groups, batch-size thresholds of the kernel families, "last_kernels" (the instantiation the last evaluation ran)
     n = ccall((:jq_plan_info, libjq), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Int32), wa.handle, C_NULL, 0)
     n >= 0 || error("jq_plan_info failed")
     buf = Vector{UInt8}(undef, n + 1)

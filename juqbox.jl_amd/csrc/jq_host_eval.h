@@ -139,6 +139,7 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
             part.split_part = true, part.nsamples = n1;
             int rc = run_eval(h, part, out);
             const jq_timing t1 = h->timing;
+            const KernelSel k1 = h->last_kernels;
             const size_t npk = (size_t)2 + 2 * (size_t)ncoeff;
             if (rc == JQ_OK && d_packed) {
                 rc = dev_grow(h, &h->d_pk2, &h->cap_pk2, npk);
@@ -159,6 +160,7 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
             // timing: sums; the kernel family / size / band reported are those of the first (larger) part
             timing_add(h->timing, t1);
             h->timing.kernel_family = t1.kernel_family, h->timing.kernel_size = t1.kernel_size, h->timing.kernel_band = t1.kernel_band;
+            h->last_kernels = k1;
             h->timing.ms_shard_min = h->timing.ms_shard_max = h->timing.ms_total;
             return JQ_OK;
         }
@@ -194,6 +196,7 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
         const int rc = run_eval(e, er, out);
         if (rc != JQ_OK) h->err = e->err;
         h->timing = e->timing;
+        if (rc == JQ_OK) h->last_kernels = e->last_kernels;
         return rc;
     }
     GateHold gate_hold;      // (held until the evaluation ends when the plan takes the split latency kernels)
@@ -581,6 +584,7 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     h->timing.kernel_size = p.kernel_size;
     h->timing.kernel_band = p.kernel_band;
     h->timing.kernel_variant = p.kernel_variant;
+    h->last_kernels = p.sel;
     h->timing.ms_allreduce = 0.0;
     h->timing.ms_shard_min = h->timing.ms_shard_max = h->timing.ms_total;
     return JQ_OK;

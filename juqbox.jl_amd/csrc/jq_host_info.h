@@ -114,6 +114,7 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
             if (x->BW == JQ_BW_T4) {
                 for (const char* pre : {"k", "s", "p", "u", "w", "q", "v"}) tag(pre, x->NT, JQ_BW_T4Q);
                 tag("k", x->NT, JQ_BW_T4);
+                tag("j", x->NT, JQ_BW_T4);
             } else if (!x->big) {
                 tag("k", x->NT, x->BW);
                 tag("j", x->NT, x->BW);
@@ -140,6 +141,18 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
             if (end != std::string::npos) hipcc = man.substr(at + 9, end - at - 8);
         }
         kv("build", std::string("{\"manifest\": ") + (man.size() > 2 ? "true" : "false") + ", \"hipcc\": " + hipcc + ", \"objects\": " + objs + "}");
+    }
+    {   // the instantiation the last evaluation ran on, recorded where the tables of jq_host_select.h picked its kernels (null: no evaluation
+        // since the handle was created or planned again): the objects of the backward and the forward kernel as csrc/Makefile names them
+        // (jq_timing's family / size / band cannot tell k_N_7 from s_N_7, nor a specialised instantiation from the generic one) and the
+        // compile-time variant.  The first (larger) part's where a batch was split into two launches; the embedded twin's where it served.
+        const KernelSel& k = h->last_kernels;
+        auto tf = [](bool v) { return std::string(v ? "true" : "false"); };
+        kv("last_kernels", !k.set ? std::string("null")
+                                  : std::string("{\"object\": \"") + k.bwd + "\", \"forward_object\": \"" + k.fwd + "\", \"slabs_per_workgroup\": " + num(k.spw) +
+                                        ", \"quads_per_workgroup\": " + num(k.qs_qw) + ", \"backward_workgroups\": " + num(k.bwd_wgs) + ", \"uni\": " + tf(k.uni) +
+                                        ", \"ord\": " + tf(k.ord) + ", \"sc_forward\": " + tf(k.sc_fwd) + ", \"sc_backward\": " + tf(k.sc_bwd) + ", \"ride\": " + tf(k.ride) +
+                                        ", \"modd\": " + tf(k.modd) + ", \"fwd2\": " + tf(k.fwd2) + ", \"wlr\": " + tf(k.wlr) + ", \"imr_two_sets\": " + tf(k.imr_two) + "}");
     }
     kv("full_weight_rank", num(h->wrank));
     kv("options", hh->opt.str(), true);      // the options that are set (jq_create_opts / JQ_OPTIONS / jq_set_option); "" = all defaults

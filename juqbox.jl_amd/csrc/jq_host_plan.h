@@ -146,6 +146,7 @@ struct BatchPlan {
     size_t lds_stage;           // ... bytes of the operator staging (the tables behind it), ...
     SweepLds fwd, bwd;          // ... each sweep's areas behind its layout
     int kernel_size, kernel_band, kernel_variant;      // jq_timing (kernel_family: family)
+    KernelSel sel;              // what select_* chose for kfwd / kbwd (jq_plan_info "last_kernels")
 };
 // MFMA tiles of the trace products of control q per step (jq_timing.mfma_executed)
 static long long plan_trace_tiles(const jq_handle* h, const BatchPlan& p, int q)
@@ -337,6 +338,7 @@ static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateH
     }
     if (rc) return rc;
     if (qsplit && (rc = select_qsplit_kernel(h, p->qs_qw, &p->kbwd))) return rc;
+    p->sel = h->sel;
     // Jacobi solver with N > 16 on the slab kernels: ONE workgroup per sample when its parts fit one (N <= 64): the waves add their parts'
     // residual norms through LDS, so the stopping test is the reference's (src/linear_solvers.jl:121), not one per 16-column part (round 5;
     // option jac_wg=0: per part, as with more parts or the cooperative kernels)

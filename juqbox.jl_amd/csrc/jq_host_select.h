@@ -3,6 +3,22 @@
 // ---------------------------------------------------------------------------------------------
 typedef void (*prop_kernel_t)(PropArgs);
 
+// What the tables below chose (KernelSel, juqbox_hip.hip; jq_plan_info "last_kernels"): every branch that assigns a kernel pointer names
+// the object the instantiation is compiled into (csrc/Makefile, jq_kernel_inst.hip) and its compile-time variant in the same statement
+// block, so the record cannot drift from the choice.  sel_objects starts a record (both sweeps from one object).
+static void sel_tag(char* dst, char prefix, int a, int b)
+{
+    if (b >= 0) snprintf(dst, JQ_SEL_TAG, "%c_%d_%d", prefix, a, b);
+    else snprintf(dst, JQ_SEL_TAG, "%c_%d", prefix, a);
+}
+static void sel_objects(jq_handle* h, char prefix, int a, int b = -1)
+{
+    h->sel = KernelSel();
+    h->sel.set = true;
+    sel_tag(h->sel.fwd, prefix, a, b);
+    sel_tag(h->sel.bwd, prefix, a, b);
+}
+
 // The (NT, BW) instantiations are compiled in their own translation units (jq_kernel_inst.hip).
 #define JQ_FOR_EACH_INST(X)                                                                       \
     X(1, 0) X(2, 0) X(2, 1) X(3, 0) X(3, 1) X(3, 2) X(4, 0) X(4, 1) X(4, 2) X(4, 3) X(5, 0) X(5, 1) \
@@ -35,11 +51,13 @@ static int select_kernels(jq_handle* h, prop_kernel_t* fwd, prop_kernel_t* bwd)
         if (h->NT == 1 && h->BW == 0) {
             *fwd = jac ? k_forward<1, 0, JQ_MINW_OF(1), true, true> : k_forward<1, 0, JQ_MINW_OF(1), false, true>;
             *bwd = jac ? k_backward<1, 0, JQ_MINW_OF(1), true, true> : k_backward<1, 0, JQ_MINW_OF(1), false, true>;
+            sel_objects(h, jac ? 'x' : 'w', 1, 0), h->sel.wlr = true;
             return JQ_OK;
         }
         if (h->NT == 6 && h->BW == 5) {
             *fwd = jac ? k_forward<6, 5, JQ_MINW_OF(6), true, true> : k_forward<6, 5, JQ_MINW_OF(6), false, true>;
             *bwd = jac ? k_backward<6, 5, JQ_MINW_OF(6), true, true> : k_backward<6, 5, JQ_MINW_OF(6), false, true>;
+            sel_objects(h, jac ? 'x' : 'w', 6, 5), h->sel.wlr = true;
             return JQ_OK;
         }
         return fail(h, JQ_EUNSUPPORTED, "full leakage weights (jq_update_wmat): no kernels with the low-rank terms for this plan (row-lane kernels "
@@ -49,6 +67,7 @@ static int select_kernels(jq_handle* h, prop_kernel_t* fwd, prop_kernel_t* bwd)
     if (h->NT == nt && h->BW == bw) {                                                                    \
         *fwd = jac ? k_forward<nt, bw, JQ_MINW_OF(nt), true> : k_forward<nt, bw, JQ_MINW_OF(nt), false>; \
         *bwd = jac ? k_backward<nt, bw, JQ_MINW_OF(nt), true> : k_backward<nt, bw, JQ_MINW_OF(nt), false>; \
+        sel_objects(h, jac ? 'j' : 'k', nt, bw);                                                         \
         return JQ_OK;                                                                                    \
     }
     JQ_FOR_EACH_INST(JQ_PICK)
@@ -171,6 +190,7 @@ static int select_cq_kernels(jq_handle* h, bool fwd2, int bwd_nr, bool wlr, bool
         *bwd = bwd3 ? (modd ? k_backward_cq3<2, true, false, 3, false, true> : k_backward_cq3<2, false, false, 3, false, true>)
              : bwd2 ? (modd ? k_backward_cq3<2, true, false, 2, false, true> : k_backward_cq3<2, false, false, 2, false, true>)
                     : (modd ? k_backward_cq<2, true, false, false, true> : k_backward_cq<2, false, false, false, true>);
+        sel_objects(h, 'u', 2, JQ_BW_T4Q), h->sel.modd = modd, h->sel.bwd_wgs = bwd3 ? 3 : bwd2 ? 2 : 1;
         return JQ_OK;
     }
     const bool ord = h->Nc <= 3 && !h->opt.on(O_CQ_GENERIC_TRACES) && ctrl_per_subsystem(h);      // (more than JQ_MAXNC controls: generic traces per group)
@@ -183,6 +203,7 @@ static int select_cq_kernels(jq_handle* h, bool fwd2, int bwd_nr, bool wlr, bool
                             : (ord ? k_backward_cq3<nt, false, true, 2, true> : k_backward_cq3<nt, false, false, 2, true>))       \
                     : modd ? (ord ? k_backward_cq<nt, true, true, true> : k_backward_cq<nt, true, false, true>)         \
                            : (ord ? k_backward_cq<nt, false, true, true> : k_backward_cq<nt, false, false, true>);      \
+        sel_objects(h, 'u', nt, JQ_BW_T4Q), h->sel.modd = modd, h->sel.ord = ord, h->sel.wlr = true, h->sel.bwd_wgs = bwd3 ? 3 : bwd2 ? 2 : 1;   \
         return JQ_OK;                                                              \
     }                                                                              \
     if (h->NT == nt) {                                                             \
@@ -193,6 +214,7 @@ static int select_cq_kernels(jq_handle* h, bool fwd2, int bwd_nr, bool wlr, bool
                             : (ord ? k_backward_cq3<nt, false, true, 2> : k_backward_cq3<nt, false, false, 2>)) \
                     : modd ? (ord ? k_backward_cq<nt, true, true> : k_backward_cq<nt, true, false>)          \
                            : (ord ? k_backward_cq<nt, false, true> : k_backward_cq<nt, false, false>);       \
+        sel_objects(h, 'u', nt, JQ_BW_T4Q), h->sel.modd = modd, h->sel.ord = ord, h->sel.fwd2 = fwd2, h->sel.bwd_wgs = bwd3 ? 3 : bwd2 ? 2 : 1;   \
         return JQ_OK;                                                              \
     }
     JQ_PICKCQ(1) JQ_PICKCQ(2) JQ_PICKCQ(3) JQ_PICKCQ(4) JQ_PICKCQ(5) JQ_PICKCQ(6) JQ_PICKCQ(7)
@@ -212,6 +234,7 @@ static int select_quad_imr_kernels(jq_handle* h, prop_kernel_t* fwd, prop_kernel
     if (h->NT == nt) {                                \
         *fwd = k_forward_quad_imr<nt, 1>;             \
         *bwd = k_backward_quad_imr<nt, 1>;            \
+        sel_objects(h, 'q', nt, JQ_BW_T4Q), h->sel.spw = 1;   \
         return JQ_OK;                                 \
     }
     JQ_PICKQI(1) JQ_PICKQI(2) JQ_PICKQI(3) JQ_PICKQI(4) JQ_PICKQI(5) JQ_PICKQI(6) JQ_PICKQI(7) JQ_PICKQI(8)
@@ -244,12 +267,14 @@ static int select_cq_imr_kernels(jq_handle* h, bool two, bool three, bool dense,
         if (h->NT != 2 || two) return fail(h, JQ_EHIP, "internal error: dense implicit-midpoint cooperative-quad kernels selected for a plan they do not exist for");
         *fwd = k_forward_cq_imr<2, true>;
         *bwd = three ? k_backward_cq_imr3<2, true> : k_backward_cq_imr<2, true>;
+        sel_objects(h, 'v', 2, JQ_BW_T4Q), h->sel.bwd_wgs = three ? 3 : 1;
         return JQ_OK;
     }
 #define JQ_PICKCI(nt)                            \
     if (h->NT == nt && three) {                  \
         *fwd = k_forward_cq_imr<nt>;             \
         *bwd = k_backward_cq_imr3<nt>;           \
+        sel_objects(h, 'v', nt, JQ_BW_T4Q), h->sel.bwd_wgs = 3;   \
         return JQ_OK;                            \
     }
     JQ_PICKCI(1) JQ_PICKCI(2) JQ_PICKCI(3) JQ_PICKCI(4) JQ_PICKCI(5) JQ_PICKCI(6) JQ_PICKCI(7)
@@ -258,6 +283,7 @@ static int select_cq_imr_kernels(jq_handle* h, bool two, bool three, bool dense,
     if (h->NT == nt && two) {                    \
         *fwd = k_forward_cq_imr<nt>;             \
         *bwd = k_backward_cq_imr2<nt>;           \
+        sel_objects(h, 'v', nt, JQ_BW_T4Q), h->sel.bwd_wgs = 1, h->sel.imr_two = true;   \
         return JQ_OK;                            \
     }
     JQ_PICKCI(1) JQ_PICKCI(2) JQ_PICKCI(3) JQ_PICKCI(4) JQ_PICKCI(5) JQ_PICKCI(6)
@@ -266,6 +292,7 @@ static int select_cq_imr_kernels(jq_handle* h, bool two, bool three, bool dense,
     if (h->NT == nt) {                           \
         *fwd = k_forward_cq_imr<nt>;             \
         *bwd = k_backward_cq_imr<nt>;            \
+        sel_objects(h, 'v', nt, JQ_BW_T4Q), h->sel.bwd_wgs = 1;   \
         return JQ_OK;                            \
     }
     JQ_PICKCI(1) JQ_PICKCI(2) JQ_PICKCI(3) JQ_PICKCI(4) JQ_PICKCI(5) JQ_PICKCI(6) JQ_PICKCI(7)
@@ -291,6 +318,8 @@ static int select_quad_kernels(jq_handle* h, int spw, prop_kernel_t* fwd, prop_k
         *bwd = spw == 3 ? (ord ? (sc ? k_backward<nt, JQ_BW_T4Q, 3, false, false, true, true, true> : k_backward<nt, JQ_BW_T4Q, 3, false, false, true, true>) \
                                 : uni ? k_backward<nt, JQ_BW_T4Q, 3, false, false, true> : k_backward<nt, JQ_BW_T4Q, 3, false>)                 \
                         : spw == 2 ? k_backward<nt, JQ_BW_T4Q, 2, false> : k_backward<nt, JQ_BW_T4Q, 1, false>;  \
+        sel_objects(h, spw == 3 ? 'k' : 's', nt, JQ_BW_T4Q), h->sel.spw = spw == 3 ? 3 : spw == 2 ? 2 : 1;                                       \
+        h->sel.uni = spw == 3 && (ord || uni), h->sel.ord = spw == 3 && ord, h->sel.sc_fwd = sc, h->sel.sc_bwd = sc && ord;                      \
         return JQ_OK;                                                                                                                            \
     }
     JQ_PICKQ(1) JQ_PICKQ(2) JQ_PICKQ(3) JQ_PICKQ(4) JQ_PICKQ(5) JQ_PICKQ(6) JQ_PICKQ(7) JQ_PICKQ(8)
@@ -325,6 +354,8 @@ static int select_qsplit_kernel(jq_handle* h, int qw, prop_kernel_t* bwd)
     if (h->NT == nt) {                                                                                        \
         *bwd = qw == 4 ? (ride ? k_backward_qsplit<nt, true, 4, true> : ord ? k_backward_qsplit<nt, true, 4> : k_backward_qsplit<nt, false, 4>)             \
                        : (ride ? k_backward_qsplit<nt, true, 2, true> : ord ? k_backward_qsplit<nt, true, 2> : k_backward_qsplit<nt, false, 2>);            \
+        /* (the backward kernel of a plan whose forward kernel select_quad_kernels / select_cq_kernels has recorded) */                             \
+        sel_tag(h->sel.bwd, 'p', nt, JQ_BW_T4Q), h->sel.qs_qw = qw == 4 ? 4 : 2, h->sel.ord = ride || ord, h->sel.ride = ride, h->sel.uni = h->sel.sc_bwd = false, h->sel.bwd_wgs = 0;   \
         return JQ_OK;                                                                                         \
     }
     JQ_PICKQS(1) JQ_PICKQS(2) JQ_PICKQS(3) JQ_PICKQS(4) JQ_PICKQS(5) JQ_PICKQS(6)
@@ -344,6 +375,7 @@ static int select_quad_w_kernels(jq_handle* h, prop_kernel_t* fwd, prop_kernel_t
     if (h->NT == nt) {                                         \
         *fwd = k_forward<nt, JQ_BW_T4Q, 1, false, true>;       \
         *bwd = k_backward<nt, JQ_BW_T4Q, 1, false, true>;      \
+        sel_objects(h, 'w', nt, JQ_BW_T4Q), h->sel.spw = 1, h->sel.wlr = true;   \
         return JQ_OK;                                          \
     }
     JQ_PICKQW(1) JQ_PICKQW(2) JQ_PICKQW(3) JQ_PICKQW(4) JQ_PICKQW(5) JQ_PICKQW(6) JQ_PICKQW(7) JQ_PICKQW(8)
@@ -371,12 +403,15 @@ static int select_coop_kernels(jq_handle* h, prop_kernel_t* fwd, prop_kernel_t* 
 {
     if (h->huge) {
         *fwd = k_forward_huge, *bwd = k_backward_huge;
+        sel_objects(h, 'c', h->NT);      // (run-time sizes: compiled with the host code, no object of their own)
+        snprintf(h->sel.fwd, JQ_SEL_TAG, "host"), snprintf(h->sel.bwd, JQ_SEL_TAG, "host");
         return JQ_OK;
     }
 #define JQ_PICKC(nt, bw)                      \
     if (h->NT == nt && h->BWc == bw) {        \
         *fwd = k_forward_coop<nt, bw>;        \
         *bwd = k_backward_coop<nt, bw>;       \
+        sel_objects(h, 'c', nt, bw);          \
         return JQ_OK;                         \
     }
     JQ_FOR_EACH_COOP(JQ_PICKC)
@@ -405,6 +440,7 @@ static int select_lane_kernels(jq_handle* h, prop_kernel_t* fwd, prop_kernel_t* 
         *bwd = k_backward_lane<np>;      \
         *init = k_init_state_lane<np>;   \
         *term = k_terminal_lane<np>;     \
+        sel_objects(h, 'l', np);         \
         return JQ_OK;                    \
     }
     JQ_FOR_EACH_LANE(JQ_PICKL)
@@ -431,6 +467,7 @@ static int select_rowlane_kernels(jq_handle* h, int split, bool hist, prop_kerne
     if (h->rl_npj == npj) {                                                    \
         *fwd = h->wrank > 0 ? k_forward_rowlane<npj, true, true> : hist ? k_forward_rowlane<npj, false, true> : k_forward_rowlane<npj>;     \
         *bwd = h->wrank > 0 ? k_backward_rowlane<npj, true> : split == 3 ? k_backward_rowlane3<npj> : split == 2 ? k_backward_rowlane2<npj> : k_backward_rowlane<npj>;     \
+        sel_objects(h, 'r', npj), h->sel.wlr = h->wrank > 0;                   \
         return JQ_OK;                                                          \
     }
     JQ_FOR_EACH_ROWLANE(JQ_PICKR)
@@ -451,6 +488,7 @@ static int select_rowlane_imr_kernels(jq_handle* h, bool split, prop_kernel_t* f
     if (h->rl_npj == npj) {                                                            \
         *fwd = k_forward_rowlane_imr<npj>;                                             \
         *bwd = split ? k_backward_rowlane_imr2<npj> : k_backward_rowlane_imr<npj>;     \
+        sel_objects(h, 'm', npj), h->sel.imr_two = split;                              \
         return JQ_OK;                                                                  \
     }
     JQ_FOR_EACH_ROWLANE(JQ_PICKM)
@@ -485,12 +523,14 @@ static int select_coop_imr_parts_kernels(jq_handle* h, bool hbm, prop_kernel_t* 
     if (hbm) {
         *fwd = k_forward_coop_imr_parts<6, 5, true>;
         *bwd = k_backward_coop_imr_parts<6, 5, true>;
+        sel_objects(h, 'i', 6, 5);
         return JQ_OK;
     }
 #define JQ_PICKCIP(nt, bw)                                      \
     if (h->NT == nt && h->BWc == bw) {                          \
         *fwd = k_forward_coop_imr_parts<nt, bw, (nt > 6)>;      \
         *bwd = k_backward_coop_imr_parts<nt, bw, (nt > 6)>;     \
+        sel_objects(h, 'i', nt, bw);                            \
         return JQ_OK;                                           \
     }
     JQ_FOR_EACH_COOP(JQ_PICKCIP)
@@ -504,12 +544,14 @@ static int select_coop_imr_kernels(jq_handle* h, bool hbm, prop_kernel_t* fwd, p
     if (hbm) {
         *fwd = k_forward_coop_imr<6, 5, true>;
         *bwd = k_backward_coop_imr<6, 5, true>;
+        sel_objects(h, 'i', 6, 5);
         return JQ_OK;
     }
 #define JQ_PICKCI(nt, bw)                                 \
     if (h->NT == nt && h->BWc == bw) {                    \
         *fwd = k_forward_coop_imr<nt, bw, (nt > 6)>;      \
         *bwd = k_backward_coop_imr<nt, bw, (nt > 6)>;     \
+        sel_objects(h, 'i', nt, bw);                      \
         return JQ_OK;                                     \
     }
     JQ_FOR_EACH_COOP(JQ_PICKCI)

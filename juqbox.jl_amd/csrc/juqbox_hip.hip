@@ -52,8 +52,22 @@ static bool debug_timing()
 // "max_agprs": .., "max_scratch_bytes": ..}, ...} -- flat entries, quoted by jq_plan_info
 extern "C" const char jq_build_manifest[];
 
+// Which instantiation the tables of jq_host_select.h chose for a batch: the objects (csrc/Makefile tags) of the forward and the backward
+// kernel and the compile-time variant.  select_* fill jq_handle::sel, plan_batch keeps it in its BatchPlan, run_eval publishes the plan's
+// record as jq_handle::last_kernels once the evaluation is through (jq_plan_info "last_kernels").
+#define JQ_SEL_TAG 12
+struct KernelSel {
+    bool set = false;
+    char fwd[JQ_SEL_TAG] = "", bwd[JQ_SEL_TAG] = "";
+    int spw = 0;                // quad layout: slabs per workgroup (0: another family)
+    int qs_qw = 0;              // k_backward_qsplit: column quads per workgroup (0: not taken)
+    int bwd_wgs = 0;            // cooperative quad: workgroups per column quad in the backward sweep (0: another family)
+    bool uni = false, ord = false, sc_fwd = false, sc_bwd = false, ride = false, modd = false, fwd2 = false, wlr = false, imr_two = false;
+};
+
 struct jq_handle {
     int device = 0;
+    KernelSel sel, last_kernels;      // (sel: scratch of the select_* call in flight)
     JqOptions opt;              // per-handle options (jq_options.h): jq_create_opts / JQ_OPTIONS / jq_set_option
     hipStream_t stream = nullptr;
     // problem

@@ -283,7 +283,9 @@ class Working_Arrays_HIP:
         return _lib.load().jq_rccl_world_size(self.handle)
 
     def plan_info(self):
-        """jq_plan_info: structure found in the operators, control groups, batch-size thresholds of the kernel families (dict)"""
+        """jq_plan_info: structure found in the operators, control groups, batch-size thresholds of the kernel families and, under
+        "last_kernels", the instantiation the last evaluation ran (object tags, slabs / quads per workgroup, variant flags; None before the
+        first evaluation) (dict)"""
         import json
         L = _lib.load()
         n = L.jq_plan_info(self.handle, None, 0)

@@ -98,11 +98,10 @@ def kind_of(route):
 
 
 # ---- the CPU oracle's side: one reference per (problem, solver), shared by the cells that need it ------------------------------------------
-def _reference(jq, NT, code, Ntot, kind):
+def oracle_reference(jq, prob, kind, sparse):
+    """{"single", "ensemble"} of a Problem under the solver settings of `kind` (shared with tests/structured_matrix.py)"""
     from oracle.oracle import Oracle
-    prob = problem(jq, NT, code, Ntot)
     p = with_solver(jq, prob.p, kind)
-    sparse = generator_band(NT, code) < NT - 1      # (storage only: the oracle multiplies over the nonzero pattern in both forms)
     orc = Oracle(p, use_sparse=sparse)
     if kind != "imr":
         return {"single": orc.traceobjgrad(prob.pcof, history=True),
@@ -117,23 +116,41 @@ def _reference(jq, NT, code, Ntot, kind):
     return {"single": orc.traceobjgrad_imr(prob.pcof, 60, 1e-11, history=True), "ensemble": {"last_infidelity": inf, "last_infidelity_grad": g}}
 
 
-_pool, _futures = None, {}
+def _reference(jq, NT, code, Ntot, kind):
+    # (sparse is storage only: the oracle multiplies over the nonzero pattern in both forms)
+    return oracle_reference(jq, problem(jq, NT, code, Ntot), kind, generator_band(NT, code) < NT - 1)
+
+
+class ReferencePool:
+    """The first request starts every reference of a matrix on a few threads (the oracle is C behind ctypes and holds no global
+    state; the largest problems take seconds each); every cell then waits for its own only.  jobs(): (key, function, arguments) in the
+    order the cells run; a key asked for that jobs() did not name is computed on the spot by missing(key)."""
+    def __init__(self, jobs, missing=None):
+        self.jobs, self.missing, self.pool, self.futures = jobs, missing, None, {}
+
+    def result(self, key):
+        if self.pool is None:
+            from oracle import oracle
+            oracle.lib()      # (loaded before the threads start)
+            pool = self.pool = concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(12, (os.cpu_count() or 2) - 1)))
+            atexit.register(lambda: pool.shutdown(wait=False, cancel_futures=True))
+            for k, fn, args in self.jobs():
+                if k not in self.futures:
+                    self.futures[k] = pool.submit(fn, *args)
+        if key not in self.futures:
+            self.futures[key] = self.pool.submit(*self.missing(key))
+        return self.futures[key].result()
+
+
+_pool = None
 
 
 def reference(jq, cell, Ntot):
-    """The first request starts every reference of the matrix on a few threads (the oracle is C behind ctypes and holds no global
-    state; the largest problems take seconds each); every cell then waits for its own only."""
     global _pool
     if _pool is None:
-        from oracle import oracle
-        oracle.lib()      # (loaded before the threads start)
-        _pool = concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(12, (os.cpu_count() or 2) - 1)))
-        atexit.register(lambda: _pool.shutdown(wait=False, cancel_futures=True))
-        for c, nt in CASES:      # (in the order the cells run)
-            key = (c.code, nt, kind_of(c.route))
-            if c.tag is not None and key not in _futures:
-                _futures[key] = _pool.submit(_reference, jq, c.NT, c.code, nt, key[2])
-    return _futures[cell.code, Ntot, kind_of(cell.route)].result()
+        _pool = ReferencePool(lambda: [((c.code, nt, kind_of(c.route)), _reference, (jq, c.NT, c.code, nt, kind_of(c.route)))
+                                       for c, nt in CASES if c.tag is not None])
+    return _pool.result((cell.code, Ntot, kind_of(cell.route)))
 
 
 # ---- the GPU's side ----------------------------------------------------------------------------------------------------------------------
@@ -189,10 +206,15 @@ def exact(out):
             "ensemble": [hx(v) for v in out["ensemble"]]}
 
 
-if __name__ == "__main__":
+def dump_main(runs):
+    """python tests/<matrix>.py OUT.json: runs() -> (id, result of run_cell) through the library named by JQ_LIB, every number in exact form"""
     import json
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import juqbox_jl_amd
-    dump = {cell_id(c, nt): exact(run_cell(juqbox_jl_amd, c, nt)) for c, nt in CASES if c.NT <= 6 and c.tag is not None}
+    dump = {k: exact(out) for k, out in runs(juqbox_jl_amd)}
     with open(sys.argv[1], "w") as f:
         json.dump(dump, f)
+
+
+if __name__ == "__main__":
+    dump_main(lambda jq: ((cell_id(c, nt), run_cell(jq, c, nt)) for c, nt in CASES if c.NT <= 6 and c.tag is not None))

@@ -12,7 +12,7 @@ import block_band_matrix as M
 from block_band_problem import block_band, tile_rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STRUCTURE_CODES = {"7", "8", "9"}      # JQ_BW_T4Q, JQ_BW_T4, JQ_BW_OD: covered by the structured generators of tests/test_gpu_random.py
+STRUCTURE_CODES = {"7", "8", "9"}      # JQ_BW_T4Q, JQ_BW_T4, JQ_BW_OD: the structured matrix (tests/structured_matrix.py, tests/test_structured_matrix.py)
 
 
 def makefile_lists():
