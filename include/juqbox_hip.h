@@ -44,7 +44,9 @@ extern "C" {
  * 6 = continuation adjoints: jq_update_dvds, jq_set_sv_type, jq_get_sv_type (params.dVds_r / dVds_i / sv_type); later, with no
  *     change of a layout or of an existing entry point: jq_s_uniform (host-only structure test), jq_traceobjgrad_batch (many control
  *     vectors of one problem in one call), jq_eval_f_g_grad_batch (many control vectors x the nodes of one ensemble in one call),
- *     jq_traceobjgrad_drifts / jq_eval_f_g_grad_drifts (one control vector over an ensemble of arbitrary drift Hamiltonians in one call). */
+ *     jq_traceobjgrad_drifts / jq_eval_f_g_grad_drifts (one control vector over an ensemble of arbitrary drift Hamiltonians in one call),
+ *     jq_traceobjgrad_members / jq_eval_f_g_grad_members (... over members that differ in their drift, in a real mixing matrix of the
+ *     controls -- amplitude miscalibration, crosstalk -- or in both). */
 #define JQ_ABI_VERSION 6
 
 #define JQ_MAX_CONTROLS 16 /* control Hamiltonians the fast kernels hold in registers; more: cooperative kernels (no limit)    */
@@ -438,6 +440,44 @@ int jq_traceobjgrad_drifts(jq_handle *h, const double *pcof, int32_t ncoeff, con
 int jq_eval_f_g_grad_drifts(jq_handle *h, const double *pcof, int32_t ncoeff, const double *Hconsts, const double *weights,
                             int32_t ndrift, int32_t compute_adjoint, double *out2, double *infid_grad, double *leak_grad,
                             double *member_out);
+
+/*
+ * Ensembles over uncertainty in the DRIVE: nmember evaluations of ONE control vector whose member i has a real Nc x Nc mixing matrix
+ * C_i of the controls and, optionally, its own drift.  The controls keep their carriers and spline coefficients; what reaches operator
+ * l is
+ *     p~_l(t) = sum_k C_i[l, k] p_k(t),   q~_l(t) = sum_k C_i[l, k] q_k(t),
+ *     H_i(t) = Hconst_i + sum_l p~_l(t) Hsym_l + i sum_l q~_l(t) Hanti_l
+ * -- the plain problem whose operators are Hsym'_k = sum_l C_i[l, k] Hsym_l, Hanti'_k = sum_l C_i[l, k] Hanti_l.  A miscalibrated
+ * amplitude of line k (p_k, q_k arrive scaled by 1 + delta_k) is C = diag(1 + delta); control lines that leak into each other
+ * (crosstalk) are the off-diagonal entries; C = I is jq_traceobjgrad.  Uncoupled controls: the mix acts on their functions
+ * ft_k(t) alike.  A complex (phase-carrying) crosstalk matrix is not served.
+ * ctrl_mix: [Nc x Nc x nmember] column-major, element (l, k) of member i at l + Nc * k + Nc * Nc * i, or NULL: identity for every member.
+ * Hconsts: [Ntot x Ntot x nmember] as for jq_traceobjgrad_drifts, or NULL: the handle's drift for every member.  Not both NULL.
+ * Outputs: exactly those of jq_traceobjgrad_drifts, one column per member; the gradient is that with respect to the caller's
+ * coefficients (the block of control k collects sum_l C_i[l, k] times what operator l contributes, with k's own carrier).
+ * Zero entries of a mix are skipped, not multiplied: C = I returns the bits of the unmixed evaluation, and a zero column k of C an
+ * exactly zero gradient block of control k.
+ * Only two small kernels see the mix -- the one that evaluates the control functions of a chunk and the one that sums the trace records
+ * the gradient is assembled from; no operator image, tile stream or time-loop kernel differs from jq_traceobjgrad_drifts'.  Routing is
+ * that call's: grouped on the row-lane and cooperative-quad kernels (the members share launches, through the embedded twin as well),
+ * member after member on every other route -- there with the member's mix on the single evaluation, no operator is swapped for a mix,
+ * the drift (if given) as in jq_traceobjgrad_drifts.  Column i is bit-identical to the same member evaluated alone (nmember == 1) on
+ * the same kernel variant and chunk length.  Hconsts != NULL: planning as in jq_traceobjgrad_drifts.  jq_plan_info: "member_batch"
+ * (the fields of "drift_batch" and the booleans "drifts", "ctrl_mix"; the two drifts calls report there as well).
+ * Errors: JQ_EINVAL for NULL required pointers, Hconsts and ctrl_mix both NULL, nmember < 1 and a mix entry that is not finite; the
+ * single call's codes for the coefficient count; a refused call writes nothing and leaves the handle as it was.  Multi-device handles
+ * shard the MEMBERS (jq_shard_bounds).  jq_traceobjgrad_drifts / jq_eval_f_g_grad_drifts are the ctrl_mix == NULL case of this call.
+ */
+int jq_traceobjgrad_members(jq_handle *h, const double *pcof, int32_t ncoeff, const double *Hconsts, const double *ctrl_mix,
+                            int32_t nmember, int32_t evaladjoint, double *out4, double *totalgrad, double *infidelgrad,
+                            double *leakgrad);
+/*
+ * The weighted sums of jq_eval_f_g_grad_drifts over the members of jq_traceobjgrad_members (weights: [nmember]; formed on the host in
+ * member order; member_out: [4 x nmember] or NULL, bit-identical to out4 of jq_traceobjgrad_members).
+ */
+int jq_eval_f_g_grad_members(jq_handle *h, const double *pcof, int32_t ncoeff, const double *Hconsts, const double *ctrl_mix,
+                             const double *weights, int32_t nmember, int32_t compute_adjoint, double *out2, double *infid_grad,
+                             double *leak_grad, double *member_out);
 
 /*
  * The same evaluation with the result left ON THE DEVICE for a caller that runs its own collective (one process per GPU:

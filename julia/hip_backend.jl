@@ -415,6 +415,63 @@ function eval_f_g_grad_drifts!(pcof::Vector{Float64}, params::objparams, wa::Abs
     return per_member ? member_out : nothing
 end
 
+# ONE control vector over members that differ in a real Nc x Nc mixing matrix of the controls -- operator l is driven by
+# sum_k ctrl_mix[l, k, i] (p_k, q_k): diag(1 + delta) is a miscalibrated amplitude, off-diagonal entries are crosstalk -- and, optionally,
+# in their drift (jq_traceobjgrad_members).  Hconsts / ctrl_mix: `nothing` stands for the drift of params / the identity; not both.
+# Returns what traceobjgrad_drifts returns, one column per member.
+function traceobjgrad_members(pcof::Vector{Float64}, params::objparams, wa::AbstractWorkingArraysHIP,
+                              Hconsts::Union{Nothing,Array{Float64,3}}, ctrl_mix::Union{Nothing,Array{Float64,3}}, evaladjoint::Bool = true)
+    Ntot = params.N + params.Nguard
+    Nc = max(params.Ncoupled, params.Nunc)
+    (Hconsts === nothing && ctrl_mix === nothing) && throw(ArgumentError("traceobjgrad_members: give Hconsts, ctrl_mix or both"))
+    n = ctrl_mix === nothing ? size(Hconsts, 3) : size(ctrl_mix, 3)
+    n >= 1 || throw(ArgumentError("traceobjgrad_members: need at least one member"))
+    Hconsts === nothing || (size(Hconsts) == (Ntot, Ntot, n)) || throw(ArgumentError("traceobjgrad_members: Hconsts must be Ntot x Ntot x nmember"))
+    ctrl_mix === nothing || (size(ctrl_mix) == (Nc, Nc, n)) || throw(ArgumentError("traceobjgrad_members: ctrl_mix must be Nc x Nc x nmember"))
+    sync!(wa, params)
+    ncoeff = length(pcof)
+    out4 = zeros(4, n)
+    tg = zeros(ncoeff, evaladjoint ? n : 0); ig = similar(tg); lg = similar(tg)
+    jqcheck(wa, ccall((:jq_traceobjgrad_members, libjq), Cint,
+                      (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                      wa.handle, pcof, ncoeff, Hconsts === nothing ? C_NULL : pointer(Hconsts), ctrl_mix === nothing ? C_NULL : pointer(ctrl_mix),
+                      n, evaladjoint ? 1 : 0, out4,
+                      evaladjoint ? pointer(tg) : C_NULL, evaladjoint ? pointer(ig) : C_NULL, evaladjoint ? pointer(lg) : C_NULL))
+    evaladjoint || return out4[1, :], out4[2, :], out4[3, :]
+    return out4[1, :], tg, out4[2, :], out4[3, :], out4[4, :], ig, (params.objFuncType == 1 ? zeros(0, n) : lg)
+end
+
+# eval_f_g_grad_drifts! over the members of traceobjgrad_members (jq_eval_f_g_grad_members): the weighted sums land in params.last_*
+# exactly as eval_f_g_grad! leaves them; per_member = true also returns the 4 x nmember array of the members' records.
+function eval_f_g_grad_members!(pcof::Vector{Float64}, params::objparams, wa::AbstractWorkingArraysHIP,
+                                Hconsts::Union{Nothing,Array{Float64,3}}, ctrl_mix::Union{Nothing,Array{Float64,3}},
+                                weights::AbstractArray, compute_adjoint::Bool = true; per_member::Bool = false)
+    Ntot = params.N + params.Nguard
+    Nc = max(params.Ncoupled, params.Nunc)
+    (Hconsts === nothing && ctrl_mix === nothing) && throw(ArgumentError("eval_f_g_grad_members!: give Hconsts, ctrl_mix or both"))
+    nm = ctrl_mix === nothing ? size(Hconsts, 3) : size(ctrl_mix, 3)
+    wt = collect(Float64, weights)
+    nm >= 1 || throw(ArgumentError("eval_f_g_grad_members!: need at least one member"))
+    Hconsts === nothing || (size(Hconsts) == (Ntot, Ntot, nm)) || throw(ArgumentError("eval_f_g_grad_members!: Hconsts must be Ntot x Ntot x nmember"))
+    ctrl_mix === nothing || (size(ctrl_mix) == (Nc, Nc, nm)) || throw(ArgumentError("eval_f_g_grad_members!: ctrl_mix must be Nc x Nc x nmember"))
+    length(wt) == nm || throw(ArgumentError("eval_f_g_grad_members!: need one weight per member"))
+    sync!(wa, params)
+    n = length(pcof)
+    out2 = zeros(2); ig = zeros(n); lg = zeros(n)
+    member_out = zeros(4, per_member ? nm : 0)
+    jqcheck(wa, ccall((:jq_eval_f_g_grad_members, libjq), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        wa.handle, pcof, n, Hconsts === nothing ? C_NULL : pointer(Hconsts), ctrl_mix === nothing ? C_NULL : pointer(ctrl_mix), wt, nm,
+        compute_adjoint ? 1 : 0, out2, ig, lg, per_member ? pointer(member_out) : C_NULL))
+    params.last_pcof .= pcof
+    params.last_infidelity, params.last_leak = out2
+    params.last_infidelity_grad .= compute_adjoint ? ig : 0.0
+    length(params.last_leak_grad) > 0 && (params.last_leak_grad .= compute_adjoint ? lg : 0.0)
+    params.lastTraceInfidelity = params.last_infidelity
+    params.lastLeakIntegral = params.last_leak
+    return per_member ? member_out : nothing
+end
+
 # One process per GPU (MPI.jl): each rank evaluates its shard and leaves the packed sums on its device; the caller
 # all-reduces `d_packed` (2 + 2 nCoeff doubles on the GPU, e.g. a ROCArray) over the ranks.
 function shard_bounds(nquad::Integer, rank::Integer, world::Integer)

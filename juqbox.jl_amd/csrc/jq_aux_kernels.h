@@ -71,25 +71,47 @@ __device__ __forceinline__ double stream_time(const double* tt, int n0, int j, d
 // pq[j][2*Ncoupled] = (p_1, q_1, p_2, q_2, ...)(t_j)   -- KS!'s controlfunc calls (src/evalobjgrad.jl:2366-2367)
 // grid.y = control vectors of a grouped batch (jq_traceobjgrad_batch): vector g reads the coefficient block g of s.pcof and writes the
 // pq block g ([g][ntp][2 Ncoupled]); one vector is the launch it always was
-__global__ void k_ctrl(SplineArgs s, const double* tt, int n0, int ntp, double h, double* pq)
+// mix (jq_traceobjgrad_members; nullptr: none, the launch it always was): [groups][Ncoupled x Ncoupled] column-major real mixing matrices.
+// What reaches operator l of group g is sum_k C_g[l, k] (p_k, q_k) -- every control keeps its own carriers and coefficients.  The thread
+// parks its unmixed values in row j of `raw` (the layout of pq; read back by the thread that wrote them) and writes the mixed ones to pq.
+// Zero entries of C are skipped and the first term is the product alone, so C = I writes the bits of the unmixed launch.
+__global__ void k_ctrl(SplineArgs s, const double* tt, int n0, int ntp, double h, double* pq, const double* __restrict__ mix, double* raw)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= ntp) return;
+    const int Nc = s.Ncoupled;
     s.pcof += (size_t)blockIdx.y * s.nCoeff;
-    pq += (size_t)blockIdx.y * ntp * 2 * s.Ncoupled;
+    pq += ((size_t)blockIdx.y * ntp + j) * 2 * Nc;
+    double* const val = mix ? raw + ((size_t)blockIdx.y * ntp + j) * 2 * Nc : pq;      // (the unmixed values of this time point)
     const double t = stream_time(tt, n0, j, h);
     if (s.rfreq) {
         // uncoupled controls (src/evalobjgrad.jl:2373-2387): ft = 2 (p cos(2 pi Rfreq t) - q sin(2 pi Rfreq t)) multiplies
         // Hunc_ops[q], which sits in the symmetric OR the antisymmetric slot of pair q (the other slot is zero)
-        for (int q = 0; q < s.Ncoupled; ++q) {
+        for (int q = 0; q < Nc; ++q) {
             const double pt = bcarrier2_dev(s, t, 2 * q), qt = bcarrier2_dev(s, t, 2 * q + 1);
             const double ft = 2.0 * (pt * cos(2.0 * M_PI * s.rfreq[q] * t) - qt * sin(2.0 * M_PI * s.rfreq[q] * t));
-            pq[(size_t)j * 2 * s.Ncoupled + 2 * q] = ft;
-            pq[(size_t)j * 2 * s.Ncoupled + 2 * q + 1] = ft;
+            val[2 * q] = ft;
+            val[2 * q + 1] = ft;
         }
-        return;
+    } else {
+        for (int f = 0; f < 2 * Nc; ++f) val[f] = bcarrier2_dev(s, t, f);
     }
-    for (int f = 0; f < 2 * s.Ncoupled; ++f) pq[(size_t)j * 2 * s.Ncoupled + f] = bcarrier2_dev(s, t, f);
+    if (!mix) return;
+    const double* C = mix + (size_t)blockIdx.y * Nc * Nc;
+    for (int l = 0; l < Nc; ++l) {
+        double pm = 0.0, qm = 0.0;
+        bool first = true;
+        for (int k = 0; k < Nc; ++k) {
+            const double c = C[l + Nc * k];
+            if (c == 0.0) continue;
+            const double pk = c * val[2 * k], qk = c * val[2 * k + 1];
+            pm = first ? pk : pm + pk;
+            qm = first ? qk : qm + qk;
+            first = false;
+        }
+        pq[2 * l] = pm;
+        pq[2 * l + 1] = qm;
+    }
 }
 
 // KS!: K = Hconst + sum_q p_q Hsym_q ; S = sum_q q_q Hanti_q  (src/evalobjgrad.jl:2354-2370), evaluated
@@ -367,12 +389,38 @@ __global__ void k_terminal_imr(double* state, long long stride, const double* __
 // R[m][k] = sum_slab traces[slab][m][k] in slab order (deterministic).  thread per (m,k)
 // Grouped batch: grid.y = control vectors, `nslabs` = trace rows of ONE vector; R[g][m][k] sums the rows g nslabs .. (g + 1) nslabs - 1 in
 // row order -- the order a single evaluation of that vector sums them in.
-__global__ void k_trace_reduce(const double* __restrict__ traces, int nslabs, int nsteps_chunk, int ntr, double* R)
+// mix (jq_traceobjgrad_members; nullptr: none, the launch it always was): [groups][Nc x Nc] column-major mixing matrices C, and the sweep
+// computed the traces of the operators [q0, q0 + ntr / JQ_NTR).  R then holds rows for ALL Nc controls, [g][m][Nc][JQ_NTR]: the row of
+// control k is sum_{l in the sweep's group} C[l, k] (row of operator l) -- by linearity what k_gradacc needs to assemble the gradient of k's
+// coefficients with k's own carrier and spline window (launched with q0 = 0, ng = Nc), the other operator groups add theirs in their
+// sweeps.  Zero entries of C are skipped and the first term is the product alone: C = I gives the unmixed rows bit for bit and exact
+// zeros elsewhere; a zero column of C an exactly zero gradient block.   thread per (m, control, scalar), grid.x sized for Nc controls
+__global__ void k_trace_reduce(const double* __restrict__ traces, int nslabs, int nsteps_chunk, int ntr, double* R,
+                               const double* __restrict__ mix, int Nc, int q0)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long tot = (long long)nsteps_chunk * ntr;
-    if (i >= tot) return;
     traces += (size_t)blockIdx.y * nslabs * tot;
+    if (mix) {
+        const long long tot_out = (long long)nsteps_chunk * Nc * JQ_NTR;
+        if (i >= tot_out) return;
+        const int m = (int)(i / (Nc * JQ_NTR)), rem = (int)(i - (long long)m * Nc * JQ_NTR);
+        const int k = rem / JQ_NTR, t = rem - k * JQ_NTR;
+        const double* C = mix + (size_t)blockIdx.y * Nc * Nc + (size_t)Nc * k + q0;      // column k, rows q0 ..
+        double acc = 0.0;
+        bool first = true;
+        for (int l = 0; l < ntr / JQ_NTR; ++l) {
+            const double c = C[l];
+            if (c == 0.0) continue;
+            double s = 0.0;
+            for (int sl = 0; sl < nslabs; ++sl) s += traces[(size_t)sl * tot + (size_t)m * ntr + l * JQ_NTR + t];
+            acc = first ? c * s : acc + c * s;
+            first = false;
+        }
+        R[(size_t)blockIdx.y * tot_out + i] = acc;
+        return;
+    }
+    if (i >= tot) return;
     R += (size_t)blockIdx.y * tot;
     double s = 0.0;
     for (int sl = 0; sl < nslabs; ++sl) s += traces[(size_t)sl * tot + i];

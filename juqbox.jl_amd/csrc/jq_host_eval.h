@@ -17,6 +17,10 @@ struct EvalRequest {
     // drift ensemble (jq_traceobjgrad_drifts): HOST array [Ntot x Ntot x groups] of member drifts (NULL: none), a grouped batch whose groups
     // share ONE control vector (pcof: ncoeff coefficients) and differ in image 0 of their tile stream
     const double* drifts = nullptr;
+    // control mixes (jq_traceobjgrad_members): HOST array [Nc x Nc x max(groups, 1)] column-major (NULL: none) -- what reaches operator l of
+    // group g is sum_k C_g[l, k] (p_k, q_k).  In a grouped batch the groups share ONE control vector, as with drifts; without groups it is
+    // the mix of the single evaluation.  Only k_ctrl and k_trace_reduce see it.
+    const double* mix = nullptr;
     bool split_part = false;        // one part of a split batch: not split again
 };
 struct EvalOut {
@@ -193,6 +197,7 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
             for (int g = 0; g < G; ++g) embed_matrix(rq.drifts + (size_t)g * nn, h->Ntot, h->emb_row, e->Ntot, ed.data() + (size_t)g * ne);
             er.drifts = ed.data();
         }
+        // (er.mix: the caller's, unchanged -- the twin has the same controls)
         const int rc = run_eval(e, er, out);
         if (rc != JQ_OK) h->err = e->err;
         h->timing = e->timing;
@@ -231,6 +236,11 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
         if ((rc = dev_grow(h, &h->d_pq, &h->cap_pq, (size_t)G * (2 * p.cs + 1) * 2 * h->Nc))) return rc;
         if (adjoint && (rc = dev_grow(h, &h->d_R, &h->cap_R, (size_t)G * p.cs * h->NcK * JQ_NTR))) return rc;
     }
+    const size_t ncnc = (size_t)h->Nc * h->Nc;
+    if (rq.mix) {      // (the mixes, k_ctrl's unmixed values in the layout of d_pq, trace rows for ALL controls per group)
+        if ((rc = dev_grow(h, &h->d_mix, &h->cap_mix, (size_t)nvec * ncnc + (size_t)nvec * (2 * p.cs + 1) * 2 * h->Nc))) return rc;
+        if (adjoint && (rc = dev_grow(h, &h->d_R, &h->cap_R, (size_t)nvec * p.cs * h->Nc * JQ_NTR))) return rc;
+    }
     if (p.state_doubles > h->cap_state || !h->d_state || !h->d_state_save) {
         h->cap_state = 0;
         if ((rc = dev_alloc(h, &h->d_state, p.state_doubles))) return rc;
@@ -256,10 +266,12 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     // ---- inputs --------------------------------------------------------------------------------
     hipStream_t s = h->stream;
     std::vector<double> gpcof, dimg;
-    if (rq.drifts) {
-        // one control vector for every group: its block replicated (k_ctrl, k_gradacc stay the launches of a control-vector batch), and the
-        // members' drift images in the planned family's layout -- the builders and the bits of upload_operators' image 0
+    const bool one_vector = G > 0 && (rq.drifts || rq.mix);      // (an ensemble's members share ONE control vector)
+    // one control vector for every group: its block replicated (k_ctrl, k_gradacc stay the launches of a control-vector batch)
+    if (one_vector)
         for (int g = 0; g < G; ++g) gpcof.insert(gpcof.end(), pcof, pcof + ncoeff);
+    if (rq.drifts) {
+        // the members' drift images in the planned family's layout -- the builders and the bits of upload_operators' image 0
         const size_t nn = (size_t)h->Ntot * h->Ntot;
         dimg.assign((size_t)G * (size_t)p.stride, 0.0);
         for (int g = 0; g < G; ++g) {
@@ -275,7 +287,10 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     }
     const double* const h0img = rq.drifts ? h->d_drift : p.himg;      // image 0 of group 0 and the stride to the next group's
     const long long h0_gstride = rq.drifts ? p.stride : 0;
-    HIPCHK(h, hipMemcpyAsync(h->d_pcof, rq.drifts ? gpcof.data() : pcof, (size_t)nvec * ncoeff * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->d_pcof, one_vector ? gpcof.data() : pcof, (size_t)nvec * ncoeff * sizeof(double), hipMemcpyHostToDevice, s));
+    if (rq.mix) HIPCHK(h, hipMemcpyAsync(h->d_mix, rq.mix, (size_t)nvec * ncnc * sizeof(double), hipMemcpyHostToDevice, s));
+    const double* const d_mix = rq.mix ? h->d_mix : nullptr;
+    double* const d_pqraw = rq.mix ? h->d_mix + (size_t)nvec * ncnc : nullptr;
     bool use_shift = false;
     std::vector<double> colinfo(p.colinfo_doubles, 0.0);
     if (p.layout != SL_SLABS) {   // [eps per column slot | weight per column slot]  (lane kernels: cpw = 4, one slot per column)
@@ -361,7 +376,7 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     for (int n0 = 0; n0 < h->nsteps; n0 += p.cs) {
         const int nc = std::min(p.cs, h->nsteps - n0);
         const int ntp = 2 * nc + 1;
-        hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, sp, h->d_tf, n0, ntp, dt, h->d_pq);
+        hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, sp, h->d_tf, n0, ntp, dt, h->d_pq, d_mix, d_pqraw);
         hipLaunchKernelGGL(k_stream, dim3((unsigned)((p.stride + 255) / 256), ntp, nvec), dim3(256), 0, s, p.himg, h0img, h0_gstride,
                            h->d_pq, h->Nc, p.stride, 0.5 * dt, h->d_stream, (long long)gstride);
         a.nsteps_chunk = nc; a.step0 = n0; a.first_chunk = (n0 == 0); a.h = dt; a.forced = 1;
@@ -429,7 +444,7 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
             for (int n0 = 0; n0 < h->nsteps; n0 += p.cs) {
                 const int nc = std::min(p.cs, h->nsteps - n0);
                 const int ntp = 2 * nc + 1;
-                hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, sp, h->d_tb, n0, ntp, -dt, h->d_pq);
+                hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, sp, h->d_tb, n0, ntp, -dt, h->d_pq, d_mix, d_pqraw);
                 hipLaunchKernelGGL(k_stream, dim3((unsigned)((p.stride + 255) / 256), ntp, nvec), dim3(256), 0, s, p.himg, h0img,
                                    h0_gstride, h->d_pq, h->Nc, p.stride, -0.5 * dt, h->d_stream, (long long)gstride);
                 a.nsteps_chunk = nc; a.step0 = n0; a.first_chunk = (n0 == 0); a.h = -dt; a.forced = (pass == 0);
@@ -486,11 +501,13 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
                     }
                 }
                 // (grouped batch: per vector its own trace rows -- p.upg of them, the padding rows of the last slab belong to nobody -- and its own gradient)
-                hipLaunchKernelGGL(k_trace_reduce, dim3((unsigned)(((long long)nc * ntr_g + 255) / 256), nvec), dim3(256), 0, s,
-                                   h->d_traces, G > 0 ? p.upg : p.trace_rows, nc, ntr_g, h->d_R);
+                // (control mixes: the rows of the sweep's operators become rows for ALL controls, and the assembly covers all of them)
+                const int ntr_R = d_mix ? h->Nc * JQ_NTR : ntr_g;
+                hipLaunchKernelGGL(k_trace_reduce, dim3((unsigned)(((long long)nc * ntr_R + 255) / 256), nvec), dim3(256), 0, s,
+                                   h->d_traces, G > 0 ? p.upg : p.trace_rows, nc, ntr_g, h->d_R, d_mix, h->Nc, q0);
                 // gradbcarrier2! as a scatter: one workgroup per coefficient of the group's controls
-                hipLaunchKernelGGL(k_gradacc, dim3(ng * 2 * h->Nfreq * D1, nvec), dim3(JQ_GRADACC_THREADS), 0, s, sp, h->d_R, h->d_tb, n0, nc, -dt,
-                                   h->d_grad + (size_t)pass * ncoeff, q0, ng, (long long)2 * ncoeff);
+                hipLaunchKernelGGL(k_gradacc, dim3((d_mix ? h->Nc : ng) * 2 * h->Nfreq * D1, nvec), dim3(JQ_GRADACC_THREADS), 0, s, sp, h->d_R, h->d_tb, n0, nc, -dt,
+                                   h->d_grad + (size_t)pass * ncoeff, d_mix ? 0 : q0, d_mix ? h->Nc : ng, (long long)2 * ncoeff);
                 mfma += (long long)p.nslabs * nc * (2 * (8 + 2 * h->m) * p.tiles + 4 * trace_tiles);
                 if (n0 == 0) mfma += (long long)p.nslabs * trace_tiles;
             }

@@ -171,6 +171,10 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
     // stream of its own member's drift) or "sequential" (the handle's operator images swapped per member for the single evaluation), and why
     kv("drift_batch", std::string("{\"mode\": \"") + (h->db_mode.empty() ? "none yet" : h->db_mode) + "\", \"family\": " + num(h->db_family) + ", \"members_per_launch\": " + num(h->db_per_launch) +
                           ", \"reason\": \"" + h->db_why + "\"}");
+    // the last member ensemble of any kind (jq_traceobjgrad_members / jq_eval_f_g_grad_members and the two drifts calls): the fields of
+    // "drift_batch", and what differed between its members -- their drifts, their control mixes
+    kv("member_batch", std::string("{\"mode\": \"") + (h->mb_mode.empty() ? "none yet" : h->mb_mode) + "\", \"family\": " + num(h->mb_family) + ", \"members_per_launch\": " + num(h->mb_per_launch) +
+                           ", \"reason\": \"" + h->mb_why + "\", \"drifts\": " + (h->mb_drifts ? "true" : "false") + ", \"ctrl_mix\": " + (h->mb_mix ? "true" : "false") + "}");
     o += "}";
     if (buflen > 0) {
         const size_t n = std::min(o.size(), (size_t)buflen - 1);

@@ -477,12 +477,13 @@ static int multi_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int ncoe
     return JQ_OK;
 }
 
-// jq_traceobjgrad_drifts on a multi-device handle: every device tests ALL members against its plan first (one union re-plan each, so the
-// devices keep the same plan), then the members are block-partitioned over the devices (jq_shard_bounds) -- nothing to reduce
-static int traceobjgrad_drifts_single(jq_handle* h, const double* pcof, int ncoeff, const double* Hconsts, int ndrift, int evaladjoint, bool prepared,
-                                      double* out4, double* totalgrad, double* infidelgrad, double* leakgrad);
-static int multi_traceobjgrad_drifts(jq_handle* h, const double* pcof, int ncoeff, const double* Hconsts, int ndrift, int evaladjoint, double* out4,
-                                     double* totalgrad, double* infidelgrad, double* leakgrad)
+// A member ensemble (jq_traceobjgrad_drifts, jq_traceobjgrad_members) on a multi-device handle: every device tests ALL member drifts against
+// its plan first (one union re-plan each, so the devices keep the same plan), then the members -- drifts and control mixes alike -- are
+// block-partitioned over the devices (jq_shard_bounds) -- nothing to reduce
+static int traceobjgrad_members_single(jq_handle* h, const double* pcof, int ncoeff, const double* Hconsts, const double* ctrl_mix, int nmember,
+                                       int evaladjoint, bool prepared, double* out4, double* totalgrad, double* infidelgrad, double* leakgrad);
+static int multi_traceobjgrad_members(jq_handle* h, const double* pcof, int ncoeff, const double* Hconsts, const double* ctrl_mix, int nmember,
+                                      int evaladjoint, double* out4, double* totalgrad, double* infidelgrad, double* leakgrad)
 {
     DeviceGuard guard;
     // (a refused call writes nothing: the coefficient count is checked before any device starts)
@@ -490,13 +491,15 @@ static int multi_traceobjgrad_drifts(jq_handle* h, const double* pcof, int ncoef
         h->err = h->subs[0]->err;
         return rc;
     }
-    if (int rc = multi_forall(h, [&](jq_handle* sub) { return drifts_prepare(sub, Hconsts, ndrift); })) return rc;
-    const size_t nn = (size_t)h->subs[0]->Ntot * h->subs[0]->Ntot;
-    const int rc = multi_for_shards(h, ndrift, [&](jq_handle* sub, int, int lo, int hi) {
+    if (Hconsts)
+        if (int rc = multi_forall(h, [&](jq_handle* sub) { return drifts_prepare(sub, Hconsts, nmember); })) return rc;
+    const size_t nn = (size_t)h->subs[0]->Ntot * h->subs[0]->Ntot, ncnc = (size_t)h->subs[0]->Nc * h->subs[0]->Nc;
+    const int rc = multi_for_shards(h, nmember, [&](jq_handle* sub, int, int lo, int hi) {
         const size_t off = (size_t)ncoeff * lo;
         if (hi <= lo) return JQ_OK;
-        return traceobjgrad_drifts_single(sub, pcof, ncoeff, Hconsts + nn * lo, hi - lo, evaladjoint, true, out4 + (size_t)4 * lo,
-                                          totalgrad ? totalgrad + off : nullptr, infidelgrad ? infidelgrad + off : nullptr, leakgrad ? leakgrad + off : nullptr);
+        return traceobjgrad_members_single(sub, pcof, ncoeff, Hconsts ? Hconsts + nn * lo : nullptr, ctrl_mix ? ctrl_mix + ncnc * lo : nullptr, hi - lo,
+                                           evaladjoint, true, out4 + (size_t)4 * lo, totalgrad ? totalgrad + off : nullptr,
+                                           infidelgrad ? infidelgrad + off : nullptr, leakgrad ? leakgrad + off : nullptr);
     });
     if (rc != JQ_OK) return rc;
     multi_timing(h, 0.0);

@@ -10,8 +10,8 @@ static int multi_traceobjgrad_batch(jq_handle* h, const double* pcofs, int ncoef
                                     double* infidelgrad, double* leakgrad);
 static int multi_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int ncoeff, int npcof, const double* nodes, const double* weights, int nquad,
                                      const double* shift, int compute_adjoint, double* out2, double* infid_grad, double* leak_grad, double* node_out);
-static int multi_traceobjgrad_drifts(jq_handle* h, const double* pcof, int ncoeff, const double* Hconsts, int ndrift, int evaladjoint, double* out4,
-                                     double* totalgrad, double* infidelgrad, double* leakgrad);
+static int multi_traceobjgrad_members(jq_handle* h, const double* pcof, int ncoeff, const double* Hconsts, const double* ctrl_mix, int nmember,
+                                      int evaladjoint, double* out4, double* totalgrad, double* infidelgrad, double* leakgrad);
 // a single evaluation cannot be sharded: multi-device handles run it on their first device
 #define JQ_ON_FIRST(h, call)                         \
     if (!(h)->subs.empty()) {                        \

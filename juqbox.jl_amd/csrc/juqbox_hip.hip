@@ -166,6 +166,8 @@ struct jq_handle {
     double *d_stream = nullptr, *d_pq = nullptr;
     double* d_drift = nullptr;  // drift images of the members of a drift ensemble's launch, [groups][stride of the planned family] (run_eval)
     size_t cap_drift = 0;
+    double* d_mix = nullptr;    // control mixes of an evaluation's groups [groups][Nc x Nc], behind them k_ctrl's unmixed values in d_pq's layout (run_eval)
+    size_t cap_mix = 0;
     double *d_state = nullptr, *d_state_save = nullptr, *d_colinfo = nullptr, *d_traces = nullptr, *d_R = nullptr;
     double *d_grad = nullptr, *d_res = nullptr;
     double *d_wq = nullptr, *d_pack = nullptr;   // ensemble weights per sample; packed result [2 + 2 nCoeff] (multi-device all-reduce)
@@ -179,6 +181,10 @@ struct jq_handle {
     // ... and the last jq_traceobjgrad_drifts / jq_eval_f_g_grad_drifts with its members (jq_plan_info "drift_batch")
     std::string db_mode, db_why;
     int db_family = -1, db_per_launch = 0;
+    // ... and the last member ensemble of any kind, the two drifts calls included (jq_plan_info "member_batch")
+    std::string mb_mode, mb_why;
+    int mb_family = -1, mb_per_launch = 0;
+    bool mb_drifts = false, mb_mix = false;
     // Structure embedding (try_embed): a second handle of the SAME problem with its two fastest Kronecker factors zero-padded
     // to 4 levels each (row i1 + d1 i2 + d1 d2 i3 -> i1 + 4 i2 + 16 i3), under which the operators have the JQ_BW_T4 structure;
     // batches that would otherwise run on the dense / band MFMA kernels go there (quad-layout / JQ_BW_T4 slab kernels).
@@ -310,20 +316,24 @@ static int pcof_batch_per_launch(jq_handle* h, int npcof, int Q, bool adjoint, i
 // (drifts: [Ntot x Ntot x npcof] members that drifts_prepare has tested against the plan, pcofs: ONE vector, nquad == 1).  A grouped launch
 // of members hands run_eval their drifts; the sequential routes make member after member the handle's drift (apply_hconst: operator images
 // only, no re-plan) for the single call's request and put the handle's own drift back at the end.
+// ... and control mixes (mixes: [Nc x Nc x npcof], alone or together with drifts; pcofs: ONE vector, nquad == 1): a grouped launch hands
+// run_eval the mixes of its members, the sequential routes give the single evaluation its member's mix -- no operator is swapped for a mix.
 template <typename Put>
-static int pcof_batch(jq_handle* h, const double* pcofs, int ncoeff, int npcof, const double* drifts, const double* nodes, const double* weights,
-                      int nquad, const double* shift, bool adjoint, Put&& put)
+static int pcof_batch(jq_handle* h, const double* pcofs, int ncoeff, int npcof, const double* drifts, const double* mixes, const double* nodes,
+                      const double* weights, int nquad, const double* shift, bool adjoint, Put&& put)
 {
     int spg = 1, family = -1;
     const char* why = "";
     const int per = pcof_batch_per_launch(h, npcof, nquad, adjoint, &spg, &family, &why);
     const int step = per > 0 ? per : 1;
-    if (drifts) h->db_mode = per > 0 ? "grouped" : "sequential", h->db_why = why, h->db_family = family, h->db_per_launch = step;
-    else h->pb_mode = per > 0 ? "grouped" : "sequential", h->pb_why = why, h->pb_family = family, h->pb_per_launch = step, h->pb_nodes = nquad;
+    const bool members = drifts || mixes;
+    if (members) h->mb_mode = per > 0 ? "grouped" : "sequential", h->mb_why = why, h->mb_family = family, h->mb_per_launch = step, h->mb_drifts = drifts != nullptr, h->mb_mix = mixes != nullptr;
+    if (drifts && !mixes) h->db_mode = per > 0 ? "grouped" : "sequential", h->db_why = why, h->db_family = family, h->db_per_launch = step;
+    if (!members) h->pb_mode = per > 0 ? "grouped" : "sequential", h->pb_why = why, h->pb_family = family, h->pb_per_launch = step, h->pb_nodes = nquad;
     EvalRequest rq;
     rq.ncoeff = ncoeff, rq.nsamples = nquad, rq.eps = nodes, rq.wgt = weights, rq.shift = shift, rq.adjoint = adjoint;
     if (per > 0) rq.spg = spg, rq.nodes = nquad;
-    const size_t nn = (size_t)h->Ntot * h->Ntot;
+    const size_t nn = (size_t)h->Ntot * h->Ntot, ncnc = (size_t)h->Nc * h->Nc;
     const bool swap = drifts && per == 0;
     const std::vector<double> own = swap ? h->Hconst : std::vector<double>();
     struct Restore {      // (also when a member's evaluation fails)
@@ -334,7 +344,8 @@ static int pcof_batch(jq_handle* h, const double* pcofs, int ncoeff, int npcof, 
     jq_timing tsum = {};
     for (int i0 = 0; i0 < npcof; i0 += step) {
         const int G = std::min(step, npcof - i0);      // (sequential: one vector, spg == 1)
-        rq.pcof = drifts ? pcofs : pcofs + (size_t)ncoeff * i0;
+        rq.pcof = members ? pcofs : pcofs + (size_t)ncoeff * i0;
+        if (mixes) rq.mix = mixes + ncnc * i0;
         if (per > 0) rq.groups = G, rq.nsamples = G * spg;
         if (drifts && per > 0) rq.drifts = drifts + nn * i0;
         if (swap)
@@ -361,26 +372,89 @@ extern "C" int jq_traceobjgrad_batch(jq_handle* h, const double* pcofs, int32_t 
     if (npcof < 1) return fail(h, JQ_EINVAL, "jq_traceobjgrad_batch: npcof must be >= 1");
     if (!h->subs.empty()) return multi_traceobjgrad_batch(h, pcofs, ncoeff, npcof, evaladjoint, out4, totalgrad, infidelgrad, leakgrad);
     if (int rc = check_ncoeff(h, ncoeff)) return rc;      // (before anything is written)
-    return pcof_batch(h, pcofs, ncoeff, npcof, nullptr, nullptr, nullptr, 1, nullptr, evaladjoint != 0, [&](int i, const double* res, const double* g0, const double* g1) {
+    return pcof_batch(h, pcofs, ncoeff, npcof, nullptr, nullptr, nullptr, nullptr, 1, nullptr, evaladjoint != 0, [&](int i, const double* res, const double* g0, const double* g1) {
         const size_t off = (size_t)ncoeff * i;
         out_record(out4 + (size_t)4 * i, res);
         if (evaladjoint) out_grads(h, ncoeff, g0, g1, totalgrad + off, infidelgrad + off, leakgrad + off);
     });
 }
 
-// jq_traceobjgrad_drifts on a single-device handle whose plan holds every member (prepared: by the caller -- a multi-device handle tests
-// ALL members on every device before it shards them, so that the devices keep one plan)
-static int traceobjgrad_drifts_single(jq_handle* h, const double* pcof, int ncoeff, const double* Hconsts, int ndrift, int evaladjoint, bool prepared,
-                                      double* out4, double* totalgrad, double* infidelgrad, double* leakgrad)
+// An ensemble of nmember members under ONE control vector on a single-device handle: member i has the drift Hconsts[:, :, i] (NULL: the
+// handle's) and the control mix ctrl_mix[:, :, i] (NULL: identity).  The two drifts calls are the ctrl_mix == NULL case.
+// prepared: the caller has tested the member drifts against the plan -- a multi-device handle tests ALL members on every device before it
+// shards them, so that the devices keep one plan
+static int traceobjgrad_members_single(jq_handle* h, const double* pcof, int ncoeff, const double* Hconsts, const double* ctrl_mix, int nmember,
+                                       int evaladjoint, bool prepared, double* out4, double* totalgrad, double* infidelgrad, double* leakgrad)
 {
     if (int rc = check_ncoeff(h, ncoeff)) return rc;      // (before anything is written or re-planned)
-    if (!prepared)
-        if (int rc = drifts_prepare(h, Hconsts, ndrift)) return rc;
-    return pcof_batch(h, pcof, ncoeff, ndrift, Hconsts, nullptr, nullptr, 1, nullptr, evaladjoint != 0, [&](int i, const double* res, const double* g0, const double* g1) {
+    if (Hconsts && !prepared)
+        if (int rc = drifts_prepare(h, Hconsts, nmember)) return rc;
+    return pcof_batch(h, pcof, ncoeff, nmember, Hconsts, ctrl_mix, nullptr, nullptr, 1, nullptr, evaladjoint != 0, [&](int i, const double* res, const double* g0, const double* g1) {
         const size_t off = (size_t)ncoeff * i;
         out_record(out4 + (size_t)4 * i, res);
         if (evaladjoint) out_grads(h, ncoeff, g0, g1, totalgrad + off, infidelgrad + off, leakgrad + off);
     });
+}
+
+// the argument rules of the member entry points (who: the entry point's name; need_drifts: the drifts calls require Hconsts)
+static int members_args(jq_handle* h, const char* who, bool need_drifts, const void* pcof, const double* Hconsts, const double* ctrl_mix, int nmember, const void* out)
+{
+    const std::string w(who);
+    if (!pcof || !out || (need_drifts && !Hconsts)) return fail(h, JQ_EINVAL, (w + ": NULL pointer").c_str());
+    if (!Hconsts && !ctrl_mix) return fail(h, JQ_EINVAL, (w + ": Hconsts and ctrl_mix are both NULL (the plain evaluation: jq_traceobjgrad)").c_str());
+    if (nmember < 1) return fail(h, JQ_EINVAL, (w + ": the member count must be >= 1").c_str());
+    if (ctrl_mix) {
+        const int Nc = h->subs.empty() ? h->Nc : h->subs[0]->Nc;
+        for (size_t e = 0; e < (size_t)Nc * Nc * nmember; ++e)
+            if (!std::isfinite(ctrl_mix[e])) return fail(h, JQ_EINVAL, (w + ": a control mix entry is not finite").c_str());
+    }
+    return JQ_OK;
+}
+
+static int traceobjgrad_members(jq_handle* h, const char* who, bool need_drifts, const double* pcof, int ncoeff, const double* Hconsts, const double* ctrl_mix,
+                                int nmember, int evaladjoint, double* out4, double* totalgrad, double* infidelgrad, double* leakgrad)
+{
+    if (int rc = members_args(h, who, need_drifts, pcof, Hconsts, ctrl_mix, nmember, out4)) return rc;
+    if (evaladjoint && (!totalgrad || !infidelgrad || !leakgrad))
+        return fail(h, JQ_EINVAL, (std::string(who) + ": gradient outputs are required when evaladjoint != 0").c_str());
+    if (!h->subs.empty()) return multi_traceobjgrad_members(h, pcof, ncoeff, Hconsts, ctrl_mix, nmember, evaladjoint, out4, totalgrad, infidelgrad, leakgrad);
+    return traceobjgrad_members_single(h, pcof, ncoeff, Hconsts, ctrl_mix, nmember, evaladjoint, false, out4, totalgrad, infidelgrad, leakgrad);
+}
+
+// the weighted sums of eval_f_g_grad! (src/ipopt_interface.jl:48-59) over the members of an ensemble instead of over eps-nodes: the
+// members' columns from traceobjgrad_members, summed on the host in member order
+static int eval_f_g_grad_members(jq_handle* h, const char* who, bool need_drifts, const double* pcof, int ncoeff, const double* Hconsts, const double* ctrl_mix,
+                                 const double* weights, int nmember, int compute_adjoint, double* out2, double* infid_grad, double* leak_grad, double* member_out)
+{
+    if (!weights) return fail(h, JQ_EINVAL, (std::string(who) + ": NULL pointer").c_str());
+    if (int rc = members_args(h, who, need_drifts, pcof, Hconsts, ctrl_mix, nmember, out2)) return rc;
+    if (compute_adjoint && (!infid_grad || !leak_grad))
+        return fail(h, JQ_EINVAL, (std::string(who) + ": gradient outputs are required when compute_adjoint != 0").c_str());
+    if (int rc = check_ncoeff(h->subs.empty() ? h : h->subs[0], ncoeff)) {      // (before the temporaries are sized by it)
+        if (!h->subs.empty()) h->err = h->subs[0]->err;
+        return rc;
+    }
+    const size_t ng = compute_adjoint ? (size_t)ncoeff * nmember : 0;
+    std::vector<double> rec((size_t)4 * nmember), tg(ng), ig(ng), lg(ng);
+    const int rc = traceobjgrad_members(h, who, need_drifts, pcof, ncoeff, Hconsts, ctrl_mix, nmember, compute_adjoint, rec.data(), tg.data(), ig.data(), lg.data());
+    if (rc) return rc;
+    double inf = 0.0, leak = 0.0;
+    for (int i = 0; i < nmember; ++i) {
+        inf += rec[(size_t)4 * i + 1] * weights[i];      // (primaryobjf, secondaryobjf of the member's record)
+        leak += rec[(size_t)4 * i + 2] * weights[i];
+    }
+    out2[0] = inf, out2[1] = leak;
+    if (member_out) std::copy(rec.begin(), rec.end(), member_out);
+    if (compute_adjoint) {
+        std::fill_n(infid_grad, ncoeff, 0.0);
+        std::fill_n(leak_grad, ncoeff, 0.0);
+        for (int i = 0; i < nmember; ++i)
+            for (int k = 0; k < ncoeff; ++k) {
+                infid_grad[k] += weights[i] * ig[(size_t)ncoeff * i + k];
+                leak_grad[k] += weights[i] * lg[(size_t)ncoeff * i + k];
+            }
+    }
+    return JQ_OK;
 }
 
 extern "C" int jq_traceobjgrad_drifts(jq_handle* h, const double* pcof, int32_t ncoeff, const double* Hconsts, int32_t ndrift, int32_t evaladjoint,
@@ -388,51 +462,34 @@ extern "C" int jq_traceobjgrad_drifts(jq_handle* h, const double* pcof, int32_t 
 {
     if (!h) return JQ_EINVAL;
     return abi_guard(h, "jq_traceobjgrad_drifts", [&]() -> int {
-        if (!pcof || !Hconsts || !out4) return fail(h, JQ_EINVAL, "jq_traceobjgrad_drifts: NULL pointer");
-        if (evaladjoint && (!totalgrad || !infidelgrad || !leakgrad))
-            return fail(h, JQ_EINVAL, "jq_traceobjgrad_drifts: gradient outputs are required when evaladjoint != 0");
-        if (ndrift < 1) return fail(h, JQ_EINVAL, "jq_traceobjgrad_drifts: ndrift must be >= 1");
-        if (!h->subs.empty()) return multi_traceobjgrad_drifts(h, pcof, ncoeff, Hconsts, ndrift, evaladjoint, out4, totalgrad, infidelgrad, leakgrad);
-        return traceobjgrad_drifts_single(h, pcof, ncoeff, Hconsts, ndrift, evaladjoint, false, out4, totalgrad, infidelgrad, leakgrad);
+        return traceobjgrad_members(h, "jq_traceobjgrad_drifts", true, pcof, ncoeff, Hconsts, nullptr, ndrift, evaladjoint, out4, totalgrad, infidelgrad, leakgrad);
     });
 }
 
-// the weighted sums of eval_f_g_grad! (src/ipopt_interface.jl:48-59) over the members of a drift ensemble instead of over eps-nodes: the
-// members' columns from jq_traceobjgrad_drifts, summed on the host in member order
 extern "C" int jq_eval_f_g_grad_drifts(jq_handle* h, const double* pcof, int32_t ncoeff, const double* Hconsts, const double* weights, int32_t ndrift,
                                        int32_t compute_adjoint, double* out2, double* infid_grad, double* leak_grad, double* member_out)
 {
     if (!h) return JQ_EINVAL;
     return abi_guard(h, "jq_eval_f_g_grad_drifts", [&]() -> int {
-        if (!pcof || !Hconsts || !weights || !out2) return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_drifts: NULL pointer");
-        if (compute_adjoint && (!infid_grad || !leak_grad))
-            return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_drifts: gradient outputs are required when compute_adjoint != 0");
-        if (ndrift < 1) return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_drifts: ndrift must be >= 1");
-        if (int rc = check_ncoeff(h->subs.empty() ? h : h->subs[0], ncoeff)) {      // (before the temporaries are sized by it)
-            if (!h->subs.empty()) h->err = h->subs[0]->err;
-            return rc;
-        }
-        const size_t ng = compute_adjoint ? (size_t)ncoeff * ndrift : 0;
-        std::vector<double> rec((size_t)4 * ndrift), tg(ng), ig(ng), lg(ng);
-        const int rc = jq_traceobjgrad_drifts(h, pcof, ncoeff, Hconsts, ndrift, compute_adjoint, rec.data(), tg.data(), ig.data(), lg.data());
-        if (rc) return rc;
-        double inf = 0.0, leak = 0.0;
-        for (int i = 0; i < ndrift; ++i) {
-            inf += rec[(size_t)4 * i + 1] * weights[i];      // (primaryobjf, secondaryobjf of the member's record)
-            leak += rec[(size_t)4 * i + 2] * weights[i];
-        }
-        out2[0] = inf, out2[1] = leak;
-        if (member_out) std::copy(rec.begin(), rec.end(), member_out);
-        if (compute_adjoint) {
-            std::fill_n(infid_grad, ncoeff, 0.0);
-            std::fill_n(leak_grad, ncoeff, 0.0);
-            for (int i = 0; i < ndrift; ++i)
-                for (int k = 0; k < ncoeff; ++k) {
-                    infid_grad[k] += weights[i] * ig[(size_t)ncoeff * i + k];
-                    leak_grad[k] += weights[i] * lg[(size_t)ncoeff * i + k];
-                }
-        }
-        return JQ_OK;
+        return eval_f_g_grad_members(h, "jq_eval_f_g_grad_drifts", true, pcof, ncoeff, Hconsts, nullptr, weights, ndrift, compute_adjoint, out2, infid_grad, leak_grad, member_out);
+    });
+}
+
+extern "C" int jq_traceobjgrad_members(jq_handle* h, const double* pcof, int32_t ncoeff, const double* Hconsts, const double* ctrl_mix, int32_t nmember,
+                                       int32_t evaladjoint, double* out4, double* totalgrad, double* infidelgrad, double* leakgrad)
+{
+    if (!h) return JQ_EINVAL;
+    return abi_guard(h, "jq_traceobjgrad_members", [&]() -> int {
+        return traceobjgrad_members(h, "jq_traceobjgrad_members", false, pcof, ncoeff, Hconsts, ctrl_mix, nmember, evaladjoint, out4, totalgrad, infidelgrad, leakgrad);
+    });
+}
+
+extern "C" int jq_eval_f_g_grad_members(jq_handle* h, const double* pcof, int32_t ncoeff, const double* Hconsts, const double* ctrl_mix, const double* weights,
+                                        int32_t nmember, int32_t compute_adjoint, double* out2, double* infid_grad, double* leak_grad, double* member_out)
+{
+    if (!h) return JQ_EINVAL;
+    return abi_guard(h, "jq_eval_f_g_grad_members", [&]() -> int {
+        return eval_f_g_grad_members(h, "jq_eval_f_g_grad_members", false, pcof, ncoeff, Hconsts, ctrl_mix, weights, nmember, compute_adjoint, out2, infid_grad, leak_grad, member_out);
     });
 }
 
@@ -630,7 +687,7 @@ extern "C" int jq_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int32_t
         return multi_eval_f_g_grad_batch(h, pcofs, ncoeff, npcof, nodes, weights, nquad, shift, compute_adjoint, out2, infid_grad, leak_grad, node_out);
     if (int rc = check_ncoeff(h, ncoeff)) return rc;      // (before anything is written)
     // column i of the outputs from the records of its nquad samples (the sums in node order: src/ipopt_interface.jl:58-59)
-    return pcof_batch(h, pcofs, ncoeff, npcof, nullptr, nodes, weights, nquad, shift, compute_adjoint != 0, [&](int i, const double* res, const double* g0, const double* g1) {
+    return pcof_batch(h, pcofs, ncoeff, npcof, nullptr, nullptr, nodes, weights, nquad, shift, compute_adjoint != 0, [&](int i, const double* res, const double* g0, const double* g1) {
         double inf = 0.0, leak = 0.0;
         for (int q = 0; q < nquad; ++q) {
             inf += res[(size_t)q * 4 + 0] * weights[q];

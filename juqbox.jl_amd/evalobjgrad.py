@@ -14,6 +14,10 @@
   traceobjgrad_drifts(pcof, params, wa, Hconsts, evaladjoint=True)
                                         ONE control vector over an ensemble of drift Hamiltonians in one library
                                         call (jq_traceobjgrad_drifts): column i = traceobjgrad with Hconst = member i.
+  traceobjgrad_members(pcof, params, wa, Hconsts=None, ctrl_mix=None, evaladjoint=True)
+                                        ... over members that differ in a real mixing matrix of the controls (amplitude
+                                        miscalibration, crosstalk), in their drift, or in both (jq_traceobjgrad_members).
+  amplitude_mix(scales)                 [nmember, Nc] amplitude factors -> the diagonal mixes of such an ensemble.
   gradient_check(pcof0, params, wa, kpars, h=1e-6)
                                         adjoint gradient entries against central differences, from one batch.
 """
@@ -462,6 +466,102 @@ def traceobjgrad_drifts(pcof, params: objparams, wa: Working_Arrays_HIP, Hconsts
         return out4[:, 0].copy(), out4[:, 1].copy(), out4[:, 2].copy()
     tg, ig, lg = np.zeros((n, ncoeff)), np.zeros((n, ncoeff)), np.zeros((n, ncoeff))
     _lib.check(L.jq_traceobjgrad_drifts(h, _ptr(p), ncoeff, _ptr(H), n, 1, _ptr(out4), _ptr(tg), _ptr(ig), _ptr(lg)), h)
+    leak = np.zeros((0, n)) if params.objFuncType == 1 else np.ascontiguousarray(lg.T)
+    return (out4[:, 0].copy(), np.ascontiguousarray(tg.T), out4[:, 1].copy(), out4[:, 2].copy(), out4[:, 3].copy(),
+            np.ascontiguousarray(ig.T), leak)
+
+
+def _ncontrols(params):
+    """the controls a mix acts on: the coupled pairs, or the uncoupled controls of a problem that has those"""
+    return max(int(getattr(params, "Ncoupled", 0)), int(getattr(params, "Nunc", 0)))
+
+
+def amplitude_mix(scales):
+    """Amplitude miscalibration as control mixes: scales[i, k] is the factor with which p_k, q_k of member i arrive (1 + delta_k); returns
+    the [Nc, Nc, nmember] array of diagonal mixes C_i = diag(scales[i]).  A vector is one member.  ValueError for other shapes."""
+    try:
+        s = np.asarray(scales, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("amplitude_mix: scales must be an [nmember, Nc] array of numbers (%s)" % e)
+    if s.ndim == 1:
+        s = s[None, :]
+    if s.ndim != 2 or s.shape[0] < 1 or s.shape[1] < 1:
+        raise ValueError("amplitude_mix: scales must be an [nmember, Nc] array, not shape %r" % (s.shape,))
+    n, nc = s.shape
+    C = np.zeros((nc, nc, n))
+    for i in range(n):
+        C[:, :, i] = np.diag(s[i])
+    return C
+
+
+def _mix_members(ctrl_mix, Nc, who):
+    """ctrl_mix -> contiguous [nmember, Nc * Nc] array, member i column-major in row i (= the C ABI's Nc x Nc x nmember).  An Nc x Nc x
+    nmember array holds one member per slice [:, :, i], a sequence one matrix per element, a 2-D array is one member.  ValueError for
+    everything else, entries that are not finite included."""
+    if isinstance(ctrl_mix, np.ndarray):
+        if ctrl_mix.ndim == 2:
+            mats = [ctrl_mix]
+        elif ctrl_mix.ndim == 3:
+            mats = [ctrl_mix[:, :, i] for i in range(ctrl_mix.shape[2])]
+        else:
+            raise ValueError("%s: ctrl_mix must be an Nc x Nc x nmember array or a sequence of matrices, not %d-dimensional" % (who, ctrl_mix.ndim))
+    else:
+        try:
+            mats = [np.asarray(M) for M in ctrl_mix]
+            mats = [M if np.iscomplexobj(M) else np.asarray(M, dtype=np.float64) for M in mats]      # (complex: refused below, not cast)
+        except (TypeError, ValueError) as e:
+            raise ValueError("%s: ctrl_mix must be an Nc x Nc x nmember array or a sequence of real matrices (%s)" % (who, e))
+    if len(mats) == 0:
+        raise ValueError("%s: need at least one member mix" % who)
+    for i, M in enumerate(mats):
+        if np.ndim(M) != 2 or np.shape(M) != (Nc, Nc):
+            raise ValueError("%s: mix %d has shape %r, expected (%d, %d) (the controls of params)" % (who, i, np.shape(M), Nc, Nc))
+        if np.iscomplexobj(M):
+            raise ValueError("%s: mix %d is complex; only real mixing matrices are served" % (who, i))
+        if not np.all(np.isfinite(M)):
+            raise ValueError("%s: mix %d has an entry that is not finite" % (who, i))
+    return np.ascontiguousarray(np.stack([_f64(M) for M in mats]))
+
+
+def _members(params, Hconsts, ctrl_mix, who):
+    """(drifts [n, Ntot * Ntot] or None, mixes [n, Nc * Nc] or None, n) of a member ensemble; ValueError for wrong shapes"""
+    if Hconsts is None and ctrl_mix is None:
+        raise ValueError("%s: give Hconsts, ctrl_mix or both (neither: the plain evaluation, traceobjgrad)" % who)
+    H = _drift_members(Hconsts, int(params.Ntot), who) if Hconsts is not None else None
+    C = _mix_members(ctrl_mix, _ncontrols(params), who) if ctrl_mix is not None else None
+    if H is not None and C is not None and H.shape[0] != C.shape[0]:
+        raise ValueError("%s: %d member drifts but %d member mixes" % (who, H.shape[0], C.shape[0]))
+    return H, C, (H if H is not None else C).shape[0]
+
+
+def traceobjgrad_members(pcof, params: objparams, wa: Working_Arrays_HIP, Hconsts=None, ctrl_mix=None, evaladjoint: bool = True):
+    """nmember evaluations of ONE control vector in one library call (jq_traceobjgrad_members) whose member i has the real Nc x Nc mixing
+    matrix C_i = ctrl_mix[:, :, i] of the controls -- operator l is driven by sum_k C_i[l, k] (p_k, q_k); diag(1 + delta): miscalibrated
+    amplitudes (amplitude_mix), off-diagonal entries: crosstalk -- and, with Hconsts, its own drift.  Column i equals traceobjgrad on the
+    problem whose operators are Hsym'_k = sum_l C_i[l, k] Hsym_l, Hanti'_k likewise, and is bit-identical to that member evaluated alone.
+    Routing as traceobjgrad_drifts (wa.plan_info()["member_batch"]); ctrl_mix=None is traceobjgrad_drifts.
+
+    Hconsts: None (the drift of params) or as for traceobjgrad_drifts; ctrl_mix: None (identity), an Nc x Nc x nmember array or a sequence
+    of Nc x Nc matrices.  Returns the arrays of traceobjgrad_batch, one column per member.  Shape errors raise ValueError before any
+    library call."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("traceobjgrad_members: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("traceobjgrad_members: wa was allocated for a different objparams")
+    ncoeff = int(wa.nCoeff)
+    H, C, n = _members(params, Hconsts, ctrl_mix, "traceobjgrad_members")
+    p = np.asarray(pcof, dtype=np.float64)
+    if p.ndim != 1 or p.size != ncoeff:
+        raise ValueError("traceobjgrad_members: pcof has shape %r, expected (%d,) (wa.nCoeff)" % (p.shape, ncoeff))
+    p = _f64(p)
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    out4 = np.zeros((n, 4))
+    if not evaladjoint:
+        _lib.check(L.jq_traceobjgrad_members(h, _ptr(p), ncoeff, _ptr(H), _ptr(C), n, 0, _ptr(out4), None, None, None), h)
+        return out4[:, 0].copy(), out4[:, 1].copy(), out4[:, 2].copy()
+    tg, ig, lg = np.zeros((n, ncoeff)), np.zeros((n, ncoeff)), np.zeros((n, ncoeff))
+    _lib.check(L.jq_traceobjgrad_members(h, _ptr(p), ncoeff, _ptr(H), _ptr(C), n, 1, _ptr(out4), _ptr(tg), _ptr(ig), _ptr(lg)), h)
     leak = np.zeros((0, n)) if params.objFuncType == 1 else np.ascontiguousarray(lg.T)
     return (out4[:, 0].copy(), np.ascontiguousarray(tg.T), out4[:, 1].copy(), out4[:, 2].copy(), out4[:, 3].copy(),
             np.ascontiguousarray(ig.T), leak)

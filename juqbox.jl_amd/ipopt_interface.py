@@ -5,7 +5,7 @@ signatures, so any L-BFGS driver can call them)."""
 import numpy as np
 
 from . import _lib
-from .evalobjgrad import Working_Arrays_HIP, _drift_members, _f64, _pcof_columns, _ptr
+from .evalobjgrad import Working_Arrays_HIP, _drift_members, _f64, _members, _pcof_columns, _ptr
 from .setup_utils import tikhonov_grad, tikhonov_pen
 
 
@@ -253,41 +253,91 @@ def eval_f_g_grad_drifts(pcof, params, wa, Hconsts, weights, compute_adjoint=Tru
     return params.last_infidelity, params.last_leak
 
 
+def eval_f_g_grad_members(pcof, params, wa, weights, Hconsts=None, ctrl_mix=None, compute_adjoint=True, per_member=False):
+    """eval_f_g_grad_drifts over the members of traceobjgrad_members (jq_eval_f_g_grad_members): the weighted sums over members that differ
+    in a real mixing matrix of the controls (ctrl_mix: Nc x Nc x nmember; amplitude_mix for miscalibrated amplitudes), in their drift
+    (Hconsts), or in both.  Results land in params.last_* exactly as eval_f_g_grad leaves them; routing: wa.plan_info()["member_batch"].
+
+    weights: one per member.  Returns (last_infidelity, last_leak), with per_member=True also the array [4, nmember] of the members'
+    records -- the bits of traceobjgrad_members.  Shape errors raise ValueError before any library call."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("eval_f_g_grad_members: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("eval_f_g_grad_members: wa was allocated for a different objparams")
+    H, C, nm = _members(params, Hconsts, ctrl_mix, "eval_f_g_grad_members")
+    try:
+        w = np.asarray(weights, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("eval_f_g_grad_members: weights must be a vector of numbers (%s)" % e)
+    if w.ndim != 1 or w.size != nm:
+        raise ValueError("eval_f_g_grad_members: need one weight per member (%d), not shape %r" % (nm, w.shape))
+    w = _f64(w)
+    p = np.asarray(pcof, dtype=np.float64)
+    n = int(wa.nCoeff)
+    if p.ndim != 1 or p.size != n:
+        raise ValueError("eval_f_g_grad_members: pcof has shape %r, expected (%d,) (wa.nCoeff)" % (p.shape, n))
+    p = _f64(p)
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    # (the memoised gradients are reset like eval_f_g_grad resets them: src/ipopt_interface.jl:27-31)
+    params.last_infidelity_grad = np.zeros(n)
+    params.last_leak_grad = np.zeros(n) if params.objFuncType != 1 else np.zeros(0)
+    out2 = np.zeros(2)
+    ig, lg = np.zeros(n), np.zeros(n)
+    member_out = np.zeros((nm, 4)) if per_member else None
+    _lib.check(L.jq_eval_f_g_grad_members(h, _ptr(p), n, _ptr(H), _ptr(C), _ptr(w), nm, 1 if compute_adjoint else 0, _ptr(out2), _ptr(ig),
+                                          _ptr(lg), _ptr(member_out)), h)
+    params.last_pcof = p.copy()
+    params.last_infidelity = float(out2[0])
+    params.last_leak = float(out2[1])
+    if compute_adjoint:
+        params.last_infidelity_grad = ig.copy()
+        params.last_leak_grad = lg.copy() if params.objFuncType != 1 else np.zeros(0)
+    params.lastTraceInfidelity = params.last_infidelity
+    params.lastLeakIntegral = params.last_leak
+    if per_member:
+        return params.last_infidelity, params.last_leak, np.ascontiguousarray(member_out.T)
+    return params.last_infidelity, params.last_leak
+
+
 def _stale(pcof, params):
     # memoisation on ||pcof - last_pcof|| > 1e-15 (src/ipopt_interface.jl:83-84)
     last = params.last_pcof
     return last.size != np.size(pcof) or np.linalg.norm(np.asarray(pcof, dtype=np.float64) - last) > 1.0e-15
 
 
-def _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights):
-    """the evaluation the callbacks memoise: eval_f_g_grad over the eps-nodes, or (drifts given) eval_f_g_grad_drifts over the members"""
-    if drifts is not None:
+def _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights, ctrl_mix=None):
+    """the evaluation the callbacks memoise: eval_f_g_grad over the eps-nodes, (drifts given) eval_f_g_grad_drifts over the members, or
+    (ctrl_mix given, with or without drifts; drift_weights: the members' weights) eval_f_g_grad_members"""
+    if ctrl_mix is not None:
+        eval_f_g_grad_members(pcof, params, wa, drift_weights, Hconsts=drifts, ctrl_mix=ctrl_mix, compute_adjoint=True)
+    elif drifts is not None:
         eval_f_g_grad_drifts(pcof, params, wa, drifts, drift_weights, True)
     else:
         eval_f_g_grad(pcof, params, wa, nodes, weights, True)
 
 
-def eval_f_par(pcof, params, wa, nodes=(0.0,), weights=(1.0,), drifts=None, drift_weights=None):
+def eval_f_par(pcof, params, wa, nodes=(0.0,), weights=(1.0,), drifts=None, drift_weights=None, ctrl_mix=None):
     """src/ipopt_interface.jl:77-99"""
     if _stale(pcof, params):
-        _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights)
+        _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights, ctrl_mix)
     f = params.last_infidelity + params.last_leak if params.objFuncType == 1 else params.last_infidelity
     prior = params.priorCoeffs if params.usingPriorCoeffs else None
     return f + tikhonov_pen(pcof, params.tik0, prior)
 
 
-def eval_g_par(pcof, g, params, wa, nodes=(0.0,), weights=(1.0,), drifts=None, drift_weights=None):
+def eval_g_par(pcof, g, params, wa, nodes=(0.0,), weights=(1.0,), drifts=None, drift_weights=None, ctrl_mix=None):
     """src/ipopt_interface.jl:104-118"""
     if _stale(pcof, params):
-        _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights)
+        _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights, ctrl_mix)
     g[0] = params.last_leak
     return g[0]
 
 
-def eval_grad_f_par(pcof, grad_f, params, wa, nodes=(0.0,), weights=(1.0,), drifts=None, drift_weights=None):
+def eval_grad_f_par(pcof, grad_f, params, wa, nodes=(0.0,), weights=(1.0,), drifts=None, drift_weights=None, ctrl_mix=None):
     """src/ipopt_interface.jl:124-148"""
     if _stale(pcof, params):
-        _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights)
+        _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights, ctrl_mix)
     grad_f[:] = params.last_infidelity_grad
     prior = params.priorCoeffs if params.usingPriorCoeffs else None
     wa.gr[:] = tikhonov_grad(pcof, params.tik0, prior)
@@ -296,7 +346,7 @@ def eval_grad_f_par(pcof, grad_f, params, wa, nodes=(0.0,), weights=(1.0,), drif
         params.pcof_hist.append(np.array(pcof, dtype=np.float64))
 
 
-def eval_jac_g_par(pcof, rows, cols, jac_g, params, wa, nodes=(0.0,), weights=(1.0,), drifts=None, drift_weights=None):
+def eval_jac_g_par(pcof, rows, cols, jac_g, params, wa, nodes=(0.0,), weights=(1.0,), drifts=None, drift_weights=None, ctrl_mix=None):
     """src/ipopt_interface.jl:153-179 (including its quirk: when it has to recompute it returns
     without filling jac_g, :169-173)."""
     if jac_g is None:
@@ -306,7 +356,7 @@ def eval_jac_g_par(pcof, rows, cols, jac_g, params, wa, nodes=(0.0,), weights=(1
                 cols[i] = i + 1
         return
     if _stale(pcof, params):
-        _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights)
+        _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights, ctrl_mix)
         return
     jac_g[:] = params.last_leak_grad
 
@@ -363,18 +413,40 @@ class OptimProblem:
 
 def setup_ipopt_problem(params, wa, nCoeff, minCoeff, maxCoeff, maxIter=50, lbfgsMax=10, startFromScratch=True,
                         ipTol=1.0e-5, acceptTol=1.0e-5, acceptIter=15, nodes=(0.0,), weights=(1.0,),
-                        jacob_approx="exact", drifts=None, drift_weights=None):
+                        jacob_approx="exact", drifts=None, drift_weights=None, ctrl_mix=None, member_weights=None):
     """src/ipopt_interface.jl:262-415.
     drifts (an Ntot x Ntot x ndrift array or a sequence of matrices) with drift_weights (one per member): the callbacks memoise through
     eval_f_g_grad_drifts instead of eval_f_g_grad, so run_optimizer optimises the risk-neutral objective over that drift ensemble
-    (nodes / weights are then not used).  Shape errors raise ValueError before any library call."""
-    if drifts is not None:
+    (nodes / weights are then not used).
+    ctrl_mix (an Nc x Nc x nmember array or a sequence of matrices; amplitude_mix builds diagonal ones) with member_weights (one per member):
+    the callbacks memoise through eval_f_g_grad_members -- the risk-neutral objective over miscalibrated amplitudes / crosstalk.  drifts and
+    ctrl_mix may be given together (member i has both) with ONE weight vector, under either keyword; giving both weight keywords is an error.
+    Shape errors raise ValueError before any library call."""
+    if drift_weights is not None and member_weights is not None:
+        raise ValueError("setup_ipopt_problem: give drift_weights or member_weights, not both")
+    if member_weights is not None:      # (one weight vector for the members, whatever differs between them)
+        drift_weights = member_weights
+    if ctrl_mix is not None:
+        if drift_weights is None:
+            raise ValueError("setup_ipopt_problem: ctrl_mix needs member_weights (one weight per member)")
+        H, C, nm = _members(params, drifts, ctrl_mix, "setup_ipopt_problem")
+        try:
+            mw = np.asarray(drift_weights, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError("setup_ipopt_problem: member_weights must be a vector of numbers (%s)" % e)
+        if mw.ndim != 1 or mw.size != nm:
+            raise ValueError("setup_ipopt_problem: need one weight per member (%d), not shape %r" % (nm, mw.shape))
+        nc = int(round(np.sqrt(C.shape[1])))
+        ctrl_mix = [M.reshape((nc, nc), order="F") for M in C]
+        drifts = [M.reshape((int(params.Ntot), int(params.Ntot)), order="F") for M in H] if H is not None else None
+        drift_weights = _f64(mw)
+    elif drifts is not None:
         if drift_weights is None:
             raise ValueError("setup_ipopt_problem: drifts needs drift_weights (one weight per member)")
         drifts, drift_weights = _drift_ensemble(params, drifts, drift_weights, "setup_ipopt_problem")
         drifts = [M.reshape((int(params.Ntot), int(params.Ntot)), order="F") for M in drifts]
     elif drift_weights is not None:
-        raise ValueError("setup_ipopt_problem: drift_weights without drifts")
+        raise ValueError("setup_ipopt_problem: member weights without drifts or ctrl_mix")
     minCoeff = np.asarray(minCoeff, dtype=np.float64)
     maxCoeff = np.asarray(maxCoeff, dtype=np.float64)
     if minCoeff.size != nCoeff or maxCoeff.size != nCoeff:
@@ -390,7 +462,7 @@ def setup_ipopt_problem(params, wa, nCoeff, minCoeff, maxCoeff, maxIter=50, lbfg
     prob = OptimProblem()
     prob.params, prob.wa, prob.nCoeff = params, wa, int(nCoeff)
     prob.x_L, prob.x_U = minCoeff, maxCoeff
-    ens = dict(drifts=drifts, drift_weights=drift_weights)
+    ens = dict(drifts=drifts, drift_weights=drift_weights, ctrl_mix=ctrl_mix)
     prob.eval_f = lambda pcof: eval_f_par(pcof, params, wa, nodes, weights, **ens)
 
     def _grad(pcof):
@@ -413,7 +485,7 @@ def setup_ipopt_problem(params, wa, nCoeff, minCoeff, maxCoeff, maxIter=50, lbfg
     def _jac_g(pcof):
         jac = np.zeros(nCoeff)
         if _stale(pcof, params):     # the reference's callback returns unfilled in this case (:169-173); Ipopt
-            _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights)   # always calls eval_g first -- here we recompute
+            _refresh(pcof, params, wa, nodes, weights, drifts, drift_weights, ctrl_mix)   # always calls eval_g first -- here we recompute
         eval_jac_g_par(pcof, [], [], jac, params, wa, nodes, weights, **ens)
         return jac
     prob.eval_g, prob.eval_jac_g = _g, _jac_g
