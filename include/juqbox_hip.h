@@ -510,7 +510,7 @@ int jq_traceobj_sweep(jq_handle *h, const double *pcof, int32_t ncoeff, const do
  * as csrc/Makefile names them (k_6_7, s_6_7, p_6_7, u_6_7, k_6_8, c_6_9, ...; "host": the run-time-size kernels), "slabs_per_workgroup"
  * (quad layout, else 0), "quads_per_workgroup" (split quad backward sweep: 4 / 2, else 0), "backward_workgroups" (cooperative quad: 1 /
  * 2 / 3 workgroups per column quad, else 0), and the compile-time variant as booleans "uni", "ord", "sc_forward", "sc_backward", "ride",
- * "modd", "fwd2", "wlr", "imr_two_sets"} -- recorded by the tables that pick the kernel (csrc/jq_host_select.h), for the first (larger)
+ * "modd", "fwd2", "wlr", "imr_two_sets"} -- recorded by the functions that pick the kernel (csrc/jq_host_select.h), for the first (larger)
  * part of a batch that was split into two launches.  The key is additive: no ABI version change.
  */
 int jq_plan_info(const jq_handle *h, char *buf, int32_t buflen);

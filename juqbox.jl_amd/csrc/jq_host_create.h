@@ -28,7 +28,6 @@ static int dev_grow(jq_handle* h, T** p, size_t* cap, size_t need)
     return rc;
 }
 
-static bool hanti_s_uniform(const double* Hanti, int Ntot, int NT, int Nc);      // (jq_host_select.h)
 static int upload_operators(jq_handle* h)
 {
     const size_t nn = (size_t)h->Ntot * h->Ntot;

@@ -212,3 +212,47 @@ static void rowlane_image(const double* M, int Ntot, int NPJ, double* img)
         for (int j = 0; j < Ntot; ++j) img[(size_t)i * NPJ + j] = M[i + (size_t)Ntot * j];
 }
 
+// control q acts on subsystem q only (the usual Juqbox set-up: Hsym_ops = [a + a', b + b', c + c']): its trace products need one part of
+// the product each (the callers bound Nc first: at most JQ_MAXNC trace modes)
+static bool ctrl_per_subsystem(const jq_handle* h)
+{
+    for (int q = 0; q < h->Nc; ++q)
+        if (h->bw_trace[q] != (1 << q)) return false;
+    return true;
+}
+// Uniform S: the S image of every time point, c sum_k q_k(t) Hanti_k, repeats its block 0 -- what Juqbox's usual set-up Hanti_k = a_k - a_k'
+// gives on a 4 x 4 x n space (row = 16 mt + 4 b + i): the 4 x 4 diagonal blocks are those of the fastest subsystem in every row group, the
+// +-4 couplings those of the middle one in every 16-row block, the +-16 couplings one number per pair of neighbouring blocks.  Tested on
+// the JQ_BW_T4 image of each Hanti_k, entry by entry and BIT by bit (k_stream forms every entry of S with the same operations from the
+// same entries of the Hanti images: equal inputs give equal entries), in exactly the form the compact operand of the kernels relies on
+// (jq_kernels.h OpS):
+//   (1) the A operand (64 doubles) of every 16-row block equals that of block 0;
+//   (2) the lane-shift coefficients (c0, c1) of every row of a block equal those of the same row of block 0;
+//   (3) the neighbour-block coefficients c2 (blocks mt > 0) and c3 (blocks mt < NT - 1) are the same in all 16 rows of a block.
+static bool s_image_uniform(const double* img, int NT)
+{
+    auto same = [](double x, double y) { return memcmp(&x, &y, sizeof x) == 0; };
+    const double* cf = img + (size_t)4 * NT * JQ_T4_TILE;
+    for (int mt = 0; mt < NT; ++mt) {
+        for (int e = 0; e < 64; ++e)
+            if (!same(img[mt * 64 + e], img[e])) return false;
+        for (int g = 0; g < 4; ++g)
+            for (int r = 0; r < 4; ++r) {
+                const double* rec = cf + mt * 64 + JQ_T4_CIDX(g, r, 0);
+                if (!same(rec[0], cf[JQ_T4_CIDX(g, r, 0)]) || !same(rec[1], cf[JQ_T4_CIDX(g, r, 1)])) return false;
+                if (mt > 0 && !same(rec[2], cf[mt * 64 + 2])) return false;
+                if (mt + 1 < NT && !same(rec[3], cf[mt * 64 + 3])) return false;
+            }
+    }
+    return true;
+}
+// ... of all Nc antisymmetric control operators (column-major Ntot x Ntot each) of a 4 x 4 x n plan with NT 16-row blocks
+static bool hanti_s_uniform(const double* Hanti, int Ntot, int NT, int Nc)
+{
+    std::vector<double> img((size_t)JQ_T4_ELEMS(NT));
+    for (int q = 0; q < Nc; ++q) {
+        tile_image(Hanti + (size_t)q * Ntot * Ntot, Ntot, NT, JQ_BW_T4, img.data());
+        if (!s_image_uniform(img.data(), NT)) return false;
+    }
+    return true;
+}

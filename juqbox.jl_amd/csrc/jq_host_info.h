@@ -142,7 +142,7 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
         }
         kv("build", std::string("{\"manifest\": ") + (man.size() > 2 ? "true" : "false") + ", \"hipcc\": " + hipcc + ", \"objects\": " + objs + "}");
     }
-    {   // the instantiation the last evaluation ran on, recorded where the tables of jq_host_select.h picked its kernels (null: no evaluation
+    {   // the instantiation the last evaluation ran on, recorded where the select_* functions of jq_host_select.h picked its kernels (null: no evaluation
         // since the handle was created or planned again): the objects of the backward and the forward kernel as csrc/Makefile names them
         // (jq_timing's family / size / band cannot tell k_N_7 from s_N_7, nor a specialised instantiation from the generic one) and the
         // compile-time variant.  The first (larger) part's where a batch was split into two launches; the embedded twin's where it served.

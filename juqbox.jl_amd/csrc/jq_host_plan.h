@@ -325,20 +325,19 @@ static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateH
     p->dense = cq_dn || imr_dq;
     int rc = JQ_OK;
     switch (p->family) {
-    case KF_CQ_IMR: rc = select_cq_imr_kernels(h, imr_cq2, imr_cq3, imr_dq, &p->kfwd, &p->kbwd); break;
-    case KF_QUAD_IMR: rc = select_quad_imr_kernels(h, &p->kfwd, &p->kbwd); break;
-    case KF_COOP_IMR: rc = p->parts ? select_coop_imr_parts_kernels(h, p->hbm, &p->kfwd, &p->kbwd) : select_coop_imr_kernels(h, p->hbm, &p->kfwd, &p->kbwd); break;
-    case KF_ROWLANE_IMR: rc = select_rowlane_imr_kernels(h, rl_split, &p->kfwd, &p->kbwd); break;
-    case KF_ROWLANE: rc = select_rowlane_kernels(h, p->rl_waves, hist, &p->kfwd, &p->kbwd); break;
-    case KF_LANE: rc = select_lane_kernels(h, &p->kfwd, &p->kbwd, &p->klinit, &p->klterm); break;
-    case KF_CQ: rc = select_cq_kernels(h, p->fwd2, p->cq_nr, wfull, cq_dn, &p->kfwd, &p->kbwd); break;
-    case KF_COOP: rc = select_coop_kernels(h, &p->kfwd, &p->kbwd); break;
-    case KF_QUAD: rc = wfull ? select_quad_w_kernels(h, &p->kfwd, &p->kbwd) : select_quad_kernels(h, p->spw, &p->kfwd, &p->kbwd); break;
-    case KF_SLAB: rc = select_kernels(h, &p->kfwd, &p->kbwd); break;
+    case KF_CQ_IMR: rc = select_cq_imr_kernels(h, imr_cq2, imr_cq3, imr_dq, &p->kfwd, &p->kbwd, &p->sel); break;
+    case KF_QUAD_IMR: rc = select_quad_imr_kernels(h, &p->kfwd, &p->kbwd, &p->sel); break;
+    case KF_COOP_IMR: rc = p->parts ? select_coop_imr_parts_kernels(h, p->hbm, &p->kfwd, &p->kbwd, &p->sel) : select_coop_imr_kernels(h, p->hbm, &p->kfwd, &p->kbwd, &p->sel); break;
+    case KF_ROWLANE_IMR: rc = select_rowlane_imr_kernels(h, rl_split, &p->kfwd, &p->kbwd, &p->sel); break;
+    case KF_ROWLANE: rc = select_rowlane_kernels(h, p->rl_waves, hist, &p->kfwd, &p->kbwd, &p->sel); break;
+    case KF_LANE: rc = select_lane_kernels(h, &p->kfwd, &p->kbwd, &p->klinit, &p->klterm, &p->sel); break;
+    case KF_CQ: rc = select_cq_kernels(h, p->fwd2, p->cq_nr, wfull, cq_dn, &p->kfwd, &p->kbwd, &p->sel); break;
+    case KF_COOP: rc = select_coop_kernels(h, &p->kfwd, &p->kbwd, &p->sel); break;
+    case KF_QUAD: rc = wfull ? select_quad_w_kernels(h, &p->kfwd, &p->kbwd, &p->sel) : select_quad_kernels(h, p->spw, &p->kfwd, &p->kbwd, &p->sel); break;
+    case KF_SLAB: rc = select_kernels(h, &p->kfwd, &p->kbwd, &p->sel); break;
     }
     if (rc) return rc;
-    if (qsplit && (rc = select_qsplit_kernel(h, p->qs_qw, &p->kbwd))) return rc;
-    p->sel = h->sel;
+    if (qsplit && (rc = select_qsplit_kernel(h, p->qs_qw, &p->kbwd, &p->sel))) return rc;
     // Jacobi solver with N > 16 on the slab kernels: ONE workgroup per sample when its parts fit one (N <= 64): the waves add their parts'
     // residual norms through LDS, so the stopping test is the reference's (src/linear_solvers.jl:121), not one per 16-column part (round 5;
     // option jac_wg=0: per part, as with more parts or the cooperative kernels)

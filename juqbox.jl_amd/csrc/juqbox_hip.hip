@@ -52,9 +52,9 @@ static bool debug_timing()
 // "max_agprs": .., "max_scratch_bytes": ..}, ...} -- flat entries, quoted by jq_plan_info
 extern "C" const char jq_build_manifest[];
 
-// Which instantiation the tables of jq_host_select.h chose for a batch: the objects (csrc/Makefile tags) of the forward and the backward
-// kernel and the compile-time variant.  select_* fill jq_handle::sel, plan_batch keeps it in its BatchPlan, run_eval publishes the plan's
-// record as jq_handle::last_kernels once the evaluation is through (jq_plan_info "last_kernels").
+// Which instantiation the select_* functions of jq_host_select.h chose for a batch: the objects (csrc/Makefile tags) of the forward and the
+// backward kernel and the compile-time variant.  select_* fill the record of the BatchPlan that plan_batch hands them, run_eval publishes
+// the plan's record as jq_handle::last_kernels once the evaluation is through (jq_plan_info "last_kernels").
 #define JQ_SEL_TAG 12
 struct KernelSel {
     bool set = false;
@@ -67,7 +67,7 @@ struct KernelSel {
 
 struct jq_handle {
     int device = 0;
-    KernelSel sel, last_kernels;      // (sel: scratch of the select_* call in flight)
+    KernelSel last_kernels;
     JqOptions opt;              // per-handle options (jq_options.h): jq_create_opts / JQ_OPTIONS / jq_set_option
     hipStream_t stream = nullptr;
     // problem
@@ -87,7 +87,7 @@ struct jq_handle {
     // per GROUP of at most JQ_MAXNC controls (ctrl_groups(); 5 .. 8 controls: two sweeps), each with its own trace images.
     int NcK = 0;                // controls per backward sweep the LDS plan is made for: min(Nc, JQ_MAXNC)
     std::vector<int> bw_trace;  // [Nc]
-    bool s_uniform = false;     // 4 x 4 x n plan: every 16-row block of an S image repeats block 0 (hanti_s_uniform, jq_host_select.h)
+    bool s_uniform = false;     // 4 x 4 x n plan: every 16-row block of an S image repeats block 0 (hanti_s_uniform, jq_host_images.h)
     long long mat_elems = 0;    // doubles per operator image slot ("stride"): band tiles, padded to 1 KiB
     long long mat_elems_c = 0;  // ... in the row-window layout of the cooperative kernels (0: not available)
     bool coop_ok = false;       // the cooperative Stormer-Verlet kernels fit the LDS (dense 96 x 96: only the implicit-midpoint variant that reads its images from HBM)
@@ -240,7 +240,8 @@ struct DeviceGuard {
 #include "jq_host_images.h"      // operator / state images in the kernels' layouts and the structure tests the planner uses
 #include "jq_host_create.h"      // device buffers, uploads, jq_create* (planning from the operators' nonzero structure), structure embedding
 #include "jq_host_update.h"      // the mutations scripts apply to params after construction: solver / integrator, target, drift (re-planning), leakage weights
-#include "jq_host_select.h"      // the kernel instantiations (compiled in their own translation units) and the tables that pick one
+#include "jq_inst_list.h"        // the list of the propagator-kernel instantiations
+#include "jq_host_select.h"      // ... declared (they are compiled in their own translation units), and the functions that pick one
 #include "jq_host_plan.h"      // plan_batch: how a batch is routed to a kernel family, its geometry and LDS layout
 #include "jq_host_eval.h"      // run_eval: an EvalRequest evaluated by its plan, chunk by chunk
 extern "C" int jq_traceobjgrad(jq_handle* h, const double* pcof, int32_t ncoeff, int32_t evaladjoint, double* out4,
@@ -670,7 +671,6 @@ extern "C" int jq_traceobj_sweep(jq_handle* h, const double* pcof, int32_t ncoef
     return JQ_OK;
 }
 
-// jq_eval_f_g_grad for npcof control vectors and ONE set of nodes (pcof_batch)
 // jq_eval_f_g_grad for npcof control vectors and ONE set of nodes: grouped launches of G vectors x nquad nodes where the plan allows
 // (pcof_batch_per_launch), else one ensemble evaluation per vector -- the very calls jq_eval_f_g_grad makes.
 extern "C" int jq_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int32_t ncoeff, int32_t npcof, const double* nodes,
@@ -701,3 +701,6 @@ extern "C" int jq_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int32_t
 
 #include "jq_host_multi.h"      // multi-device handles: one process, N GPUs, one RCCL all-reduce
 #include "jq_host_info.h"      // options of a live handle, plan and timing introspection
+#ifdef JQ_DUMP_SELECTION
+#include "jq_dump_selection.h"      // build/dump_selection: main() prints what every select_* function picks (no HIP call)
+#endif

@@ -1,7 +1,7 @@
 """Random 4 x 4 x n problems whose control q acts on subsystem q ONLY (tests/test_structured_matrix.py, tests/test_gpu_structured.py):
 control 0 has nothing but 4 x 4 diagonal blocks, control 1 nothing but (i, i +- 4) couplings inside a 16-row block, control 2 nothing
 but (i, i +- 16) couplings -- Hsym and Hanti alike -- which is Juqbox's usual set-up Hsym_ops = [a + a', b + b', c + c'] and what the
-library's ORD / RIDE / SC specialisations are selected for (jq_host_select.h ctrl_per_subsystem).  The "t4" generators of
+library's ORD / RIDE / SC specialisations are selected for (jq_host_images.h ctrl_per_subsystem).  The "t4" generators of
 tests/test_gpu_random.py and tests/kronecker_problem.py give control 0 all three parts, so they never reach those instantiations."""
 import numpy as np
 

@@ -1,5 +1,5 @@
 """CPU: the structure test behind the compact S operand of the three-slab quad-layout kernels (jq_s_uniform = plan info "s_uniform";
-csrc/jq_host_select.h s_image_uniform).  With Hanti_k = a_k - a_k' on a 4 x 4 x n space every 16-row block of S(t) = sum_k q_k(t) Hanti_k
+csrc/jq_host_images.h s_image_uniform).  With Hanti_k = a_k - a_k' on a 4 x 4 x n space every 16-row block of S(t) = sum_k q_k(t) Hanti_k
 repeats block 0: the same 4 x 4 diagonal blocks, the same (i, i +- 4) couplings, one (i, i +- 16) coupling per pair of blocks.  The
 kernels read block 0 only when -- and only when -- that holds for the problem at hand."""
 import os
