@@ -46,7 +46,8 @@ extern "C" {
  *     vectors of one problem in one call), jq_eval_f_g_grad_batch (many control vectors x the nodes of one ensemble in one call),
  *     jq_traceobjgrad_drifts / jq_eval_f_g_grad_drifts (one control vector over an ensemble of arbitrary drift Hamiltonians in one call),
  *     jq_traceobjgrad_members / jq_eval_f_g_grad_members (... over members that differ in their drift, in a real mixing matrix of the
- *     controls -- amplitude miscalibration, crosstalk -- or in both). */
+ *     controls -- amplitude miscalibration, crosstalk -- or in both), jq_traceobj_jvp (the tangent of the discrete forward map along
+ *     directions of coefficient space: the reference's verbose && evaladjoint forward-sensitivity sweep). */
 #define JQ_ABI_VERSION 6
 
 #define JQ_MAX_CONTROLS 16 /* control Hamiltonians the fast kernels hold in registers; more: cooperative kernels (no limit)    */
@@ -342,9 +343,35 @@ int jq_state_history(jq_handle *h, const double *pcof, int32_t ncoeff, double *u
 /*
  * The whole verbose, evaladjoint = false call traceobjgrad(pcof0, params, wa, true, false) (return tuple
  * src/evalobjgrad.jl:1031) from ONE forward sweep: the history as above plus out4 = { objfv, primaryobjf,
- * secondaryobjf, traceInfidelity } of the same sweep (out4 may be NULL).
+ * secondaryobjf, traceInfidelity } of the same sweep (out4 may be NULL).  The verbose, evaladjoint = true call (return tuple :1028)
+ * is this call, jq_traceobjgrad and one jq_traceobj_jvp (below) along e_kpar.
  */
 int jq_traceobj_verbose(jq_handle *h, const double *pcof, int32_t ncoeff, double *out4, double *ur, double *ui);
+
+/*
+ * The tangent (Jacobian-vector product) of the discrete forward map at pcof along ndir directions of coefficient space -- what the
+ * verbose && evaladjoint branch of traceobjgrad computes along e_kpar with its forward-sensitivity sweep (src/evalobjgrad.jl:682-689,
+ * :723-745, :768-784, returned at :1028; step_fwdGrad!, src/StormerVerlet.jl:151-250), here for any direction and exact to rounding:
+ * a tangent-linear Stormer-Verlet sweep propagates (state, tangent) in dual-number arithmetic, differentiating the forward step as
+ * the device executes it, the truncated Neumann series included.
+ *   dirs : [ncoeff x ndir] column-major, one direction per column
+ *   out4 : the primal { objfv, primaryobjf, secondaryobjf, traceInfidelity } (no Tikhonov term)
+ *   dout : [3 x ndir] column-major: d(objfv), d(primaryobjf), d(secondaryobjf) along each direction, with
+ *          d(primaryobjf) = -2 Re(conj(s) sd), s = tr(Vtg' V)/N, sd = tr(Vtg' Vd)/N
+ *   wr,wi: [Ntot x N x ndir] each, real and imaginary part of d(vr - i vi)(T)/d(alpha) . d (the reference's wr1 - im wi); both NULL:
+ *          not wanted
+ * Direction j does not depend on the other directions of the call (the same operations in the same order).  Directions beyond what
+ * one launch holds next to the primal operator stream run in rounds; jq_plan_info reports "jvp": {directions_per_launch, chunk_steps,
+ * rounds} after a call, jq_last_timing the launches as the run-time-size kernels report theirs (family 1, tile rows, band 15).
+ * Served: the Stormer-Verlet integrator with the Neumann solver (order 0 included), Diagonal weights, coupled and uncoupled controls,
+ * any objFuncType and sv_type (the objective depends on neither), any Ntot and N, the handle's own drift.  Refused with
+ * JQ_EUNSUPPORTED, never served by something else: the implicit-midpoint integrator, the Jacobi solver (its stopping rule has no
+ * derivative), full leakage weights (jq_update_wmat).  JQ_EINVAL for NULL required pointers, ndir < 1 or exactly one of wr / wi; the
+ * codes of jq_traceobjgrad for the coefficient count.  A refused call writes nothing and leaves the handle as it was.  Multi-device
+ * handles run the call on their first device.
+ */
+int jq_traceobj_jvp(jq_handle *h, const double *pcof, int32_t ncoeff, const double *dirs, int32_t ndir, double *out4, double *dout,
+                    double *wr, double *wi);
 
 /*
  * Device-side consumers of the state history, so that the [Ntot x N x (nsteps+1)] arrays (199 MB at cnot3)

@@ -267,8 +267,20 @@ function traceobjgrad(pcof0::Array{Float64,1}, params::objparams, wa::AbstractWo
     sync!(wa, params)
     n = length(pcof0)
     out4 = zeros(4)
+    if verbose && evaladjoint
+        # the reference's forward-sensitivity self check (src/evalobjgrad.jl:1028) along e_kpar, from the adjoint call, the verbose call and
+        # one jq_traceobj_jvp: (objfv, totalgrad, unitaryhistory, fidelity, dfdp, wr1 - im wi).  dfdp = d(objfv)/d(alpha_kpar) without a
+        # Tikhonov term, as objfv is (the reference adds gr[kpar], :965, which at that point indexes the forcing work array)
+        params.sv_type == 1 || throw(ArgumentError("verbose && evaladjoint needs sv_type == 1 (src/evalobjgrad.jl:770 traces against dVds otherwise)"))
+        1 <= params.kpar <= n || throw(ArgumentError("params.kpar outside 1 .. length(pcof0)"))
+        objfv, totalgrad = traceobjgrad(pcof0, params, wa, false, true)[1:2]
+        _, hist, fidelity = traceobjgrad(pcof0, params, wa, true, false)
+        d = zeros(n)
+        d[params.kpar] = 1.0
+        r = traceobj_jvp(pcof0, d, params, wa, true)
+        return objfv, totalgrad, hist, fidelity, r.d_objfv[1], r.W[:, :, 1]
+    end
     if verbose                                              # plot_results path (plot-results.jl:44): ONE forward sweep
-        evaladjoint && error("verbose && evaladjoint (forward-gradient self check) is not accelerated")
         Ntot = params.N + params.Nguard
         ur = zeros(Ntot, params.N, params.nsteps + 1)
         ui = similar(ur)
@@ -283,6 +295,27 @@ function traceobjgrad(pcof0::Array{Float64,1}, params::objparams, wa::AbstractWo
                       wa.handle, pcof0, n, evaladjoint ? 1 : 0, out4, tg, ig, lg))
     evaladjoint || return out4[1], out4[2], out4[3]
     return out4[1], tg, out4[2], out4[3], out4[4], ig, (params.objFuncType == 1 ? zeros(0) : lg)
+end
+
+# The tangent (Jacobian-vector product) of the discrete forward map at pcof along the columns of dirs (jq_traceobj_jvp): a tangent-linear
+# Stormer-Verlet sweep, exact to rounding.  Returns (objfv, primaryobjf, secondaryobjf, d_objfv[ndir], d_primary[ndir], d_secondary[ndir],
+# W[Ntot, N, ndir] complex = d(vr - i vi)(T)/d(alpha) . d, or nothing without `final`).  Stormer-Verlet with the Neumann solver and Diagonal
+# weights; the library refuses the implicit-midpoint integrator, the Jacobi solver and full leakage weights.
+function traceobj_jvp(pcof::Vector{Float64}, dirs::VecOrMat{Float64}, params::objparams, wa::AbstractWorkingArraysHIP, final::Bool = true)
+    ncoeff = length(pcof)
+    D = dirs isa Vector ? reshape(dirs, :, 1) : Matrix{Float64}(dirs)
+    size(D, 1) == ncoeff || throw(DimensionMismatch("traceobj_jvp: dirs must have length(pcof) rows"))
+    nd = size(D, 2)
+    nd >= 1 || throw(ArgumentError("traceobj_jvp: need at least one direction"))
+    sync!(wa, params)
+    Ntot = params.N + params.Nguard
+    out4 = zeros(4); dout = zeros(3, nd)
+    wr = zeros(Ntot, params.N, final ? nd : 0); wi = similar(wr)
+    jqcheck(wa, ccall((:jq_traceobj_jvp, libjq), Cint,
+                      (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                      wa.handle, pcof, ncoeff, D, nd, out4, dout, final ? pointer(wr) : C_NULL, final ? pointer(wi) : C_NULL))
+    return (objfv = out4[1], primaryobjf = out4[2], secondaryobjf = out4[3], d_objfv = dout[1, :], d_primary = dout[2, :],
+            d_secondary = dout[3, :], W = final ? wr + 1im * wi : nothing)
 end
 
 # Many control vectors of ONE problem in one call (jq_traceobjgrad_batch): column i of every result is what

@@ -175,6 +175,9 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
     // "drift_batch", and what differed between its members -- their drifts, their control mixes
     kv("member_batch", std::string("{\"mode\": \"") + (h->mb_mode.empty() ? "none yet" : h->mb_mode) + "\", \"family\": " + num(h->mb_family) + ", \"members_per_launch\": " + num(h->mb_per_launch) +
                            ", \"reason\": \"" + h->mb_why + "\", \"drifts\": " + (h->mb_drifts ? "true" : "false") + ", \"ctrl_mix\": " + (h->mb_mix ? "true" : "false") + "}");
+    // jq_traceobj_jvp (after a call): directions one launch carried next to the primal stream, steps per chunk, launches' rounds
+    if (h->jvp_rounds > 0)
+        kv("jvp", std::string("{\"directions_per_launch\": ") + num(h->jvp_per_launch) + ", \"chunk_steps\": " + num(h->jvp_chunk) + ", \"rounds\": " + num(h->jvp_rounds) + "}");
     o += "}";
     if (buflen > 0) {
         const size_t n = std::min(o.size(), (size_t)buflen - 1);

@@ -122,5 +122,6 @@
     Y(v, JQ_SIZES_DENSE, JQ_INST_V_DENSE) Y(q, JQ_SIZES_QUAD8, JQ_INST_Q) Y(i, JQ_SIZES_I, JQ_INST_I)                   \
     Y(i, JQ_SIZES_C, JQ_INST_I_PARTS) Y(i, JQ_SIZES_HBM, JQ_INST_I_HBM) Y(m, JQ_SIZES_ROWLANE, JQ_INST_M)               \
     Y(r, JQ_SIZES_ROWLANE, JQ_INST_R) Y(l, JQ_SIZES_LANE, JQ_INST_L) Y(c, JQ_SIZES_C, JQ_INST_C)
-// the host translation unit's own propagator kernels beyond those of jq_huge_kernels.h (none: every instantiation has its object)
-#define JQ_INST_HOST(X)
+// the host translation unit's own propagator kernels beyond those of jq_huge_kernels.h: the tangent-linear forward sweep of
+// jq_tl_kernels.h (run-time size like them; every other instantiation has its object)
+#define JQ_INST_HOST(X) X(k_forward_tl)

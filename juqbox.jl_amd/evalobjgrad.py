@@ -18,6 +18,9 @@
                                         ... over members that differ in a real mixing matrix of the controls (amplitude
                                         miscalibration, crosstalk), in their drift, or in both (jq_traceobjgrad_members).
   amplitude_mix(scales)                 [nmember, Nc] amplitude factors -> the diagonal mixes of such an ensemble.
+  traceobj_jvp(pcof, dirs, params, wa, final=True)
+                                        the tangent of the discrete forward map along directions of coefficient space
+                                        (jq_traceobj_jvp): d(objective) and dV(T)/d(alpha) . d, exact to rounding.
   gradient_check(pcof0, params, wa, kpars, h=1e-6)
                                         adjoint gradient entries against central differences, from one batch.
 """
@@ -325,8 +328,14 @@ def traceobjgrad(pcof0, params: objparams, wa: Working_Arrays_HIP, verbose: bool
                                 infidelgrad, leakgrad)                                     (:1033)
     neither:                   (objfv, primaryobjf, secondaryobjf)                         (:1035)
     verbose (not evaladjoint): (objfv, unitaryhistory[Ntot,N,nsteps+1] complex, fidelity)  (:1031)
-    verbose and evaladjoint (the reference's forward-sensitivity self check, :1028) is out of scope; gradient_check() below is its
-    accelerated stand-in (adjoint entries against central differences, all from one traceobjgrad_batch call).
+    verbose and evaladjoint:   (objfv, totalgrad, unitaryhistory, fidelity, dfdp, wfinal[Ntot,N] complex)      (:1028)
+        the reference's forward-sensitivity self check along d = e_kpar (params.kpar is 1-based, :205), built from the adjoint call,
+        the verbose call and one jq_traceobj_jvp: totalgrad is bit-identical to the plain adjoint call, the history to the verbose
+        call, wfinal = d(vr - i vi)/d(alpha_kpar) (the reference's wr1 - im wi).  dfdp = d(objfv)/d(alpha_kpar) WITHOUT a Tikhonov term,
+        as objfv is: the reference adds gr[kpar] (:965), which at that point indexes the forcing work array -- a deviation on purpose.
+        ValueError for sv_type != 1 (the reference's salpha1 is then a trace against dVds, :770) and for kpar outside 1 .. ncoeff;
+        Stormer-Verlet with the Neumann solver and Diagonal weights only (traceobj_jvp).  gradient_check() below is the
+        finite-difference companion (adjoint entries against central differences, all from one traceobjgrad_batch call).
     objfv excludes the Tikhonov term (added by the Ipopt callbacks, src/ipopt_interface.jl:96-98).
     """
     if not isinstance(wa, Working_Arrays_HIP):
@@ -334,7 +343,7 @@ def traceobjgrad(pcof0, params: objparams, wa: Working_Arrays_HIP, verbose: bool
     if wa.params is not params:
         raise ValueError("traceobjgrad: wa was allocated for a different objparams")
     if verbose and evaladjoint:
-        raise NotImplementedError("verbose && evaladjoint (forward gradient self-check) is not accelerated")
+        return _traceobjgrad_selfcheck(pcof0, params, wa)
     L, h = _lib.load(), wa.handle
     pcof = _f64(pcof0)
     n = pcof.size
@@ -356,6 +365,77 @@ def traceobjgrad(pcof0, params: objparams, wa: Working_Arrays_HIP, verbose: bool
         return out4[0], tg, out4[1], out4[2], out4[3], ig, lg
     _lib.check(L.jq_traceobjgrad(h, _ptr(pcof), n, 0, _ptr(out4), None, None, None), h)
     return out4[0], out4[1], out4[2]
+
+
+def _traceobjgrad_selfcheck(pcof0, params, wa):
+    """traceobjgrad(pcof0, params, wa, True, True): the 6-tuple of src/evalobjgrad.jl:1028 (see traceobjgrad)"""
+    ncoeff = int(np.size(pcof0))
+    kpar = getattr(params, "kpar", 1)
+    if int(getattr(params, "sv_type", 1)) != 1:
+        raise ValueError("traceobjgrad: verbose && evaladjoint needs sv_type == 1 (with another type the reference takes the tangent's "
+                         "trace against dVds, src/evalobjgrad.jl:770)")
+    if int(kpar) != kpar or not 1 <= int(kpar) <= ncoeff:
+        raise ValueError("traceobjgrad: params.kpar = %r outside 1 .. %d" % (kpar, ncoeff))
+    objfv, totalgrad = traceobjgrad(pcof0, params, wa, False, True)[:2]
+    _, hist, fidelity = traceobjgrad(pcof0, params, wa, True, False)
+    d = np.zeros(ncoeff)
+    d[int(kpar) - 1] = 1.0
+    r = traceobj_jvp(pcof0, d, params, wa, final=True)
+    return objfv, totalgrad, hist, fidelity, float(r["d_objfv"][0]), r["W"][:, :, 0].copy()
+
+
+def _directions(dirs, ncoeff):
+    """dirs -> contiguous [ndir, ncoeff] array (one direction per row = the C ABI's column-major ncoeff x ndir).  A 1-D array or sequence
+    of numbers is one direction, a 2-D array holds one direction per COLUMN.  ValueError for everything else."""
+    try:
+        d = np.asarray(dirs, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("traceobj_jvp: dirs must be a vector or an ncoeff x ndir array of numbers (%s)" % e)
+    if d.ndim == 1:
+        d = d[:, None]
+    if d.ndim != 2:
+        raise ValueError("traceobj_jvp: dirs must be a vector or an ncoeff x ndir array, not %d-dimensional" % d.ndim)
+    if d.shape[0] != ncoeff or d.shape[1] < 1:
+        raise ValueError("traceobj_jvp: dirs has shape %r, expected (%d,) or (%d, ndir >= 1) (wa.nCoeff)" % (np.shape(dirs), ncoeff, ncoeff))
+    if not np.all(np.isfinite(d)):
+        raise ValueError("traceobj_jvp: dirs has an entry that is not finite")
+    return np.ascontiguousarray(d.T)
+
+
+def traceobj_jvp(pcof, dirs, params: objparams, wa: Working_Arrays_HIP, final: bool = True):
+    """The tangent (Jacobian-vector product) of the discrete forward map at pcof along directions of coefficient space, in one library
+    call (jq_traceobj_jvp): a tangent-linear Stormer-Verlet sweep that differentiates the forward step as the device executes it, the
+    truncated Neumann series included -- exact to rounding, where finite differences (gradient_check) agree to about 1e-7.
+
+    dirs: one direction (ncoeff numbers) or an ncoeff x ndir array, one direction per column.
+    Returns a dict: objfv, primaryobjf, secondaryobjf (the primal, no Tikhonov term), d_objfv[ndir], d_primary[ndir], d_secondary[ndir]
+    and, with final, W[Ntot, N, ndir] complex = d(vr - i vi)(T)/d(alpha) . d (the reference's wr1 - im wi, src/evalobjgrad.jl:1028).
+    Direction j does not depend on the other directions of the call.  Served: Stormer-Verlet with the Neumann solver, Diagonal weights,
+    coupled and uncoupled controls, any objFuncType and sv_type (the objective depends on neither); the library refuses the
+    implicit-midpoint integrator, the Jacobi solver and full leakage weights.  Shape errors raise ValueError before any library call."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("traceobj_jvp: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("traceobj_jvp: wa was allocated for a different objparams")
+    ncoeff = int(wa.nCoeff)
+    p = np.asarray(pcof, dtype=np.float64)
+    if p.ndim != 1 or p.size != ncoeff:
+        raise ValueError("traceobj_jvp: pcof has shape %r, expected (%d,) (wa.nCoeff)" % (p.shape, ncoeff))
+    D = _directions(dirs, ncoeff)
+    p = _f64(p)
+    nd = D.shape[0]
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    out4, dout = np.zeros(4), np.zeros((nd, 3))
+    shp = (int(params.Ntot), int(params.N), nd)
+    wr = np.zeros(int(np.prod(shp))) if final else None
+    wi = np.zeros_like(wr) if final else None
+    _lib.check(L.jq_traceobj_jvp(h, _ptr(p), ncoeff, _ptr(D), nd, _ptr(out4), _ptr(dout), _ptr(wr), _ptr(wi)), h)
+    r = {"objfv": out4[0], "primaryobjf": out4[1], "secondaryobjf": out4[2],
+         "d_objfv": dout[:, 0].copy(), "d_primary": dout[:, 1].copy(), "d_secondary": dout[:, 2].copy()}
+    if final:
+        r["W"] = wr.reshape(shp, order="F") + 1j * wi.reshape(shp, order="F")
+    return r
 
 
 def _pcof_columns(pcofs, ncoeff):
@@ -570,8 +650,8 @@ def traceobjgrad_members(pcof, params: objparams, wa: Working_Arrays_HIP, Hconst
 def gradient_check(pcof0, params: objparams, wa: Working_Arrays_HIP, kpars, h: float = 1e-6):
     """The adjoint gradient against central differences: returns (totalgrad[kpars], fd) with
     fd[j] = (f(p + h e_k) - f(p - h e_k)) / 2h for k = kpars[j], f = objfv.  All 2 len(kpars) + 1 evaluations are ONE
-    traceobjgrad_batch call (vector 0: p itself, then the + and - vector of every k).  The accelerated stand-in for the reference's
-    `verbose && evaladjoint` self check, which traceobjgrad refuses."""
+    traceobjgrad_batch call (vector 0: p itself, then the + and - vector of every k).  A finite-difference companion of the reference's
+    `verbose && evaladjoint` self check, which traceobjgrad serves with the exact tangent (traceobj_jvp)."""
     p0 = np.asarray(pcof0, dtype=np.float64).ravel()
     ks = [int(k) for k in np.atleast_1d(kpars)]
     if p0.size != int(wa.nCoeff):
