@@ -47,7 +47,8 @@ extern "C" {
  *     jq_traceobjgrad_drifts / jq_eval_f_g_grad_drifts (one control vector over an ensemble of arbitrary drift Hamiltonians in one call),
  *     jq_traceobjgrad_members / jq_eval_f_g_grad_members (... over members that differ in their drift, in a real mixing matrix of the
  *     controls -- amplitude miscalibration, crosstalk -- or in both), jq_traceobj_jvp (the tangent of the discrete forward map along
- *     directions of coefficient space: the reference's verbose && evaladjoint forward-sensitivity sweep). */
+ *     directions of coefficient space: the reference's verbose && evaladjoint forward-sensitivity sweep), jq_traceobjgrad_hvp (the
+ *     derivative of the gradient along directions of coefficient space: Hessian-vector products). */
 #define JQ_ABI_VERSION 6
 
 #define JQ_MAX_CONTROLS 16 /* control Hamiltonians the fast kernels hold in registers; more: cooperative kernels (no limit)    */
@@ -372,6 +373,33 @@ int jq_traceobj_verbose(jq_handle *h, const double *pcof, int32_t ncoeff, double
  */
 int jq_traceobj_jvp(jq_handle *h, const double *pcof, int32_t ncoeff, const double *dirs, int32_t ndir, double *out4, double *dout,
                     double *wr, double *wi);
+
+/*
+ * The gradient at pcof and its derivative along ndir directions of coefficient space (Hessian-vector products; the reference has no
+ * second-order path):
+ *   hv(alpha; d) = d/d eps totalgrad(alpha + eps d) at eps = 0,
+ * the exact derivative of the gradient jq_traceobjgrad returns, obtained by differentiating the backward sweep as the device executes
+ * it (tangent-linear forward sweep as jq_traceobj_jvp, then the adjoint step in dual-number arithmetic, truncated Neumann series
+ * included).  This is the Hessian of the discrete objective only as far as that gradient is its gradient: the adjoint is the exact
+ * transpose of the forward scheme for exact linear solves, with a truncated series the operator is not symmetric at truncation level
+ * (|e.Jd - d.Je| / |e.Jd| on random 7-step problems: order 0 1e-1 .. 7e-1, order 1 1e-3 .. 2e-2, order 4 4e-7 .. 4e-4, order 20 1e-15 .. 3e-14).
+ * Callers who need a symmetric operator symmetrise it or raise the order; the library does not symmetrise silently.
+ *   dirs     : [ncoeff x ndir] column-major, one direction per column
+ *   out4     : the primal { objfv, primaryobjf, secondaryobjf, traceInfidelity } (no Tikhonov term), as jq_traceobj_jvp
+ *   grad     : [ncoeff] totalgrad
+ *   hv       : [ncoeff x ndir] column-major: d(totalgrad) along each direction (no Tikhonov term, like totalgrad)
+ *   hv_infid : NULL, or [ncoeff x ndir]: the same for infidelgrad (objFuncType != 1: an unforced second backward pass; objFuncType 1:
+ *              infidelgrad is totalgrad, so is this)
+ * Direction j does not depend on the other directions of the call nor on the rounds they run in (jq_plan_info "hvp":
+ * {directions_per_launch, chunk_steps, rounds} after a call; jq_last_timing counts forward and backward launches).  More than four
+ * controls run in control groups.  Served: the Stormer-Verlet integrator with the Neumann solver (order 0 included), Diagonal weights,
+ * coupled controls, sv_type 1, any objFuncType, Ntot and N, the handle's own drift.  Refused with JQ_EUNSUPPORTED: the
+ * implicit-midpoint integrator, the Jacobi solver, full leakage weights (jq_update_wmat), sv_type != 1, uncoupled controls.
+ * JQ_EINVAL for NULL required pointers or ndir < 1; the codes of jq_traceobjgrad for the coefficient count.  A refused call writes
+ * nothing and leaves the handle as it was.  Multi-device handles run the call on their first device.
+ */
+int jq_traceobjgrad_hvp(jq_handle *h, const double *pcof, int32_t ncoeff, const double *dirs, int32_t ndir, double *out4, double *grad,
+                        double *hv, double *hv_infid);
 
 /*
  * Device-side consumers of the state history, so that the [Ntot x N x (nsteps+1)] arrays (199 MB at cnot3)

@@ -318,6 +318,33 @@ function traceobj_jvp(pcof::Vector{Float64}, dirs::VecOrMat{Float64}, params::ob
             d_secondary = dout[3, :], W = final ? wr + 1im * wi : nothing)
 end
 
+# The gradient at pcof and its derivative along the columns of dirs (jq_traceobjgrad_hvp; Hessian-vector products): hv[:, j] =
+# d/d eps totalgrad(pcof + eps dirs[:, j]) at eps = 0, the exact derivative of the gradient the library returns -- not symmetric at truncation
+# level of the Neumann series; symmetrise it or raise the order where a symmetric operator is needed.  Returns (objfv, primaryobjf,
+# secondaryobjf, totalgrad[ncoeff], hv[ncoeff, ndir], hv_infid and hv_leak = hv - hv_infid for objFuncType != 1, else nothing).  No Tikhonov
+# term.  Stormer-Verlet with the Neumann solver, Diagonal weights, coupled controls and sv_type 1; the library refuses everything else.
+function traceobjgrad_hvp(pcof::Vector{Float64}, dirs::VecOrMat{Float64}, params::objparams, wa::AbstractWorkingArraysHIP)
+    ncoeff = length(pcof)
+    D = dirs isa Vector ? reshape(dirs, :, 1) : Matrix{Float64}(dirs)
+    size(D, 1) == ncoeff || throw(DimensionMismatch("traceobjgrad_hvp: dirs must have length(pcof) rows"))
+    nd = size(D, 2)
+    nd >= 1 || throw(ArgumentError("traceobjgrad_hvp: need at least one direction"))
+    sync!(wa, params)
+    two = params.objFuncType != 1
+    out4 = zeros(4); tg = zeros(ncoeff); hv = zeros(ncoeff, nd); hvi = zeros(ncoeff, two ? nd : 0)
+    jqcheck(wa, ccall((:jq_traceobjgrad_hvp, libjq), Cint,
+                      (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                      wa.handle, pcof, ncoeff, D, nd, out4, tg, hv, two ? pointer(hvi) : C_NULL))
+    return (objfv = out4[1], primaryobjf = out4[2], secondaryobjf = out4[3], totalgrad = tg, hv = hv,
+            hv_infid = two ? hvi : nothing, hv_leak = two ? hv - hvi : nothing)
+end
+
+# All unit directions through one traceobjgrad_hvp call: the ncoeff x ncoeff Jacobian of totalgrad, (J + J')/2 with symmetrize.
+function hessian(pcof::Vector{Float64}, params::objparams, wa::AbstractWorkingArraysHIP, symmetrize::Bool = false)
+    J = traceobjgrad_hvp(pcof, Matrix{Float64}(LinearAlgebra.I, length(pcof), length(pcof)), params, wa).hv
+    return symmetrize ? (J + J') / 2 : J
+end
+
 # Many control vectors of ONE problem in one call (jq_traceobjgrad_batch): column i of every result is what
 # traceobjgrad(pcofs[:, i], params, wa, false, evaladjoint) returns.  On the latency kernels (row-lane, cooperative quad; Stormer-Verlet)
 # the vectors share launches, elsewhere they run one after the other inside the call.

@@ -178,6 +178,9 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
     // jq_traceobj_jvp (after a call): directions one launch carried next to the primal stream, steps per chunk, launches' rounds
     if (h->jvp_rounds > 0)
         kv("jvp", std::string("{\"directions_per_launch\": ") + num(h->jvp_per_launch) + ", \"chunk_steps\": " + num(h->jvp_chunk) + ", \"rounds\": " + num(h->jvp_rounds) + "}");
+    // jq_traceobjgrad_hvp (after a call): the same three of its launches, forward and backward
+    if (h->hvp_rounds > 0)
+        kv("hvp", std::string("{\"directions_per_launch\": ") + num(h->hvp_per_launch) + ", \"chunk_steps\": " + num(h->hvp_chunk) + ", \"rounds\": " + num(h->hvp_rounds) + "}");
     o += "}";
     if (buflen > 0) {
         const size_t n = std::min(o.size(), (size_t)buflen - 1);

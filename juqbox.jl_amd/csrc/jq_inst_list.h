@@ -123,5 +123,6 @@
     Y(i, JQ_SIZES_C, JQ_INST_I_PARTS) Y(i, JQ_SIZES_HBM, JQ_INST_I_HBM) Y(m, JQ_SIZES_ROWLANE, JQ_INST_M)               \
     Y(r, JQ_SIZES_ROWLANE, JQ_INST_R) Y(l, JQ_SIZES_LANE, JQ_INST_L) Y(c, JQ_SIZES_C, JQ_INST_C)
 // the host translation unit's own propagator kernels beyond those of jq_huge_kernels.h: the tangent-linear forward sweep of
-// jq_tl_kernels.h (run-time size like them; every other instantiation has its object)
-#define JQ_INST_HOST(X) X(k_forward_tl)
+// jq_tl_kernels.h and the tangent of the adjoint sweep of jq_tl_adjoint_kernels.h (run-time size like them; every other instantiation
+// has its object)
+#define JQ_INST_HOST(X) X(k_forward_tl) X(k_backward_tl)

@@ -15,6 +15,7 @@
 #include "jq_coop_imr_kernels.h"
 #include "jq_huge_kernels.h"
 #include "jq_tl_kernels.h"
+#include "jq_tl_adjoint_kernels.h"
 #include "jq_options.h"
 
 #include <rccl/rccl.h>   // types and prototypes only: librccl is loaded at run time by jq_create_multi (load_rccl)
@@ -188,6 +189,8 @@ struct jq_handle {
     bool mb_drifts = false, mb_mix = false;
     // ... and the last jq_traceobj_jvp: directions per launch, chunk length, rounds (jq_plan_info "jvp"; rounds 0: no call yet)
     int jvp_per_launch = 0, jvp_chunk = 0, jvp_rounds = 0;
+    // ... and the last jq_traceobjgrad_hvp, the same three (jq_plan_info "hvp")
+    int hvp_per_launch = 0, hvp_chunk = 0, hvp_rounds = 0;
     // Structure embedding (try_embed): a second handle of the SAME problem with its two fastest Kronecker factors zero-padded
     // to 4 levels each (row i1 + d1 i2 + d1 d2 i3 -> i1 + 4 i2 + 16 i3), under which the operators have the JQ_BW_T4 structure;
     // batches that would otherwise run on the dense / band MFMA kernels go there (quad-layout / JQ_BW_T4 slab kernels).
@@ -703,6 +706,7 @@ extern "C" int jq_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int32_t
 }
 
 #include "jq_host_jvp.h"      // jq_traceobj_jvp: the tangent of the forward map along directions of coefficient space
+#include "jq_host_hvp.h"      // jq_traceobjgrad_hvp: the derivative of the gradient along directions of coefficient space
 #include "jq_host_multi.h"      // multi-device handles: one process, N GPUs, one RCCL all-reduce
 #include "jq_host_info.h"      // options of a live handle, plan and timing introspection
 #ifdef JQ_DUMP_SELECTION

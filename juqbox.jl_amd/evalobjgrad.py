@@ -21,6 +21,11 @@
   traceobj_jvp(pcof, dirs, params, wa, final=True)
                                         the tangent of the discrete forward map along directions of coefficient space
                                         (jq_traceobj_jvp): d(objective) and dV(T)/d(alpha) . d, exact to rounding.
+  traceobjgrad_hvp(pcof, dirs, params, wa)
+                                        the gradient and its derivative along directions of coefficient space
+                                        (jq_traceobjgrad_hvp): Hessian-vector products, exact to rounding.
+  hessian(pcof, params, wa, symmetrize=False)
+                                        all unit directions through one traceobjgrad_hvp call.
   gradient_check(pcof0, params, wa, kpars, h=1e-6)
                                         adjoint gradient entries against central differences, from one batch.
 """
@@ -384,21 +389,21 @@ def _traceobjgrad_selfcheck(pcof0, params, wa):
     return objfv, totalgrad, hist, fidelity, float(r["d_objfv"][0]), r["W"][:, :, 0].copy()
 
 
-def _directions(dirs, ncoeff):
+def _directions(dirs, ncoeff, who="traceobj_jvp"):
     """dirs -> contiguous [ndir, ncoeff] array (one direction per row = the C ABI's column-major ncoeff x ndir).  A 1-D array or sequence
-    of numbers is one direction, a 2-D array holds one direction per COLUMN.  ValueError for everything else."""
+    of numbers is one direction, a 2-D array holds one direction per COLUMN.  ValueError (in the name of `who`) for everything else."""
     try:
         d = np.asarray(dirs, dtype=np.float64)
     except (TypeError, ValueError) as e:
-        raise ValueError("traceobj_jvp: dirs must be a vector or an ncoeff x ndir array of numbers (%s)" % e)
+        raise ValueError("%s: dirs must be a vector or an ncoeff x ndir array of numbers (%s)" % (who, e))
     if d.ndim == 1:
         d = d[:, None]
     if d.ndim != 2:
-        raise ValueError("traceobj_jvp: dirs must be a vector or an ncoeff x ndir array, not %d-dimensional" % d.ndim)
+        raise ValueError("%s: dirs must be a vector or an ncoeff x ndir array, not %d-dimensional" % (who, d.ndim))
     if d.shape[0] != ncoeff or d.shape[1] < 1:
-        raise ValueError("traceobj_jvp: dirs has shape %r, expected (%d,) or (%d, ndir >= 1) (wa.nCoeff)" % (np.shape(dirs), ncoeff, ncoeff))
+        raise ValueError("%s: dirs has shape %r, expected (%d,) or (%d, ndir >= 1) (wa.nCoeff)" % (who, np.shape(dirs), ncoeff, ncoeff))
     if not np.all(np.isfinite(d)):
-        raise ValueError("traceobj_jvp: dirs has an entry that is not finite")
+        raise ValueError("%s: dirs has an entry that is not finite" % who)
     return np.ascontiguousarray(d.T)
 
 
@@ -436,6 +441,53 @@ def traceobj_jvp(pcof, dirs, params: objparams, wa: Working_Arrays_HIP, final: b
     if final:
         r["W"] = wr.reshape(shp, order="F") + 1j * wi.reshape(shp, order="F")
     return r
+
+
+def traceobjgrad_hvp(pcof, dirs, params: objparams, wa: Working_Arrays_HIP):
+    """The gradient at pcof and its derivative along directions of coefficient space (Hessian-vector products) in one library call
+    (jq_traceobjgrad_hvp):  hv[:, j] = d/d eps totalgrad(pcof + eps dirs[:, j]) at eps = 0, the exact derivative of the gradient
+    traceobjgrad returns -- the backward sweep differentiated as the device executes it, truncated Neumann series included.  It is
+    the Hessian of the discrete objective only as far as that gradient is its gradient: with a truncated series it is not symmetric
+    at truncation level (order 0: 1e-1 .. 7e-1, order 4: 4e-7 .. 4e-4 relative, order 20: rounding); symmetrise it or raise the order where a
+    symmetric operator is needed (hessian(..., symmetrize=True)).
+
+    dirs: one direction (ncoeff numbers) or an ncoeff x ndir array, one direction per column (what traceobj_jvp accepts).
+    Returns a dict: objfv, primaryobjf, secondaryobjf, totalgrad[ncoeff], hv[ncoeff, ndir] -- none with a Tikhonov term -- and for
+    objFuncType != 1 hv_infid (the same for infidelgrad) and hv_leak = hv - hv_infid.  Direction j does not depend on the other
+    directions of the call.  Served: Stormer-Verlet with the Neumann solver, Diagonal weights, coupled controls, sv_type 1; the library
+    refuses the implicit-midpoint integrator, the Jacobi solver, full leakage weights, sv_type != 1 and uncoupled controls.  Shape
+    errors raise ValueError before any library call."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("traceobjgrad_hvp: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("traceobjgrad_hvp: wa was allocated for a different objparams")
+    ncoeff = int(wa.nCoeff)
+    p = np.asarray(pcof, dtype=np.float64)
+    if p.ndim != 1 or p.size != ncoeff:
+        raise ValueError("traceobjgrad_hvp: pcof has shape %r, expected (%d,) (wa.nCoeff)" % (p.shape, ncoeff))
+    D = _directions(dirs, ncoeff, "traceobjgrad_hvp")
+    p = _f64(p)
+    nd = D.shape[0]
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    two = params.objFuncType != 1
+    out4, grad, hv = np.zeros(4), np.zeros(ncoeff), np.zeros((nd, ncoeff))
+    hvi = np.zeros((nd, ncoeff)) if two else None
+    _lib.check(L.jq_traceobjgrad_hvp(h, _ptr(p), ncoeff, _ptr(D), nd, _ptr(out4), _ptr(grad), _ptr(hv), _ptr(hvi)), h)
+    r = {"objfv": out4[0], "primaryobjf": out4[1], "secondaryobjf": out4[2], "totalgrad": grad, "hv": hv.T.copy()}
+    if two:
+        r["hv_infid"] = hvi.T.copy()
+        r["hv_leak"] = r["hv"] - r["hv_infid"]
+    return r
+
+
+def hessian(pcof, params: objparams, wa: Working_Arrays_HIP, symmetrize: bool = False):
+    """The ncoeff x ncoeff Jacobian of totalgrad at pcof: all unit directions through one traceobjgrad_hvp call, column j = hv along
+    e_j.  Not symmetric at truncation level of the Neumann series (traceobjgrad_hvp); symmetrize=True returns (J + J')/2."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("hessian: wa must be a Working_Arrays_HIP")
+    J = traceobjgrad_hvp(pcof, np.eye(int(wa.nCoeff)), params, wa)["hv"]
+    return 0.5 * (J + J.T) if symmetrize else J
 
 
 def _pcof_columns(pcofs, ncoeff):
