@@ -48,7 +48,8 @@ extern "C" {
  *     jq_traceobjgrad_members / jq_eval_f_g_grad_members (... over members that differ in their drift, in a real mixing matrix of the
  *     controls -- amplitude miscalibration, crosstalk -- or in both), jq_traceobj_jvp (the tangent of the discrete forward map along
  *     directions of coefficient space: the reference's verbose && evaladjoint forward-sensitivity sweep), jq_traceobjgrad_hvp (the
- *     derivative of the gradient along directions of coefficient space: Hessian-vector products). */
+ *     derivative of the gradient along directions of coefficient space: Hessian-vector products), jq_eval_f_g_grad_hvp (the same for
+ *     the two gradients of a risk-neutral ensemble: the nodes in the lanes, the directions in the grid). */
 #define JQ_ABI_VERSION 6
 
 #define JQ_MAX_CONTROLS 16 /* control Hamiltonians the fast kernels hold in registers; more: cooperative kernels (no limit)    */
@@ -400,6 +401,31 @@ int jq_traceobj_jvp(jq_handle *h, const double *pcof, int32_t ncoeff, const doub
  */
 int jq_traceobjgrad_hvp(jq_handle *h, const double *pcof, int32_t ncoeff, const double *dirs, int32_t ndir, double *out4, double *grad,
                         double *hv, double *hv_infid);
+
+/*
+ * jq_eval_f_g_grad and the derivative of its two gradients along ndir directions of coefficient space: Hessian-vector products of a
+ * risk-neutral ensemble (the objective of eval_f_g_grad!, src/ipopt_interface.jl:24-70),
+ *   hv_infid[:, j] = sum_i w_i d/d eps infidelgrad_i(alpha + eps d_j),  hv_leak[:, j] = sum_i w_i d/d eps leakgrad_i(alpha + eps d_j)  at eps = 0,
+ * node i being the evaluation with Hconst + nodes[i] diag(shift).  Exact derivatives of the gradients jq_eval_f_g_grad returns, truncated
+ * Neumann series included: not symmetric at truncation level, and the library does not symmetrise silently (jq_traceobjgrad_hvp).
+ *   dirs     : [ncoeff x ndir] column-major, one direction per column
+ *   nodes, weights : [nquad]; shift : [Ntot] or NULL (the reference's 0.01 * 10^(j-2))
+ *   out2, infid_grad, leak_grad : as jq_eval_f_g_grad with compute_adjoint (objFuncType 1: infid_grad carries totalgrad, leak_grad zeros)
+ *   hv_infid, hv_leak : [ncoeff x ndir] column-major (objFuncType 1: hv_infid carries the derivative of totalgrad, hv_leak zeros)
+ * Lane route: Ntot <= 6 with at most four controls (and option lane != 0) runs on the tangent-linear lane kernels -- all N nquad columns
+ * x the directions of a round in ONE launch per chunk, independent of the options lane_min / lane_max (one node is served too).
+ * Sequential route: everything else jq_traceobjgrad_hvp serves (Ntot 7 and 8 included: their tangent kernel would spill) runs the nodes
+ * one after the other on its run-time-size sweeps -- correct and no faster.  Direction j does not depend on the other directions of the
+ * call nor on the rounds they run in (option stream_bytes).  jq_plan_info "ens_hvp": {route: "lane" | "sequential",
+ * directions_per_launch, chunk_steps, rounds} after a call; jq_last_timing reports the lane family and NP on the lane route and counts
+ * forward and backward launches; "last_kernels" names the instantiations.  Refused with JQ_EUNSUPPORTED: what jq_traceobjgrad_hvp
+ * refuses (implicit midpoint, the Jacobi solver, full leakage weights, sv_type != 1, uncoupled controls).  JQ_EINVAL for NULL pointers
+ * (all but shift are required), ndir < 1 or nquad < 1; the codes of jq_traceobjgrad for the coefficient count.  A refused call writes
+ * nothing and leaves the handle as it was.  Multi-device handles run the call on their first device.
+ */
+int jq_eval_f_g_grad_hvp(jq_handle *h, const double *pcof, int32_t ncoeff, const double *dirs, int32_t ndir, const double *nodes,
+                         const double *weights, int32_t nquad, const double *shift, double *out2, double *infid_grad, double *leak_grad,
+                         double *hv_infid, double *hv_leak);
 
 /*
  * Device-side consumers of the state history, so that the [Ntot x N x (nsteps+1)] arrays (199 MB at cnot3)

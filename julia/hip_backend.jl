@@ -339,6 +339,29 @@ function traceobjgrad_hvp(pcof::Vector{Float64}, dirs::VecOrMat{Float64}, params
             hv_infid = two ? hvi : nothing, hv_leak = two ? hv - hvi : nothing)
 end
 
+# eval_f_g_grad over the quadrature nodes and the derivative of its two gradients along the columns of dirs (jq_eval_f_g_grad_hvp):
+# Hessian-vector products of the risk-neutral objective, sum_i w_i d/d eps grad_i(pcof + eps dirs[:, j]).  Ntot <= 6 with at most four
+# controls: tangent-linear lane kernels, every node and direction of a round in one launch per chunk; else the nodes one after the other.
+# Returns (infidelity, leak, infid_grad[ncoeff], leak_grad[ncoeff], hv_infid[ncoeff, ndir], hv_leak[ncoeff, ndir]); objFuncType == 1:
+# infid_grad / hv_infid carry the total gradient's, leak_grad / hv_leak are zero.  No Tikhonov term.
+function eval_f_g_grad_hvp(pcof::Vector{Float64}, dirs::VecOrMat{Float64}, params::objparams, wa::AbstractWorkingArraysHIP,
+                           nodes::Vector{Float64} = [0.0], weights::Vector{Float64} = [1.0], shift::Union{Nothing, Vector{Float64}} = nothing)
+    ncoeff = length(pcof)
+    D = dirs isa Vector ? reshape(dirs, :, 1) : Matrix{Float64}(dirs)
+    size(D, 1) == ncoeff || throw(DimensionMismatch("eval_f_g_grad_hvp: dirs must have length(pcof) rows"))
+    nd = size(D, 2)
+    nd >= 1 || throw(ArgumentError("eval_f_g_grad_hvp: need at least one direction"))
+    nq = length(nodes)
+    (nq >= 1 && length(weights) == nq) || throw(ArgumentError("eval_f_g_grad_hvp: nodes and weights must have the same length >= 1"))
+    sync!(wa, params)
+    out2 = zeros(2); ig = zeros(ncoeff); lg = zeros(ncoeff); hvi = zeros(ncoeff, nd); hvl = zeros(ncoeff, nd)
+    jqcheck(wa, ccall((:jq_eval_f_g_grad_hvp, libjq), Cint,
+                      (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64},
+                       Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                      wa.handle, pcof, ncoeff, D, nd, nodes, weights, nq, shift === nothing ? C_NULL : pointer(shift), out2, ig, lg, hvi, hvl))
+    return (infidelity = out2[1], leak = out2[2], infid_grad = ig, leak_grad = lg, hv_infid = hvi, hv_leak = hvl)
+end
+
 # All unit directions through one traceobjgrad_hvp call: the ncoeff x ncoeff Jacobian of totalgrad, (J + J')/2 with symmetrize.
 function hessian(pcof::Vector{Float64}, params::objparams, wa::AbstractWorkingArraysHIP, symmetrize::Bool = false)
     J = traceobjgrad_hvp(pcof, Matrix{Float64}(LinearAlgebra.I, length(pcof), length(pcof)), params, wa).hv

@@ -12,7 +12,10 @@
 // the tangent records into hv.  More controls than JQ_MAXNC run in control groups, the infidelity part (hv_infid) in an unforced second
 // pass, each sweep from the saved terminal state.  A direction's arithmetic does not depend on the launch it rides in.  Like the JVP
 // the call plans nothing and frees what it allocates; the backward work area and state file are about twice the forward's.
-static int hvp_run(jq_handle* h, const double* pcof, int ncoeff, const double* dirs, int ndir, double* out4, double* grad, double* hv, double* hv_infid)
+// drift: the Ntot x Ntot drift Hamiltonian of the sweeps (column-major; jq_traceobjgrad_hvp: the handle's, jq_eval_f_g_grad_hvp's sequential
+// route: a node's).  grad_infid (may be NULL): the gradient of the unforced pass where there is one, else the gradient.
+static int hvp_run(jq_handle* h, const double* drift, const double* pcof, int ncoeff, const double* dirs, int ndir, double* out4, double* grad, double* hv,
+                   double* hv_infid, double* grad_infid = nullptr)
 {
     HIPCHK(h, hipSetDevice(h->device));
     const int NT = (h->Ntot + 15) / 16, KT = 4 * NT, Nc = h->Nc, parts = h->parts;
@@ -42,7 +45,7 @@ static int hvp_run(jq_handle* h, const double* pcof, int ncoeff, const double* d
     // operator images [H0 | Hsym_q | Hanti_q], the trace images in control-group order (upload_operators), the drift images of the
     // groups [H0 | 0 ...], tables
     std::vector<double> img((size_t)(1 + 2 * Nc) * stride, 0.0), cimg((size_t)2 * Nc * stride);
-    tile_image_coop(h->Hconst.data(), h->Ntot, NT, 15, img.data());
+    tile_image_coop(drift, h->Ntot, NT, 15, img.data());
     for (int q = 0; q < Nc; ++q) {
         tile_image_coop(h->Hsym.data() + q * nn, h->Ntot, NT, 15, img.data() + (size_t)(1 + q) * stride);
         tile_image_coop(h->Hanti.data() + q * nn, h->Ntot, NT, 15, img.data() + (size_t)(1 + Nc + q) * stride);
@@ -176,6 +179,7 @@ static int hvp_run(jq_handle* h, const double* pcof, int ncoeff, const double* d
         if (r == 0) {
             std::copy_n(res.begin(), 4, res0.begin());      // (the primal of the first direction's workgroups: every direction recomputes the same)
             std::copy_n(gbuf.begin(), ncoeff, grad);
+            if (grad_infid) std::copy_n(gbuf.begin() + (size_t)(two_pass ? nvec : 0) * ncoeff, ncoeff, grad_infid);
         }
         for (int j = 0; j < nd; ++j) {
             std::copy_n(gbuf.begin() + (size_t)(1 + j) * ncoeff, ncoeff, hv + (size_t)(j0 + j) * ncoeff);
@@ -245,6 +249,6 @@ extern "C" int jq_traceobjgrad_hvp(jq_handle* h, const double* pcof, int32_t nco
                 --g_eval_depth;
             }
         } leave{gate, outer};
-        return hvp_run(h, pcof, ncoeff, dirs, ndir, out4, grad, hv, hv_infid);
+        return hvp_run(h, h->Hconst.data(), pcof, ncoeff, dirs, ndir, out4, grad, hv, hv_infid);
     });
 }

@@ -1,7 +1,7 @@
 // One translation unit per (NT, BW, variant) object of the propagator kernels (parallel builds, and the MFMA register form can be
 // chosen per object -- see Makefile).  What an object instantiates is listed in jq_inst_list.h; this file applies the list.
 //   JQ_VARIANT 0: slab kernels, Neumann   1: slab kernels, Jacobi   2: cooperative (row-split) kernels
-//              3: lane kernels (one lane per column; JQ_NT = padded Hilbert dimension NP, JQ_BW unused)
+//              3: lane kernels (one lane per column; JQ_NT = padded Hilbert dimension NP, JQ_BW unused) and their tangent-linear twins
 //              6: cooperative kernels of the implicit-midpoint integrator
 //              7: quad-layout kernels of the implicit-midpoint integrator (JQ_BW = 7)
 //              8: quad-layout slab kernels with 1 and 2 slabs per workgroup (JQ_BW = 7; variant 0 holds the 3-slab ones)
@@ -57,12 +57,15 @@ JQ_INST_M(JQ_DEF, JQ_NT)
 #include "jq_rowlane_kernels.h"
 JQ_INST_R(JQ_DEF, JQ_NT)
 #elif JQ_VARIANT == 3
-#include "jq_lane_kernels.h"
+#include "jq_lane_tl_kernels.h"
 #define JQ_DEF_INIT(name, ...) template __global__ void name<__VA_ARGS__>(JQ_LANE_INIT_ARGS);
 #define JQ_DEF_TERM(name, ...) template __global__ void name<__VA_ARGS__>(JQ_LANE_TERM_ARGS);
 JQ_INST_L(JQ_DEF, JQ_NT)
 JQ_INST_L_INIT(JQ_DEF_INIT, JQ_NT)
 JQ_INST_L_TERM(JQ_DEF_TERM, JQ_NT)
+#if JQ_NT <= 6                    // (JQ_SIZES_LANE_TL: NP = 8 spills; jq_eval_f_g_grad_hvp runs it on the sequential route)
+JQ_INST_L_TL(JQ_DEF, JQ_NT)
+#endif
 #elif JQ_VARIANT == 2
 #include "jq_coop_kernels.h"
 JQ_INST_C(JQ_DEF, JQ_NT, JQ_BW)

@@ -5,7 +5,7 @@ signatures, so any L-BFGS driver can call them)."""
 import numpy as np
 
 from . import _lib
-from .evalobjgrad import Working_Arrays_HIP, _drift_members, _f64, _members, _pcof_columns, _ptr
+from .evalobjgrad import Working_Arrays_HIP, _directions, _drift_members, _f64, _members, _pcof_columns, _ptr
 from .setup_utils import tikhonov_grad, tikhonov_pen
 
 
@@ -196,6 +196,71 @@ def eval_f_g_grad_batch(pcofs, params, wa, nodes, weights, compute_adjoint=True,
     if per_node:
         res += (np.ascontiguousarray(node_out.transpose(2, 1, 0)),)
     return res
+
+
+def eval_f_g_grad_hvp(pcof, dirs, params, wa, nodes=(0.0,), weights=(1.0,), shift=None):
+    """eval_f_g_grad over the quadrature nodes and the derivative of its two gradients along the columns of dirs in one library call
+    (jq_eval_f_g_grad_hvp): Hessian-vector products of the risk-neutral objective, sum_i w_i d/d eps grad_i(pcof + eps dirs[:, j]) at
+    eps = 0 -- exact derivatives of the gradients eval_f_g_grad returns, truncated Neumann series included (not symmetric at truncation
+    level, traceobjgrad_hvp).  Ntot <= 6 with at most four controls: tangent-linear lane kernels, every node and every direction of a
+    round in ONE launch per chunk; everything else traceobjgrad_hvp serves: the nodes one after the other
+    (wa.plan_info()["ens_hvp"]["route"] says which).
+
+    dirs: an ncoeff x ndir array (one direction per column) or a single vector.  Returns a dict: infidelity, leak, infid_grad[ncoeff],
+    leak_grad[ncoeff] (as eval_f_g_grad leaves them in params.last_*; objFuncType == 1: infid_grad is the total gradient, leak_grad
+    zeros), hv_infid[ncoeff, ndir], hv_leak[ncoeff, ndir] (objFuncType == 1: hv_infid is the derivative of the total gradient, hv_leak
+    zeros).  No Tikhonov term; params.last_* are left alone.  Shape errors raise ValueError before any library call."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("eval_f_g_grad_hvp: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("eval_f_g_grad_hvp: wa was allocated for a different objparams")
+    ncoeff = int(wa.nCoeff)
+    try:
+        p = np.asarray(pcof, dtype=np.float64)
+        nodes, weights = np.asarray(nodes, dtype=np.float64), np.asarray(weights, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("eval_f_g_grad_hvp: pcof, nodes and weights must be vectors of numbers (%s)" % e)
+    if p.ndim != 1 or p.size != ncoeff:
+        raise ValueError("eval_f_g_grad_hvp: pcof has shape %r, expected (%d,) (wa.nCoeff)" % (p.shape, ncoeff))
+    if nodes.ndim != 1 or weights.ndim != 1 or nodes.size != weights.size:
+        raise ValueError("eval_f_g_grad_hvp: nodes and weights must be vectors of the same length, not %r and %r" % (nodes.shape, weights.shape))
+    if nodes.size < 1:
+        raise ValueError("eval_f_g_grad_hvp: need at least one node")
+    D = _directions(dirs, ncoeff, "eval_f_g_grad_hvp")
+    sh = None
+    if shift is not None:
+        if np.shape(shift) != (int(params.Ntot),):
+            raise ValueError("eval_f_g_grad_hvp: shift must have one entry per level, not shape %r" % (np.shape(shift),))
+        sh = _f64(shift)
+    p, nodes, weights = _f64(p), _f64(nodes), _f64(weights)
+    nd = D.shape[0]
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    out2 = np.zeros(2)
+    ig, lg = np.zeros(ncoeff), np.zeros(ncoeff)
+    hvi, hvl = np.zeros((nd, ncoeff)), np.zeros((nd, ncoeff))
+    _lib.check(L.jq_eval_f_g_grad_hvp(h, _ptr(p), ncoeff, _ptr(D), nd, _ptr(nodes), _ptr(weights), nodes.size, _ptr(sh), _ptr(out2), _ptr(ig),
+                                      _ptr(lg), _ptr(hvi), _ptr(hvl)), h)
+    return dict(infidelity=float(out2[0]), leak=float(out2[1]), infid_grad=ig, leak_grad=lg, hv_infid=np.ascontiguousarray(hvi.T),
+                hv_leak=np.ascontiguousarray(hvl.T))
+
+
+def tikhonov_hessvec(d, tik0):
+    """The second derivative of the Tikhonov term along d: tikhonov_grad is affine in pcof (2 tik0 (pcof - prior) / Npar), so its
+    derivative along d is tikhonov_grad(d) without the prior -- the prior is a constant."""
+    return tikhonov_grad(d, tik0, None)
+
+
+def eval_hessvec_par(pcof, d, params, wa, nodes=(0.0,), weights=(1.0,)):
+    """The derivative along d of what eval_grad_f_par returns (the exact-Hessian callback of setup_ipopt_problem(hessian="exact")):
+    hv_infid of eval_f_g_grad_hvp -- objFuncType == 1: the derivative of the total gradient, which that call returns as hv_infid with
+    hv_leak zero -- plus the second derivative of the Tikhonov term."""
+    d = np.asarray(d, dtype=np.float64)
+    r = eval_f_g_grad_hvp(pcof, d, params, wa, nodes, weights)
+    hv = r["hv_infid"][:, 0]
+    if params.objFuncType == 1:
+        hv = hv + r["hv_leak"][:, 0]
+    return hv + tikhonov_hessvec(d, params.tik0)
 
 
 def _drift_ensemble(params, Hconsts, weights, who):
@@ -413,7 +478,8 @@ class OptimProblem:
 
 def setup_ipopt_problem(params, wa, nCoeff, minCoeff, maxCoeff, maxIter=50, lbfgsMax=10, startFromScratch=True,
                         ipTol=1.0e-5, acceptTol=1.0e-5, acceptIter=15, nodes=(0.0,), weights=(1.0,),
-                        jacob_approx="exact", drifts=None, drift_weights=None, ctrl_mix=None, member_weights=None):
+                        jacob_approx="exact", drifts=None, drift_weights=None, ctrl_mix=None, member_weights=None,
+                        hessian="limited-memory"):
     """src/ipopt_interface.jl:262-415.
     drifts (an Ntot x Ntot x ndrift array or a sequence of matrices) with drift_weights (one per member): the callbacks memoise through
     eval_f_g_grad_drifts instead of eval_f_g_grad, so run_optimizer optimises the risk-neutral objective over that drift ensemble
@@ -421,7 +487,17 @@ def setup_ipopt_problem(params, wa, nCoeff, minCoeff, maxCoeff, maxIter=50, lbfg
     ctrl_mix (an Nc x Nc x nmember array or a sequence of matrices; amplitude_mix builds diagonal ones) with member_weights (one per member):
     the callbacks memoise through eval_f_g_grad_members -- the risk-neutral objective over miscalibrated amplitudes / crosstalk.  drifts and
     ctrl_mix may be given together (member i has both) with ONE weight vector, under either keyword; giving both weight keywords is an error.
+    hessian: "limited-memory" (the reference's L-BFGS approximation; the default changes nothing) or "exact": prob.eval_hessvec(pcof, d) =
+    eval_hessvec_par over the nodes, and run_optimizer drives scipy's trust-constr with it.  "exact" with objFuncType == 3 (the leakage
+    is a constraint), drifts or ctrl_mix raises ValueError: those Hessians are not built.
     Shape errors raise ValueError before any library call."""
+    if hessian not in ("limited-memory", "exact"):
+        raise ValueError("setup_ipopt_problem: hessian must be \"limited-memory\" or \"exact\", not %r" % (hessian,))
+    if hessian == "exact":
+        if params.objFuncType == 3:
+            raise ValueError("setup_ipopt_problem: hessian=\"exact\" with objFuncType == 3 (leakage as a constraint) is not built")
+        if drifts is not None or ctrl_mix is not None:
+            raise ValueError("setup_ipopt_problem: hessian=\"exact\" with drifts or ctrl_mix is not built (eps-node ensembles only)")
     if drift_weights is not None and member_weights is not None:
         raise ValueError("setup_ipopt_problem: give drift_weights or member_weights, not both")
     if member_weights is not None:      # (one weight vector for the members, whatever differs between them)
@@ -470,6 +546,7 @@ def setup_ipopt_problem(params, wa, nCoeff, minCoeff, maxCoeff, maxIter=50, lbfg
         eval_grad_f_par(pcof, g, params, wa, nodes, weights, **ens)
         return g
     prob.eval_grad_f = _grad
+    prob.eval_hessvec = (lambda pcof, d: eval_hessvec_par(pcof, d, params, wa, nodes, weights)) if hessian == "exact" else None
     if params.objFuncType == 3:                               # :299-306: leakage as an inequality constraint
         prob.m = 1
         prob.g_L, prob.g_U = np.array([-2e19]), np.array([params.leak_ubound])
@@ -493,7 +570,7 @@ def setup_ipopt_problem(params, wa, nCoeff, minCoeff, maxCoeff, maxIter=50, lbfg
                                                                  params)
     prob.options = dict(max_iter=int(maxIter), limited_memory_max_history=int(lbfgsMax), tol=float(ipTol),
                         acceptable_tol=float(acceptTol), acceptable_iter=int(acceptIter),
-                        warm_start=not startFromScratch, jacobian_approximation=jacob_approx)
+                        warm_start=not startFromScratch, jacobian_approximation=jacob_approx, hessian_approximation=hessian)
     if not params.quiet:
         print("Optimizer parameters: max # iterations = ", maxIter)
         print("Optimizer parameters: max history L-BFGS = ", lbfgsMax)
@@ -528,7 +605,10 @@ def run_optimizer(prob, pcof0, baseName=""):
     if not params.quiet:
         print("*** Starting the optimization ***")
     try:
-        if prob.m == 0:
+        if prob.m == 0 and getattr(prob, "eval_hessvec", None) is not None:      # hessian="exact": Newton-type steps on exact products
+            res = optimize.minimize(prob.eval_f, x0, jac=prob.eval_grad_f, hessp=prob.eval_hessvec, method="trust-constr", bounds=bounds,
+                                    callback=callback, options=dict(maxiter=opt["max_iter"], gtol=opt["tol"], xtol=1e-12))
+        elif prob.m == 0:
             res = optimize.minimize(prob.eval_f, x0, jac=prob.eval_grad_f, method="L-BFGS-B", bounds=bounds,
                                     callback=callback,
                                     options=dict(maxiter=opt["max_iter"], maxcor=opt["limited_memory_max_history"],

@@ -1,0 +1,99 @@
+#!/usr/bin/env python3
+"""Times jq_eval_f_g_grad_hvp with the library's own HIP events (jq_last_timing), two calls after a warm-up each:
+  (a) swap02 at full length, one node, 1 and 16 directions, against jq_traceobjgrad_hvp on the same handle in the same process;
+  (b) the SWAP-02 risk-neutral configuration (cases.swap02_rn, 512 nodes), 1 and 16 directions, against jq_eval_f_g_grad on the same
+      handle.
+Prints the body of profiles/ens_hvp_timing.txt.  Needs a GPU."""
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import juqbox_jl_amd as jq  # noqa: E402
+
+
+def timed(call, wa, runs=2):
+    call()      # warm-up
+    out = []
+    for _ in range(runs):
+        r = call()
+        out.append((wa.last_timing(), r))
+    return out
+
+
+def line(tag, t):
+    return "  %s: total %.2f ms, forward %.2f ms in %d launches, backward %.2f ms in %d launches, generate %.2f ms" % (
+        tag, t["ms_total"], t["ms_forward"], t["n_forward_launches"], t["ms_backward"], t["n_backward_launches"], t["ms_generate"])
+
+
+def directions(g, n, ndir, seed):
+    rng = np.random.default_rng(seed)
+    return np.stack([g / np.linalg.norm(g)] + [rng.standard_normal(n) for _ in range(ndir - 1)], axis=1)
+
+
+def part_a():
+    p, info = jq.cases.swap02()
+    pcof = np.array(json.load(open(os.path.join(ROOT, "tests", "golden", "swap02.json")))["pcof0"])
+    wa = jq.Working_Arrays_HIP(p, pcof.size)
+    g = jq.traceobjgrad(pcof, p, wa, False, True)[1]
+    tg = wa.last_timing()
+    print("(a) swap02: Ntot %d, N %d, %d time steps, Neumann order %d, %d coefficients, objFuncType %d; one node (eps 0)" % (
+        p.Ntot, p.N, p.nsteps, p.linear_solver.max_iter, pcof.size, p.objFuncType))
+    print(line("plain adjoint evaluation (family %d)" % tg["kernel_family"], tg))
+    for ndir in (1, 16):
+        D = directions(g, pcof.size, ndir, 11)
+        old = timed(lambda: jq.traceobjgrad_hvp(pcof, D, p, wa), wa)
+        new = timed(lambda: jq.eval_f_g_grad_hvp(pcof, D, p, wa), wa)
+        plan = wa.plan_info()
+        for k, (t, _) in enumerate(old):
+            print(line("ndir %2d jq_traceobjgrad_hvp  run %d" % (ndir, k), t))
+        for k, (t, _) in enumerate(new):
+            print(line("ndir %2d jq_eval_f_g_grad_hvp run %d" % (ndir, k), t))
+        bo, bn = min(t["ms_total"] for t, _ in old), min(t["ms_total"] for t, _ in new)
+        ro, rn = old[-1][1], new[-1][1]
+        hv_new = rn["hv_infid"] + rn["hv_leak"]
+        print("ndir %2d: plan %s, kernels %s; %.1f x faster than jq_traceobjgrad_hvp (best of 2: %.2f against %.2f ms); %.2f us per time step and "
+              "direction; %.1f x one jq_traceobjgrad" % (ndir, json.dumps(plan["ens_hvp"]), plan["last_kernels"]["object"], bo / bn, bn, bo,
+                                                         1e3 * bn / p.nsteps / ndir, bn / tg["ms_total"]))
+        print("         |hv - hv of jq_traceobjgrad_hvp| / |hv| = %.2e" % (np.linalg.norm(hv_new - ro["hv"]) / np.linalg.norm(ro["hv"])))
+    wa.close()
+
+
+def part_b():
+    p, info = jq.cases.swap02_rn()
+    pcof, nodes, weights = np.asarray(info["pcof0"]), info["nodes"], info["weights"]
+    wa = jq.Working_Arrays_HIP(p, pcof.size)
+
+    def grad():
+        jq.eval_f_g_grad(pcof, p, wa, nodes, weights, True)
+        return p.last_infidelity_grad.copy()
+    gr = timed(grad, wa)
+    g = gr[-1][1]
+    bg = min(t["ms_total"] for t, _ in gr)
+    print("(b) SWAP-02 risk-neutral: Ntot %d, N %d, %d time steps, Neumann order %d, %d coefficients, objFuncType %d; %d nodes = %d columns" % (
+        p.Ntot, p.N, p.nsteps, p.linear_solver.max_iter, pcof.size, p.objFuncType, nodes.size, nodes.size * p.N))
+    for k, (t, _) in enumerate(gr):
+        print(line("jq_eval_f_g_grad (family %d) run %d" % (t["kernel_family"], k), t))
+    for ndir in (1, 16):
+        D = directions(g, pcof.size, ndir, 12)
+        new = timed(lambda: jq.eval_f_g_grad_hvp(pcof, D, p, wa, nodes, weights), wa)
+        plan = wa.plan_info()
+        for k, (t, _) in enumerate(new):
+            print(line("ndir %2d jq_eval_f_g_grad_hvp run %d" % (ndir, k), t))
+        bn = min(t["ms_total"] for t, _ in new)
+        tb = min(new, key=lambda x: x[0]["ms_total"])[0]
+        print("ndir %2d: plan %s; %.1f x one jq_eval_f_g_grad for the call, %.2f x per direction (best of 2: %.2f against %.2f ms); forward %.2f, "
+              "backward %.2f us per time step" % (ndir, json.dumps(plan["ens_hvp"]), bn / bg, bn / bg / ndir, bn, bg,
+                                                  1e3 * tb["ms_forward"] / p.nsteps, 1e3 * tb["ms_backward"] / p.nsteps))
+        r = new[-1][1]
+        print("         |infid_grad - eval_f_g_grad's| / |g| = %.2e" % (np.linalg.norm(r["infid_grad"] - g) / np.linalg.norm(g)))
+    wa.close()
+
+
+if __name__ == "__main__":
+    part_a()
+    print()
+    part_b()
