@@ -27,6 +27,11 @@ static int dev_grow(jq_handle* h, T** p, size_t* cap, size_t need)
     if (rc == JQ_OK) *cap = need;
     return rc;
 }
+// the budget of a chunk's tile streams in bytes: option stream_bytes, default 1 GiB (the one reader of the option)
+static size_t stream_budget_bytes(const jq_handle* h)
+{
+    return (h->opt.has(O_STREAM_BYTES) && h->opt.get(O_STREAM_BYTES) > 0) ? (size_t)h->opt.get(O_STREAM_BYTES) : (size_t)1 << 30;
+}
 
 static int upload_operators(jq_handle* h)
 {
@@ -639,8 +644,7 @@ static int create_dense(const jq_problem* p, jq_handle* h)
     }
 
     // chunking of the time loop: the tile stream of one chunk has (2*cs+1) time points x {K,S}
-    size_t budget = (size_t)1 << 30;
-    if (h->opt.has(O_STREAM_BYTES) && h->opt.get(O_STREAM_BYTES) > 0) budget = (size_t)h->opt.get(O_STREAM_BYTES);
+    const size_t budget = stream_budget_bytes(h);
     // largest operator image of any kernel family the handle may use (slab, cooperative, lane, row-lane)
     const long long img_elems = std::max(std::max(std::max(h->mat_elems, h->mat_elems_c), std::max(h->lane_stride, h->rl_stride)), h->dq_max_quads > 0 ? (long long)JQ_DQ_ELEMS : 0LL);
     const size_t per_tp = 2 * (size_t)img_elems * sizeof(double);

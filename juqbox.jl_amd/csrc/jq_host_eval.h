@@ -99,14 +99,48 @@ static jq_handle* eval_target(jq_handle* h, int nsamples, bool hist)
 static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out);
 static int run_eval(jq_handle* h, const EvalRequest& rq, EvalOut* out)
 {
-    DevGate& gate = dev_gate(h->device);
-    const bool outer = g_eval_depth++ == 0;
-    if (outer) gate.enter();
+    EvalGate gate(h);
     int rc = run_eval_impl(h, rq, out);
     if (rc == JQ_ERETRY_INTERNAL) rc = run_eval_impl(h, rq, out);
-    if (outer) gate.leave();
-    --g_eval_depth;
     return rc;
+}
+// the handle's event pool holds at least nev events ([0] = start, [1] = end of a call, then pairs around its propagator launches)
+static int ensure_events(jq_handle* h, size_t nev)
+{
+    while (h->ev.size() < nev) {
+        hipEvent_t e;
+        HIPCHK(h, hipEventCreate(&e));
+        h->ev.push_back(e);
+    }
+    return JQ_OK;
+}
+// The operator schedule of a sweep's launches from the family's rows of JQ_SCHED (rows = JQ_SCHED[cooperative]; kind 0 K, 1 S at time
+// point 0, 1, 2 of a step = t_n "n0 / 0", t_n + h/2 "p05 / 05", t_n + h "n1 / 1"; kind 2: image q of the launch's trace images
+// [Hsym_q.. | Hanti_q..]).  Forward: the first seven entries,
+//   slab kernels Kp05 S05 Kn0 S0 Kn1 S1 Kp05, cooperative kernels Kp05 S05 Kn0 Kn1 S0 S1 Kp05.
+// Backward: all eight (the seven and S0), then the same tail for every family,
+//   | Hanti_q.. (early traces) | Kn0 Kn1 S05 Kp05 S1 | (Hanti_q Hsym_q).. (late traces),
+// and, for a sweep's first chunk (npro = ng, the caller's), the carry products with Hsym_q in pro_bits.
+static void pack_forward_schedule(PropArgs& a, const int (*rows)[8])
+{
+    a.period = 7; a.npro = 0;
+    a.sched_bits[0] = a.sched_bits[1] = a.sched_bits[2] = a.pro_bits = 0;
+    for (int i = 0; i < 7; ++i) sched_pack(a.sched_bits, i, rows[0][i], rows[1][i]);
+}
+static void pack_backward_schedule(PropArgs& a, const int (*rows)[8], int ng)
+{
+    const int kinds2[5] = {0, 0, 1, 0, 1}, tps2[5] = {0, 2, 1, 1, 2};
+    a.period = 13 + 3 * ng;
+    a.sched_bits[0] = a.sched_bits[1] = a.sched_bits[2] = a.pro_bits = 0;
+    int k = 0;
+    for (int i = 0; i < 8; ++i) sched_pack(a.sched_bits, k++, rows[0][i], rows[1][i]);
+    for (int q = 0; q < ng; ++q) sched_pack(a.sched_bits, k++, 2, ng + q);
+    for (int i = 0; i < 5; ++i) sched_pack(a.sched_bits, k++, kinds2[i], tps2[i]);
+    for (int q = 0; q < ng; ++q) {
+        sched_pack(a.sched_bits, k++, 2, ng + q);
+        sched_pack(a.sched_bits, k++, 2, q);
+        sched_pack(&a.pro_bits, q, 2, q);
+    }
 }
 static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
 {
@@ -355,11 +389,7 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     // events: [0]=start [1]=end, then pairs around every propagator launch
     const int nchunks = (h->nsteps + p.cs - 1) / p.cs;
     const size_t nev = 2 + 2 * (size_t)nchunks * (1 + (adjoint ? (two_pass ? 2 : 1) * ngroups : 0));
-    while (h->ev.size() < nev) {
-        hipEvent_t e;
-        HIPCHK(h, hipEventCreate(&e));
-        h->ev.push_back(e);
-    }
+    if ((rc = ensure_events(h, nev))) return rc;
     size_t evi = 2;
     HIPCHK(h, hipEventRecord(h->ev[0], s));
 
@@ -384,9 +414,8 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
         a.wlr_lds = p.fwd.wlr;
         a.wlr_sc_lds = p.fwd.wsc;
         a.jac_wg_lds = p.fwd.jac;
-        a.period = 7; a.npro = 0; a.nslots = h->nslots;
-        a.sched_bits[0] = a.sched_bits[1] = a.sched_bits[2] = a.pro_bits = 0;
-        for (int i = 0; i < 7; ++i) sched_pack(a.sched_bits, i, p.sched[0][i], p.sched[1][i]);
+        a.nslots = h->nslots;
+        pack_forward_schedule(a, p.sched);
         HIPCHK(h, hipEventRecord(h->ev[evi++], s));
         hipLaunchKernelGGL(p.kfwd, dim3(p.fwd_grid), dim3(p.fwd_block), p.fwd.total, s, a);
         HIPCHK(h, hipEventRecord(h->ev[evi++], s));
@@ -452,20 +481,8 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
                 a.wlr_lds = p.bwd.wlr;
                 a.wlr_sc_lds = p.bwd.wsc;
                 a.jac_wg_lds = p.bwd.jac;
-                a.period = 13 + 3 * ng; a.npro = (n0 == 0) ? ng : 0; a.nslots = h->nslots_bwd;
-                {   // Kp05 S05 Kn0 S0 Kn1 S1 Kp05 | S0 | Hanti_q.. | Kn0 Kn1 S05 Kp05 S1 | (Hanti_q Hsym_q)..
-                    const int kinds2[5] = {0, 0, 1, 0, 1}, tps2[5] = {0, 2, 1, 1, 2};
-                    a.sched_bits[0] = a.sched_bits[1] = a.sched_bits[2] = a.pro_bits = 0;
-                    int k = 0;
-                    for (int i = 0; i < 8; ++i) sched_pack(a.sched_bits, k++, p.sched[0][i], p.sched[1][i]);
-                    for (int q = 0; q < ng; ++q) sched_pack(a.sched_bits, k++, 2, ng + q);   // early traces: Hanti_q
-                    for (int i = 0; i < 5; ++i) sched_pack(a.sched_bits, k++, kinds2[i], tps2[i]);
-                    for (int q = 0; q < ng; ++q) {
-                        sched_pack(a.sched_bits, k++, 2, ng + q);                               // late traces: Hanti_q
-                        sched_pack(a.sched_bits, k++, 2, q);                                    //              Hsym_q
-                        sched_pack(&a.pro_bits, q, 2, q);          // first chunk: carry products with Hsym_q
-                    }
-                }
+                a.npro = (n0 == 0) ? ng : 0; a.nslots = h->nslots_bwd;
+                pack_backward_schedule(a, p.sched, ng);
                 if (cq3) {      // (progress counters of the launch: the 64-double header in front of every quad's ring -- the ring itself is written
                                 // before it is read; the error word in front of everything survives until the end of the evaluation, the
                                 // arrival counter of the start-up rendezvous behind it is per launch)

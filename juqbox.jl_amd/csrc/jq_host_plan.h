@@ -91,6 +91,21 @@ struct DevGate {
 static DevGate g_gate[64];
 static DevGate& dev_gate(int device) { return g_gate[(unsigned)device % 64u]; }
 static thread_local int g_eval_depth = 0;      // run_eval calls itself (split batches, the embedded twin): only the outermost call is counted
+struct EvalGate {      // an evaluation in flight on the handle's device for the rest of a scope (also when it throws): run_eval and the derivative calls
+    DevGate& g;
+    const bool outer;
+    explicit EvalGate(const jq_handle* h) : g(dev_gate(h->device)), outer(g_eval_depth++ == 0)
+    {
+        if (outer) g.enter();
+    }
+    ~EvalGate()
+    {
+        if (outer) g.leave();
+        --g_eval_depth;
+    }
+    EvalGate(const EvalGate&) = delete;
+    EvalGate& operator=(const EvalGate&) = delete;
+};
 struct GateHold {      // exclusive use of a device for the rest of a scope
     DevGate* g = nullptr;
     bool acquire(DevGate& gate)
@@ -363,8 +378,7 @@ static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateH
         // a chunk holds one tile stream per vector, each of THIS family's image size (not the largest image of any family jq_create sized the
         // buffer by): as many steps as the stream budget holds -- option stream_bytes, default 1 GiB, or the buffer the handle has; run_eval
         // grows a buffer that option chunk_steps kept below the budget.  Never longer than the single evaluation's chunk.
-        size_t budget = ((size_t)1 << 30) / sizeof(double);
-        if (h->opt.has(O_STREAM_BYTES) && h->opt.get(O_STREAM_BYTES) > 0) budget = (size_t)h->opt.get(O_STREAM_BYTES) / sizeof(double);
+        const size_t budget = stream_budget_bytes(h) / sizeof(double);
         const long long tps = (long long)(std::max(budget, h->cap_stream) / ((size_t)groups * 2 * (size_t)p->stride));
         p->cs = (int)std::max<long long>(1, std::min<long long>(p->cs, (tps - 1) / 2));
     }

@@ -708,6 +708,7 @@ extern "C" int jq_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int32_t
     });
 }
 
+#include "jq_host_tl.h"      // what the drivers of the tangent-linear sweeps share: budgeting, stream generation, trace reduction, timing
 #include "jq_host_jvp.h"      // jq_traceobj_jvp: the tangent of the forward map along directions of coefficient space
 #include "jq_host_hvp.h"      // jq_traceobjgrad_hvp: the derivative of the gradient along directions of coefficient space
 #include "jq_host_ens_hvp.h"      // jq_eval_f_g_grad_hvp: the same over the nodes of a risk-neutral ensemble (lane kernels: one launch per chunk)

@@ -131,6 +131,10 @@ def test_directions_in_rounds_and_the_jvp_around_the_call_are_the_same_bits(jq):
         a, b = jq.traceobjgrad_hvp(pcof, D, p, wa), jq.traceobjgrad_hvp(pcof, D, p, wb)
         assert wa.plan_info()["hvp"] == {"directions_per_launch": 5, "chunk_steps": NSTEPS, "rounds": 1}
         assert wb.plan_info()["hvp"] == {"directions_per_launch": 2, "chunk_steps": NSTEPS, "rounds": 3}
+        t = wb.last_timing()      # the launch timer over rounds: one chunk, three rounds, two sweeps (objFuncType 3: forced and unforced)
+        nchunks, rounds, nsweeps = 1, 3, 2
+        assert t["n_forward_launches"] == nchunks * rounds and t["n_backward_launches"] == nchunks * rounds * nsweeps
+        assert t["ms_generate"] >= 0 and t["ms_total"] >= t["ms_propagate"]
         for k in SAME_BITS + ("hv", "hv_infid", "hv_leak"):
             assert np.array_equal(a[k], b[k]), k
         jvp1 = [jq.traceobj_jvp(pcof, D, p, w) for w in (wa, wb)]
