@@ -414,10 +414,13 @@ int jq_traceobjgrad_hvp(jq_handle *h, const double *pcof, int32_t ncoeff, const 
  *   hv_infid, hv_leak : [ncoeff x ndir] column-major (objFuncType 1: hv_infid carries the derivative of totalgrad, hv_leak zeros)
  * Lane route: Ntot <= 6 with at most four controls (and option lane != 0) runs on the tangent-linear lane kernels -- all N nquad columns
  * x the directions of a round in ONE launch per chunk, independent of the options lane_min / lane_max (one node is served too).
- * Sequential route: everything else jq_traceobjgrad_hvp serves (Ntot 7 and 8 included: their tangent kernel would spill) runs the nodes
- * one after the other on its run-time-size sweeps -- correct and no faster.  Direction j does not depend on the other directions of the
- * call nor on the rounds they run in (option stream_bytes).  jq_plan_info "ens_hvp": {route: "lane" | "sequential",
- * directions_per_launch, chunk_steps, rounds} after a call; jq_last_timing reports the lane family and NP on the lane route and counts
+ * Row-lane route: Ntot 9 .. 16 with at most four controls (and option lane != 0) runs on the tangent-linear row-lane kernels -- four
+ * columns per wave, ceil(N nquad / 4) waves x the directions of a round in ONE launch per chunk, independent of option rowlane_max.
+ * Sequential route: everything else jq_traceobjgrad_hvp serves (Ntot 7 and 8, which have no tangent kernel; Ntot > 16; option lane=0;
+ * more than four controls) runs the nodes one after the other on its run-time-size sweeps -- correct and no faster.  Direction j does not depend on the other directions of the
+ * call nor on the rounds they run in (option stream_bytes).  jq_plan_info "ens_hvp": {route: "lane" | "rowlane" | "sequential",
+ * directions_per_launch, chunk_steps, rounds} after a call; jq_last_timing reports the lane family and NP on the lane route, the
+ * row-lane family and NPJ on the row-lane route, and counts
  * forward and backward launches; "last_kernels" names the instantiations.  Refused with JQ_EUNSUPPORTED: what jq_traceobjgrad_hvp
  * refuses (implicit midpoint, the Jacobi solver, full leakage weights, sv_type != 1, uncoupled controls).  JQ_EINVAL for NULL pointers
  * (all but shift are required), ndir < 1 or nquad < 1; the codes of jq_traceobjgrad for the coefficient count.  A refused call writes

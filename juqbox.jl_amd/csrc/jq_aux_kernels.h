@@ -4,6 +4,7 @@
 #pragma once
 #include "jq_kernels.h"
 #include "jq_rowlane_kernels.h"
+#include "jq_rowlane_tl_kernels.h"
 
 struct SplineArgs {
     const double* pcof;   // [nCoeff]
@@ -711,3 +712,62 @@ __global__ void k_terminal_rowlane_imr(double* state, long long nw, const double
     res[(size_t)s * 4 + 3] = im;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Tangent-linear row-lane kernels (jq_rowlane_tl_kernels.h; jq_eval_f_g_grad_hvp): initial state and terminal condition of every direction
+// state files <- (Uinit, 0 ...) for every direction.  a.cimg: uinit [N][16]; a.nslabs: waves; a.nsamples N columns in use.
+// grid = (waves, directions)
+__global__ __launch_bounds__(64) void k_init_rowlane_tl(PropArgs a)
+{
+    const int lane = threadIdx.x;
+    const long long w = blockIdx.x, nw = a.nslabs;
+    const long long col = 4 * w + (lane >> 4);
+    double* st = a.state + (size_t)blockIdx.y * (size_t)a.state_stride + w * 64 + lane;
+    const bool used = col < (long long)a.nsamples * a.N;
+    for (int r = 0; r < JQ_ROWLANE_TL_ROWS; ++r) st[(size_t)r * nw * 64] = (r == 0 && used) ? a.cimg[(col % a.N) * 16 + (lane & 15)] : 0.0;
+}
+
+// Fidelity, leak, lambda(T) and its tangent per (sample, direction): k_terminal_rowlane (mode 1) and its derivative.
+//   s = tr(Vtg' V) / N, sd = tr(Vtg' Vd) / N ; lambda(T) = s conj(Vtg) / N, its tangent sd conj(Vtg) / N
+// a.cimg: vtr [N][16], a.tabs: vti [N][16], a.h: leak scale, a.nslabs: waves, a.traces: res [direction][sample][4] = { primary,
+// secondary, Re s, Im s }.  Thread per sample -- its columns are read wherever their waves are; grid = (ceil(samples / 64), directions)
+__global__ __launch_bounds__(64) void k_terminal_rowlane_tl(PropArgs a)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.nsamples) return;
+    const size_t arr = (size_t)a.nslabs * 64;
+    const int N = a.N;
+    double* state = a.state + (size_t)blockIdx.y * (size_t)a.state_stride;
+    const double *vtr = a.cimg, *vti = a.tabs;
+    double re = 0.0, im = 0.0, dre = 0.0, dim = 0.0, lk = 0.0;
+    for (int ic = 0; ic < N; ++ic) {
+        const long long col = (long long)s * N + ic;
+        const size_t base = (size_t)(col / 4) * 64 + (size_t)(col % 4) * 16;
+        for (int r = 0; r < 16; ++r) {
+            const double u = state[base + r], v = state[arr + base + r];
+            const double ud = state[4 * arr + base + r], vd = state[5 * arr + base + r];
+            const double tr = vtr[ic * 16 + r], ti = vti[ic * 16 + r];
+            re += jq_det2(u, tr, v, ti);
+            im += jq_dot2(u, ti, v, tr);
+            dre += jq_det2(ud, tr, vd, ti);
+            dim += jq_dot2(ud, ti, vd, tr);
+            lk += state[(size_t)(JQ_ROWLANE_TL_ROWS - 1) * arr + base + r];
+        }
+    }
+    re /= N, im /= N, dre /= N, dim /= N;
+    for (int ic = 0; ic < N; ++ic) {
+        const long long col = (long long)s * N + ic;
+        const size_t base = (size_t)(col / 4) * 64 + (size_t)(col % 4) * 16;
+        for (int r = 0; r < 16; ++r) {
+            const double tr = vtr[ic * 16 + r], ti = vti[ic * 16 + r];
+            state[2 * arr + base + r] = jq_dot2(im, ti, re, tr) / N;         // lambda_r
+            state[3 * arr + base + r] = -(jq_det2(im, tr, re, ti) / N);      // nb = -lambda_i
+            state[6 * arr + base + r] = jq_dot2(dim, ti, dre, tr) / N;
+            state[7 * arr + base + r] = -(jq_det2(dim, tr, dre, ti) / N);
+        }
+    }
+    double* res = a.traces + ((size_t)blockIdx.y * a.nsamples + s) * 4;
+    res[0] = 1.0 - jq_dot2(re, re, im, im);
+    res[1] = a.h * lk;
+    res[2] = re;
+    res[3] = im;
+}

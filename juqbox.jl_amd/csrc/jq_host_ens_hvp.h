@@ -8,7 +8,11 @@
 // repeats the backward sweep unforced from the saved terminal state for the infidelity part.  The call reads the handle's lane images
 // and time tables, allocates everything it writes and frees it when it returns.
 //
-// Sequential route (everything else jq_traceobjgrad_hvp serves: Ntot > 6, option lane=0, more than JQ_MAXNC controls): the nodes one
+// Row-lane route (Ntot 9 .. 16 padded to NPJ = 12, 16; at most JQ_MAXNC controls): the same driver on the tangent-linear row-lane
+// kernels of jq_rowlane_tl_kernels.h -- four columns per wave, ceil(N nquad / 4) waves x `dpl` directions in one launch per chunk, the
+// handle's row-lane images.  What differs between the two is the layout record (EnsHvpLayout) the driver reads.
+//
+// Sequential route (everything else jq_traceobjgrad_hvp serves: Ntot 7, 8 and > 16, option lane=0, more than JQ_MAXNC controls): the nodes one
 // after the other through hvp_run with the drift Hconst + eps_i diag(shift) -- correct and no faster.
 static double ens_hvp_shift(const double* shift, int i) { return shift ? shift[i] : (i >= 1 ? 0.01 * pow(10.0, (double)(i - 1)) : 0.0); }
 
@@ -28,25 +32,51 @@ static void ens_hvp_outputs(const jq_handle* h, const EnsHvpArgs& x, const doubl
     }
 }
 
-static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, prop_kernel_t kinit, prop_kernel_t kfwd, prop_kernel_t kterm, prop_kernel_t kbwd, const KernelSel& sel)
+// What the driver needs to know about a kernel family: the handle's images in its layout, the geometry of a wave and of the state file.
+struct EnsHvpLayout {
+    int route;                  // ens_hvp_route: 1 lane, 3 row-lane
+    int family, size;           // jq_last_timing: kernel_family, kernel_size (NP / NPJ)
+    const char* label;          // JQ_DEBUG_TIMING
+    size_t stride;              // doubles per operator image
+    const double *himg, *cimg, *uinit, *vtr, *vti;
+    int cpw;                    // columns per wave; colinfo = [eps per column | weight per column] at cpw nwaves
+    int state_rows;             // rows of 64 doubles per wave in one direction's state file
+    bool slabs_are_waves;       // PropArgs::nslabs: waves (row-lane kernels) or padded columns (lane kernels)
+    int tab_off;                // tables [wd(tab_off) | ws(tab_off)]
+    size_t lds_fwd, lds_bwd;    // dynamic LDS bytes of the sweep kernels
+};
+static EnsHvpLayout ens_hvp_layout_lane(const jq_handle* h)
+{
+    return {1, KF_LANE, h->lane_np, "tangent-linear lane", (size_t)h->lane_stride, h->d_himg_l, h->d_cimg_l, h->d_uinit_l, h->d_vtr_l, h->d_vti_l,
+            64, JQ_LANE_TL_ROWS(h->lane_np), false, h->lane_np, 0, 0};
+}
+static EnsHvpLayout ens_hvp_layout_rowlane(const jq_handle* h)
+{
+    const size_t rings = JQ_ROWLANE_TL_RINGS(h->rl_npj);
+    return {3, KF_ROWLANE, h->rl_npj, "tangent-linear row-lane", (size_t)h->rl_stride, h->d_himg_r, h->d_cimg_r, h->d_uinit_r, h->d_vtr_r, h->d_vti_r,
+            4, JQ_ROWLANE_TL_ROWS, true, 16, rings, rings + (size_t)2 * h->Nc * h->rl_stride * sizeof(double)};
+}
+
+static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& lay, prop_kernel_t kinit, prop_kernel_t kfwd, prop_kernel_t kterm, prop_kernel_t kbwd,
+                        const KernelSel& sel)
 {
     const char* who = "jq_eval_f_g_grad_hvp";
     HIPCHK(h, hipSetDevice(h->device));
-    const int NP = h->lane_np, Nc = h->Nc, ncoeff = x.ncoeff, ndir = x.ndir, nquad = x.nquad;
-    const size_t stride = (size_t)h->lane_stride;
-    const long long ncols_used = (long long)nquad * h->N, ncols = (ncols_used + 63) / 64 * 64;
-    const int nwaves = (int)(ncols / 64), ntr = Nc * JQ_NTR;
+    const int Nc = h->Nc, ncoeff = x.ncoeff, ndir = x.ndir, nquad = x.nquad;
+    const size_t stride = lay.stride;
+    const long long ncols_used = (long long)nquad * h->N, ncols = (ncols_used + lay.cpw - 1) / lay.cpw * lay.cpw;
+    const int nwaves = (int)(ncols / lay.cpw), ntr = Nc * JQ_NTR;
     const double dt = h->T / h->nsteps;
     const bool two_pass = h->objFuncType != 1;
     const int npass = two_pass ? 2 : 1;
-    const size_t sstride = (size_t)JQ_LANE_TL_ROWS(NP) * (size_t)ncols;      // doubles of one direction's state file
+    const size_t sstride = (size_t)lay.state_rows * (size_t)nwaves * 64;      // doubles of one direction's state file
     const TlBudget b = tl_budget(h, stride, ndir, JQ_JVP_MAX_DIRS, (size_t)nwaves * ntr);      // (the directions are a grid dimension of their own)
     const int dpl = b.dpl, cs = b.cs, rounds = b.rounds, nvec = 1 + dpl;
 
-    // tables [wd | ws], column info [eps | weight] (run_eval's for the lane layout), drift images of the groups [H0 | 0 ...]
-    std::vector<double> tabs((size_t)2 * NP, 0.0), colinfo((size_t)2 * ncols, 0.0);
+    // tables [wd | ws], column info [eps | weight] (run_eval's for the layout), drift images of the groups [H0 | 0 ...]
+    std::vector<double> tabs((size_t)2 * lay.tab_off, 0.0), colinfo((size_t)2 * ncols, 0.0);
     bool use_shift = false;
-    for (int i = 0; i < h->Ntot; ++i) tabs[i] = h->wd[i], tabs[NP + i] = ens_hvp_shift(x.shift, i);
+    for (int i = 0; i < h->Ntot; ++i) tabs[i] = h->wd[i], tabs[lay.tab_off + i] = ens_hvp_shift(x.shift, i);
     for (long long c = 0; c < ncols_used; ++c) {
         const int smp = (int)(c / h->N);
         colinfo[c] = x.nodes[smp];
@@ -65,19 +95,21 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, prop_kernel_t kinit, 
     // d_g: [pass][primal | direction ...][ncoeff]
     hipStream_t s = h->stream;
     HIPCHK(h, hipMemsetAsync(d_h0.p, 0, (size_t)nvec * stride * sizeof(double), s));
-    HIPCHK(h, hipMemcpyAsync(d_h0.p, h->d_himg_l, stride * sizeof(double), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(d_h0.p, lay.himg, stride * sizeof(double), hipMemcpyDeviceToDevice, s));
     HIPCHK(h, hipMemcpyAsync(d_tabs.p, tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(d_col.p, colinfo.data(), colinfo.size() * sizeof(double), hipMemcpyHostToDevice, s));
 
-    const TlGen gen = {tl_spline(h, d_pc.p, ncoeff, nullptr), h->d_himg_l, d_h0.p, d_pq.p, d_stream.p, stride, b.gstride, nvec};
+    const TlGen gen = {tl_spline(h, d_pc.p, ncoeff, nullptr), lay.himg, d_h0.p, d_pq.p, d_stream.p, stride, b.gstride, nvec};
     PropArgs a;
     memset(&a, 0, sizeof a);
     a.stream = d_stream.p; a.stream_gstride = (long long)b.gstride; a.group_units = 1; a.state = d_state.p; a.state_stride = (long long)sstride;
-    a.colinfo = d_col.p; a.tabs = d_tabs.p; a.traces = d_tr.p; a.cimg = h->d_cimg_l; a.stride = (long long)stride; a.m = h->m; a.nslabs = (int)ncols;
+    a.colinfo = d_col.p; a.tabs = d_tabs.p; a.traces = d_tr.p; a.cimg = lay.cimg; a.stride = (long long)stride; a.m = h->m; a.nslabs = lay.slabs_are_waves ? nwaves : (int)ncols;
     a.Ncoupled = Nc; a.Ntot = h->Ntot; a.N = h->N; a.parts = 1; a.nsamples = nquad; a.sps = 1; a.tinv = 1.0 / h->T; a.use_shift = use_shift ? 1 : 0;
-    PropArgs ai = a, at = a;      // the init and terminal kernels read their images and scalars through the fields jq_lane_tl_kernels.h names
-    ai.cimg = h->d_uinit_l;
-    at.cimg = h->d_vtr_l; at.tabs = h->d_vti_l; at.traces = d_res.p; at.h = 0.5 * dt * (1.0 / h->T);
+    PropArgs ai = a, at = a;      // the init and terminal kernels read their images and scalars through the fields their headers name
+    ai.cimg = lay.uinit;
+    at.cimg = lay.vtr; at.tabs = lay.vti; at.traces = d_res.p; at.h = 0.5 * dt * (1.0 / h->T);
+    if (lay.lds_fwd) HIPCHK(h, hipFuncSetAttribute((const void*)kfwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.lds_fwd));
+    if (lay.lds_bwd) HIPCHK(h, hipFuncSetAttribute((const void*)kbwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.lds_bwd));
 
     LaunchTimer tm{h};
     if ((rc = tm.start((size_t)b.nchunks * rounds * (1 + npass)))) return rc;
@@ -96,7 +128,7 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, prop_kernel_t kinit, 
             tl_generate(h, gen, n0, nc, dt);
             a.nsteps_chunk = nc; a.step0 = n0; a.first_chunk = (n0 == 0);
             if ((rc = tm.begin(false))) return rc;
-            hipLaunchKernelGGL(kfwd, grid, dim3(64), 0, s, a);
+            hipLaunchKernelGGL(kfwd, grid, dim3(64), lay.lds_fwd, s, a);
             if ((rc = tm.end())) return rc;
         }
         hipLaunchKernelGGL(kterm, dim3((unsigned)((nquad + 63) / 64), (unsigned)dpl), dim3(64), 0, s, at);
@@ -112,7 +144,7 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, prop_kernel_t kinit, 
                 tl_generate(h, gen, n0, nc, -dt);
                 a.nsteps_chunk = nc; a.step0 = n0; a.first_chunk = (n0 == 0);
                 if ((rc = tm.begin(true))) return rc;
-                hipLaunchKernelGGL(kbwd, grid, dim3(64), 0, s, a);
+                hipLaunchKernelGGL(kbwd, grid, dim3(64), lay.lds_bwd, s, a);
                 if ((rc = tm.end())) return rc;
                 tl_reduce_chunk(h, gen.sp, r == 0, d_tr.p, nwaves, dpl, n0, nc, 0, Nc, d_R.p, d_R.p + (size_t)cs * ntr, d_g.p + (size_t)pass * nvec * ncoeff);
             }
@@ -130,12 +162,12 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, prop_kernel_t kinit, 
     }
     x.out2[0] = inf, x.out2[1] = leak;
     ens_hvp_outputs(h, x, g0.data(), g1.data(), v0.data(), v1.data());
-    h->ens_hvp_route = 1, h->ens_hvp_per_launch = dpl, h->ens_hvp_chunk = cs, h->ens_hvp_rounds = rounds;
+    h->ens_hvp_route = lay.route, h->ens_hvp_per_launch = dpl, h->ens_hvp_chunk = cs, h->ens_hvp_rounds = rounds;
 
-    if ((rc = tm.finish("tangent-linear lane"))) return rc;
+    if ((rc = tm.finish(lay.label))) return rc;
     h->timing.svts = (long long)ndir * nquad * h->N * h->nsteps;
-    h->timing.kernel_family = KF_LANE;
-    h->timing.kernel_size = NP;
+    h->timing.kernel_family = lay.family;
+    h->timing.kernel_size = lay.size;
     h->timing.kernel_band = 0;
     h->last_kernels = sel;
     return JQ_OK;
@@ -205,7 +237,15 @@ extern "C" int jq_eval_f_g_grad_hvp(jq_handle* h, const double* pcof, int32_t nc
             const int np = h->lane_np;
             const prop_kernel_t kfwd = pick(sel.fwd, np, -1, "k_forward_lane_tl", {np}), kbwd = pick(sel.bwd, np, -1, "k_backward_lane_tl", {np});
             const prop_kernel_t kinit = pick(unused, np, -1, "k_init_lane_tl", {np}), kterm = pick(unused, np, -1, "k_terminal_lane_tl", {np});
-            if (kfwd && kbwd && kinit && kterm) return ens_hvp_lane(h, x, kinit, kfwd, kterm, kbwd, sel);
+            if (kfwd && kbwd && kinit && kterm) return ens_hvp_lane(h, x, ens_hvp_layout_lane(h), kinit, kfwd, kterm, kbwd, sel);
+        }
+        // row-lane route: Ntot 9 .. 16 (rl_npj is 0 under option lane=0 and on embedded twins; NPJ <= 8 has no tangent kernels: Ntot <= 6 went
+        // the lane route above, Ntot 7 and 8 stay sequential)
+        if (h->rl_npj >= 12 && h->Nc <= JQ_MAXNC) {
+            KernelSel sel = sel_start();
+            const int np = h->rl_npj;
+            const prop_kernel_t kfwd = pick(sel.fwd, np, -1, "k_forward_rowlane_tl", {np}), kbwd = pick(sel.bwd, np, -1, "k_backward_rowlane_tl", {np});
+            if (kfwd && kbwd) return ens_hvp_lane(h, x, ens_hvp_layout_rowlane(h), k_init_rowlane_tl, kfwd, k_terminal_rowlane_tl, kbwd, sel);
         }
         return ens_hvp_sequential(h, x);
     });

@@ -78,6 +78,8 @@
 #define JQ_INST_R(X, np)                                                                                                \
     X(k_forward_rowlane, np) X(k_forward_rowlane, np, false, true) X(k_backward_rowlane, np) X(k_backward_rowlane2, np) \
     X(k_backward_rowlane3, np) X(k_forward_rowlane, np, true, true) X(k_backward_rowlane, np, true)
+// ... and the tangent-linear twins of the one-wave kernels (jq_rowlane_tl_kernels.h; jq_eval_f_g_grad_hvp at Ntot 9 .. 16): waves x directions
+#define JQ_INST_R_TL(X, np) X(k_forward_rowlane_tl, np) X(k_backward_rowlane_tl, np)
 // l_: lane kernels (np = padded Hilbert dimension NP); their init / terminal kernels have signatures of their own
 #define JQ_INST_L(X, np) X(k_forward_lane, np) X(k_backward_lane, np)
 #define JQ_INST_L_INIT(X, np) X(k_init_state_lane, np)
@@ -110,6 +112,8 @@
 // (the tangent-linear kernels of the l_ objects: none at NP = 8, whose backward kernel does not fit the 512 registers of a wave without scratch)
 #define JQ_SIZES_LANE_TL(L, A) L(A, 2) L(A, 4) L(A, 6)
 #define JQ_SIZES_ROWLANE(L, A) L(A, 2) L(A, 4) L(A, 6) L(A, 8) L(A, 12) L(A, 16)
+// (the tangent-linear kernels of the r_ objects: the row lengths jq_eval_f_g_grad_hvp has no lane kernel for; none at NPJ = 8, Ntot 7 and 8)
+#define JQ_SIZES_ROWLANE_TL(L, A) L(A, 12) L(A, 16)
 #define JQ_SIZES_QUAD8(L, A) JQ_SIZES_QUAD(L, A) JQ_SIZES_QUADBIG(L, A)      // k_<nt>_7, s_, q_, w_<nt>_7
 #define JQ_SIZES_QUAD7(L, A) JQ_SIZES_QUAD(L, A) L(A, 7, 7)                  // u_, v_
 #define JQ_SIZES_DENSE(L, A) L(A, 2, 7)                                      // the dense policy of u_ / v_
@@ -125,7 +129,8 @@
     Y(p, JQ_SIZES_QUAD, JQ_INST_P) Y(v, JQ_SIZES_QUAD7, JQ_INST_V) Y(v, JQ_SIZES_QUAD, JQ_INST_V_IMR2)                  \
     Y(v, JQ_SIZES_DENSE, JQ_INST_V_DENSE) Y(q, JQ_SIZES_QUAD8, JQ_INST_Q) Y(i, JQ_SIZES_I, JQ_INST_I)                   \
     Y(i, JQ_SIZES_C, JQ_INST_I_PARTS) Y(i, JQ_SIZES_HBM, JQ_INST_I_HBM) Y(m, JQ_SIZES_ROWLANE, JQ_INST_M)               \
-    Y(r, JQ_SIZES_ROWLANE, JQ_INST_R) Y(l, JQ_SIZES_LANE, JQ_INST_L) Y(l, JQ_SIZES_LANE_TL, JQ_INST_L_TL)      \
+    Y(r, JQ_SIZES_ROWLANE, JQ_INST_R) Y(r, JQ_SIZES_ROWLANE_TL, JQ_INST_R_TL) Y(l, JQ_SIZES_LANE, JQ_INST_L)            \
+    Y(l, JQ_SIZES_LANE_TL, JQ_INST_L_TL)                                                                                \
     Y(c, JQ_SIZES_C, JQ_INST_C)
 // the host translation unit's own propagator kernels beyond those of jq_huge_kernels.h: the tangent-linear forward sweep of
 // jq_tl_kernels.h and the tangent of the adjoint sweep of jq_tl_adjoint_kernels.h (run-time size like them; every other instantiation

@@ -54,8 +54,11 @@ JQ_INST_I_HBM(JQ_DEF, JQ_NT, JQ_BW)
 #include "jq_rowlane_imr_kernels.h"
 JQ_INST_M(JQ_DEF, JQ_NT)
 #elif JQ_VARIANT == 4
-#include "jq_rowlane_kernels.h"
+#include "jq_rowlane_tl_kernels.h"
 JQ_INST_R(JQ_DEF, JQ_NT)
+#if JQ_NT >= 12                   // (JQ_SIZES_ROWLANE_TL: Ntot <= 6 has the lane kernels' twins, Ntot 7 and 8 run on the sequential route)
+JQ_INST_R_TL(JQ_DEF, JQ_NT)
+#endif
 #elif JQ_VARIANT == 3
 #include "jq_lane_tl_kernels.h"
 #define JQ_DEF_INIT(name, ...) template __global__ void name<__VA_ARGS__>(JQ_LANE_INIT_ARGS);

@@ -338,9 +338,11 @@ __device__ __forceinline__ void row_state(const PropArgs& a, const OPS& o, doubl
 // (NPJ = 12, 16: a step takes longer than the latency and a slot is 6 .. 8 KiB -- two steps ahead)
 #define JQ_RL_AHEAD(npj) ((npj) <= 8 ? 3 : 2)
 #define JQ_RL_RING_BYTES(npj) ((size_t)(JQ_RL_AHEAD(npj) + 2) * 4 * 128 * (npj))
-template <int NPJ, bool ORDERED = true>
+// (AHEAD: the distance as a template argument -- the tangent-linear kernels of jq_rowlane_tl_kernels.h, whose step is three times as long,
+//  run one step ahead in rings of three slots)
+template <int NPJ, bool ORDERED = true, int AHEAD = JQ_RL_AHEAD(NPJ)>
 struct RlRing {
-    static constexpr int D = JQ_RL_AHEAD(NPJ), R = D + 2, P = NPJ / 2, IMG = 16 * NPJ, GROUP_B = 4 * 128 * NPJ;
+    static constexpr int D = AHEAD, R = D + 2, P = NPJ / 2, IMG = 16 * NPJ, GROUP_B = 4 * 128 * NPJ;
     static constexpr size_t BYTES = (size_t)R * GROUP_B;
     const double* lds;      // slot 0
     unsigned lds0;          // ... as an LDS address (M0 of the DMA)

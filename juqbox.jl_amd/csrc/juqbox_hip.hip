@@ -12,6 +12,7 @@
 #include "jq_lane_kernels.h"
 #include "jq_lane_tl_kernels.h"
 #include "jq_rowlane_kernels.h"
+#include "jq_rowlane_tl_kernels.h"
 #include "jq_rowlane_imr_kernels.h"
 #include "jq_coop_imr_kernels.h"
 #include "jq_huge_kernels.h"
@@ -192,7 +193,7 @@ struct jq_handle {
     int jvp_per_launch = 0, jvp_chunk = 0, jvp_rounds = 0;
     // ... and the last jq_traceobjgrad_hvp, the same three (jq_plan_info "hvp")
     int hvp_per_launch = 0, hvp_chunk = 0, hvp_rounds = 0;
-    // ... and the last jq_eval_f_g_grad_hvp: its route (0: no call yet, 1 lane, 2 sequential) and the same three (jq_plan_info "ens_hvp")
+    // ... and the last jq_eval_f_g_grad_hvp: its route (0: no call yet, 1 lane, 2 sequential, 3 row-lane) and the same three (jq_plan_info "ens_hvp")
     int ens_hvp_route = 0, ens_hvp_per_launch = 0, ens_hvp_chunk = 0, ens_hvp_rounds = 0;
     // Structure embedding (try_embed): a second handle of the SAME problem with its two fastest Kronecker factors zero-padded
     // to 4 levels each (row i1 + d1 i2 + d1 d2 i3 -> i1 + 4 i2 + 16 i3), under which the operators have the JQ_BW_T4 structure;
@@ -711,7 +712,7 @@ extern "C" int jq_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int32_t
 #include "jq_host_tl.h"      // what the drivers of the tangent-linear sweeps share: budgeting, stream generation, trace reduction, timing
 #include "jq_host_jvp.h"      // jq_traceobj_jvp: the tangent of the forward map along directions of coefficient space
 #include "jq_host_hvp.h"      // jq_traceobjgrad_hvp: the derivative of the gradient along directions of coefficient space
-#include "jq_host_ens_hvp.h"      // jq_eval_f_g_grad_hvp: the same over the nodes of a risk-neutral ensemble (lane kernels: one launch per chunk)
+#include "jq_host_ens_hvp.h"      // jq_eval_f_g_grad_hvp: the same over the nodes of a risk-neutral ensemble (lane / row-lane kernels: one launch per chunk)
 #include "jq_host_multi.h"      // multi-device handles: one process, N GPUs, one RCCL all-reduce
 #include "jq_host_info.h"      // options of a live handle, plan and timing introspection
 #ifdef JQ_DUMP_SELECTION

@@ -2,8 +2,13 @@
 """Times jq_eval_f_g_grad_hvp with the library's own HIP events (jq_last_timing), two calls after a warm-up each:
   (a) swap02 at full length, one node, 1 and 16 directions, against jq_traceobjgrad_hvp on the same handle in the same process;
   (b) the SWAP-02 risk-neutral configuration (cases.swap02_rn, 512 nodes), 1 and 16 directions, against jq_eval_f_g_grad on the same
-      handle.
-Prints the body of profiles/ens_hvp_timing.txt.  Needs a GPU."""
+      handle;
+  (c) cnot2 (Ntot 12: the row-lane route) at full length with 1 and with 3 nodes, 1 and 16 directions, on a default handle and on one with
+      option lane=0 (the sequential route) -- run with JQ_LIB=<the parent commit's library> the same calls give the baseline;
+  (d) cnot2 over 512 nodes (the ensemble scripts/time_rl_ens.py times: Gauss-Legendre nodes on [-0.05, 0.05], shift 0.01 j), 1 and 16
+      directions, against jq_eval_f_g_grad on the same handle.
+Prints the body of profiles/ens_hvp_timing.txt (a, b) and of profiles/ens_hvp_rowlane_timing.txt (c, d, kernels).  Sections are chosen
+by letter on the command line (default: a b).  Needs a GPU, except `kernels`, which reads the build manifest."""
 import json
 import os
 import sys
@@ -93,7 +98,88 @@ def part_b():
     wa.close()
 
 
+def cnot2_problem():
+    p, info = jq.cases.cnot2()
+    pcof = np.array(json.load(open(os.path.join(ROOT, "tests", "golden", "cnot2.json")))["pcof0"])
+    return p, pcof, 0.01 * np.arange(p.Ntot)
+
+
+def gl_nodes(nquad):
+    if nquad == 1:
+        return np.zeros(1), np.ones(1)
+    x, w = np.polynomial.legendre.leggauss(nquad)
+    return 0.05 * x, 0.5 * w
+
+
+def part_c():
+    p, pcof, shift = cnot2_problem()
+    print("(c) cnot2: Ntot %d, N %d, %d time steps, Neumann order %d, %d coefficients, objFuncType %d; library %s" % (
+        p.Ntot, p.N, p.nsteps, p.linear_solver.max_iter, pcof.size, p.objFuncType, os.environ.get("JQ_LIB", "(this build)")))
+    for opts in (None, {"lane": 0}):
+        wa = jq.Working_Arrays_HIP(p, pcof.size, options=opts)
+        for nquad in (1, 3):
+            nodes, weights = gl_nodes(nquad)
+            jq.eval_f_g_grad(pcof, p, wa, nodes, weights, True, shift=shift)
+            g = p.last_infidelity_grad.copy()
+            for ndir in (1, 16):
+                D = directions(g, pcof.size, ndir, 13)
+                new = timed(lambda: jq.eval_f_g_grad_hvp(pcof, D, p, wa, nodes, weights, shift), wa)
+                plan = wa.plan_info()
+                tag = "options %s, %d node(s), ndir %2d" % (json.dumps(opts), nquad, ndir)
+                for k, (t, _) in enumerate(new):
+                    print(line("%s run %d" % (tag, k), t))
+                tb = min(new, key=lambda x: x[0]["ms_total"])[0]
+                nb = max(tb["n_backward_launches"] // max(tb["n_forward_launches"], 1), 1)
+                print("%s: plan %s, kernels %s, family %d; best of 2: %.2f ms; forward %.2f, backward %.2f us per time step and pass" % (
+                    tag, json.dumps(plan["ens_hvp"]), plan["last_kernels"]["object"], tb["kernel_family"], tb["ms_total"],
+                    1e3 * tb["ms_forward"] / p.nsteps, 1e3 * tb["ms_backward"] / p.nsteps / nb))
+        wa.close()
+
+
+def part_d():
+    p, pcof, shift = cnot2_problem()
+    nodes, weights = gl_nodes(512)
+    wa = jq.Working_Arrays_HIP(p, pcof.size)
+
+    def grad():
+        jq.eval_f_g_grad(pcof, p, wa, nodes, weights, True, shift=shift)
+        return p.last_infidelity_grad.copy()
+    gr = timed(grad, wa)
+    g = gr[-1][1]
+    bg = min(t["ms_total"] for t, _ in gr)
+    print("(d) cnot2 x %d nodes = %d columns (%d waves per direction)" % (nodes.size, nodes.size * p.N, (nodes.size * p.N + 3) // 4))
+    for k, (t, _) in enumerate(gr):
+        print(line("jq_eval_f_g_grad (family %d) run %d" % (t["kernel_family"], k), t))
+    for ndir in (1, 16):
+        D = directions(g, pcof.size, ndir, 14)
+        new = timed(lambda: jq.eval_f_g_grad_hvp(pcof, D, p, wa, nodes, weights, shift), wa)
+        plan = wa.plan_info()
+        for k, (t, _) in enumerate(new):
+            print(line("ndir %2d jq_eval_f_g_grad_hvp run %d" % (ndir, k), t))
+        bn = min(t["ms_total"] for t, _ in new)
+        tb = min(new, key=lambda x: x[0]["ms_total"])[0]
+        print("ndir %2d: plan %s; %.1f x one jq_eval_f_g_grad for the call, %.2f x per direction (best of 2: %.2f against %.2f ms); forward %.2f, "
+              "backward %.2f us per time step" % (ndir, json.dumps(plan["ens_hvp"]), bn / bg, bn / bg / ndir, bn, bg,
+                                                  1e3 * tb["ms_forward"] / p.nsteps, 1e3 * tb["ms_backward"] / p.nsteps))
+        r = new[-1][1]
+        print("         |infid_grad - eval_f_g_grad's| / |g| = %.2e" % (np.linalg.norm(r["infid_grad"] - g) / np.linalg.norm(g)))
+    wa.close()
+
+
+def part_kernels():
+    """registers, AGPRs, LDS and scratch of the tangent-linear row-lane kernels from the build manifest (dynamic LDS: the host's figures)"""
+    m = json.load(open(os.path.join(ROOT, "juqbox.jl_amd", "csrc", "build", "manifest.json")))
+    print("kernels (build manifest; LDS is dynamic: 2 rings of 1 536 NPJ bytes, the backward sweep adds 2 Nc images of 128 NPJ bytes):")
+    for obj in ("r_12", "r_16"):
+        for k in m["objects"][obj]["kernels"]:
+            if "rowlane_tl" in k["name"]:
+                print("  %s %s: %d VGPRs, %d AGPRs, %d SGPRs, scratch %d bytes, static LDS %d bytes, occupancy %d" % (
+                    obj, k["name"], k["vgprs"], k["agprs"], k["sgprs"], k["scratch_bytes"], k["lds_bytes"], k["occupancy"]))
+
+
 if __name__ == "__main__":
-    part_a()
-    print()
-    part_b()
+    parts = {"a": part_a, "b": part_b, "c": part_c, "d": part_d, "kernels": part_kernels}
+    for k, name in enumerate(sys.argv[1:] or ["a", "b"]):
+        if k:
+            print()
+        parts[name]()
