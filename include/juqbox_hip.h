@@ -416,11 +416,16 @@ int jq_traceobjgrad_hvp(jq_handle *h, const double *pcof, int32_t ncoeff, const 
  * x the directions of a round in ONE launch per chunk, independent of the options lane_min / lane_max (one node is served too).
  * Row-lane route: Ntot 9 .. 16 with at most four controls (and option lane != 0) runs on the tangent-linear row-lane kernels -- four
  * columns per wave, ceil(N nquad / 4) waves x the directions of a round in ONE launch per chunk, independent of option rowlane_max.
- * Sequential route: everything else jq_traceobjgrad_hvp serves (Ntot 7 and 8, which have no tangent kernel; Ntot > 16; option lane=0;
- * more than four controls) runs the nodes one after the other on its run-time-size sweeps -- correct and no faster.  Direction j does not depend on the other directions of the
- * call nor on the rounds they run in (option stream_bytes).  jq_plan_info "ens_hvp": {route: "lane" | "rowlane" | "sequential",
+ * Quad route: Ntot > 16 with the 4 x 4 x n structure of the handle's own plan (NT = 2 .. 6 blocks of 16 rows, e.g. cnot3; never an embedded
+ * twin), at most four controls and the quad-layout kernels enabled (option quad != 0) runs on the tangent-linear quad-layout kernels -- four
+ * columns per wave, up to four waves of a direction per workgroup sharing its operator images in LDS, x the directions of a round in ONE
+ * launch per chunk.
+ * Sequential route: everything else jq_traceobjgrad_hvp serves (Ntot 7 and 8, which have no tangent kernel; Ntot > 16 without that structure,
+ * with NT = 7, 8 or through an embedded twin; options lane=0 / quad=0; more than four controls) runs the nodes one after the other on its
+ * run-time-size sweeps -- correct and no faster.  Direction j does not depend on the other directions of the
+ * call nor on the rounds they run in (option stream_bytes).  jq_plan_info "ens_hvp": {route: "lane" | "rowlane" | "quad" | "sequential",
  * directions_per_launch, chunk_steps, rounds} after a call; jq_last_timing reports the lane family and NP on the lane route, the
- * row-lane family and NPJ on the row-lane route, and counts
+ * row-lane family and NPJ on the row-lane route, the quad family, NT and band 7 on the quad route, and counts
  * forward and backward launches; "last_kernels" names the instantiations.  Refused with JQ_EUNSUPPORTED: what jq_traceobjgrad_hvp
  * refuses (implicit midpoint, the Jacobi solver, full leakage weights, sv_type != 1, uncoupled controls).  JQ_EINVAL for NULL pointers
  * (all but shift are required), ndir < 1 or nquad < 1; the codes of jq_traceobjgrad for the coefficient count.  A refused call writes

@@ -342,7 +342,9 @@ end
 # eval_f_g_grad over the quadrature nodes and the derivative of its two gradients along the columns of dirs (jq_eval_f_g_grad_hvp):
 # Hessian-vector products of the risk-neutral objective, sum_i w_i d/d eps grad_i(pcof + eps dirs[:, j]).  Ntot <= 6 with at most four
 # controls: tangent-linear lane kernels, every node and direction of a round in one launch per chunk; Ntot 9 .. 16 with at most four
-# controls: the same on the tangent-linear row-lane kernels (four columns per wave); else the nodes one after the other.
+# controls: the same on the tangent-linear row-lane kernels (four columns per wave); Ntot > 16 with the 4 x 4 x n structure (NT = 2 .. 6,
+# e.g. cnot3) and at most four controls: the same on the tangent-linear quad-layout kernels (route "quad" of jq_plan_info "ens_hvp"; option
+# quad=0 switches it off); else the nodes one after the other.
 # Returns (infidelity, leak, infid_grad[ncoeff], leak_grad[ncoeff], hv_infid[ncoeff, ndir], hv_leak[ncoeff, ndir]); objFuncType == 1:
 # infid_grad / hv_infid carry the total gradient's, leak_grad / hv_leak are zero.  No Tikhonov term.
 function eval_f_g_grad_hvp(pcof::Vector{Float64}, dirs::VecOrMat{Float64}, params::objparams, wa::AbstractWorkingArraysHIP,

@@ -5,6 +5,7 @@
 #include "jq_kernels.h"
 #include "jq_rowlane_kernels.h"
 #include "jq_rowlane_tl_kernels.h"
+#include "jq_quad_tl_kernels.h"
 
 struct SplineArgs {
     const double* pcof;   // [nCoeff]
@@ -763,6 +764,74 @@ __global__ __launch_bounds__(64) void k_terminal_rowlane_tl(PropArgs a)
             state[3 * arr + base + r] = -(jq_det2(im, tr, re, ti) / N);      // nb = -lambda_i
             state[6 * arr + base + r] = jq_dot2(dim, ti, dre, tr) / N;
             state[7 * arr + base + r] = -(jq_det2(dim, tr, dre, ti) / N);
+        }
+    }
+    double* res = a.traces + ((size_t)blockIdx.y * a.nsamples + s) * 4;
+    res[0] = 1.0 - jq_dot2(re, re, im, im);
+    res[1] = a.h * lk;
+    res[2] = re;
+    res[3] = im;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Tangent-linear quad-layout kernels (jq_quad_tl_kernels.h; jq_eval_f_g_grad_hvp at Ntot > 16): initial state and terminal condition of
+// every direction.  New kernels: the state file is [row][quad][lane 16 i + 4 b + j <-> row 16 mt + 4 b + i, column j], not the
+// [row][wave][16 column + row] of the row-lane twins; the handle's slab images are read where they are (element (R, c) of an Ntot x N array:
+// ((c / 16) KT + R / 4) 64 + 16 (R % 4) + c % 16).
+// state files <- (Uinit, 0 ...) for every direction.  a.cimg: the slab image of Uinit; a.nslabs: quads; a.nsamples N columns in use.
+// grid = (quads, directions)
+__global__ __launch_bounds__(64) void k_init_quad_tl(PropArgs a)
+{
+    const int lane = threadIdx.x, NT = (a.Ntot + 15) / 16;
+    const long long w = blockIdx.x, nw = a.nslabs;
+    const long long col = 4 * w + (lane & 3);
+    const int rowb = 4 * ((lane >> 2) & 3) + (lane >> 4);
+    double* st = a.state + (size_t)blockIdx.y * (size_t)a.state_stride + w * 64 + lane;
+    const bool used = col < (long long)a.nsamples * a.N;
+    const int c = (int)(col % a.N);
+    for (int r = 0; r < JQ_QUAD_TL_ROWS(NT); ++r) {
+        const int R = 16 * r + rowb;
+        st[(size_t)r * nw * 64] = (r < NT && used) ? a.cimg[((size_t)(c / 16) * 4 * NT + R / 4) * 64 + 16 * (R % 4) + c % 16] : 0.0;
+    }
+}
+
+// Fidelity, leak, lambda(T) and its tangent per (sample, direction): k_terminal_rowlane_tl on the quad-layout state file.
+// a.cimg / a.tabs: the slab images of the target (real / imaginary part), a.h: leak scale, a.nslabs: quads, a.traces: res [direction][sample][4].
+// Thread per sample -- its columns are read wherever their quads are; grid = (ceil(samples / 64), directions)
+__global__ __launch_bounds__(64) void k_terminal_quad_tl(PropArgs a)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.nsamples) return;
+    const int N = a.N, NT = (a.Ntot + 15) / 16;
+    const size_t rs = (size_t)a.nslabs * 64, arr = (size_t)NT * rs;
+    double* state = a.state + (size_t)blockIdx.y * (size_t)a.state_stride;
+    const double *vtr = a.cimg, *vti = a.tabs;
+    auto at = [&](long long col, int R) { return (size_t)(R / 16) * rs + (size_t)(col / 4) * 64 + 16 * (R % 4) + 4 * ((R % 16) / 4) + (size_t)(col % 4); };
+    auto tg = [&](int ic, int R) { return ((size_t)(ic / 16) * 4 * NT + R / 4) * 64 + 16 * (R % 4) + ic % 16; };
+    double re = 0.0, im = 0.0, dre = 0.0, dim = 0.0, lk = 0.0;
+    for (int ic = 0; ic < N; ++ic) {
+        const long long col = (long long)s * N + ic;
+        for (int R = 0; R < a.Ntot; ++R) {
+            const size_t e = at(col, R);
+            const double u = state[e], v = state[arr + e], ud = state[4 * arr + e], vd = state[5 * arr + e];
+            const double tr = vtr[tg(ic, R)], ti = vti[tg(ic, R)];
+            re += jq_det2(u, tr, v, ti);
+            im += jq_dot2(u, ti, v, tr);
+            dre += jq_det2(ud, tr, vd, ti);
+            dim += jq_dot2(ud, ti, vd, tr);
+        }
+        for (int r = 0; r < 16; ++r) lk += state[(size_t)(JQ_QUAD_TL_ROWS(NT) - 1) * rs + at(col, r)];
+    }
+    re /= N, im /= N, dre /= N, dim /= N;
+    for (int ic = 0; ic < N; ++ic) {
+        const long long col = (long long)s * N + ic;
+        for (int R = 0; R < a.Ntot; ++R) {
+            const size_t e = at(col, R);
+            const double tr = vtr[tg(ic, R)], ti = vti[tg(ic, R)];
+            state[2 * arr + e] = jq_dot2(im, ti, re, tr) / N;         // lambda_r
+            state[3 * arr + e] = -(jq_det2(im, tr, re, ti) / N);      // nb = -lambda_i
+            state[6 * arr + e] = jq_dot2(dim, ti, dre, tr) / N;
+            state[7 * arr + e] = -(jq_det2(dim, tr, dre, ti) / N);
         }
     }
     double* res = a.traces + ((size_t)blockIdx.y * a.nsamples + s) * 4;

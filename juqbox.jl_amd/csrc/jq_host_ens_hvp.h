@@ -12,8 +12,13 @@
 // kernels of jq_rowlane_tl_kernels.h -- four columns per wave, ceil(N nquad / 4) waves x `dpl` directions in one launch per chunk, the
 // handle's row-lane images.  What differs between the two is the layout record (EnsHvpLayout) the driver reads.
 //
-// Sequential route (everything else jq_traceobjgrad_hvp serves: Ntot 7, 8 and > 16, option lane=0, more than JQ_MAXNC controls): the nodes one
-// after the other through hvp_run with the drift Hconst + eps_i diag(shift) -- correct and no faster.
+// Quad route (Ntot > 16 with the 4 x 4 x n structure of the handle's own plan, NT = 2 .. 6 blocks of 16 rows, quad-layout kernels enabled; at
+// most JQ_MAXNC controls): the same driver on the tangent-linear quad-layout kernels of jq_quad_tl_kernels.h -- four columns per wave, up to
+// JQ_QUAD_TL_WAVES waves of one direction per workgroup sharing its operator rings, the handle's T4 images and slab images.
+//
+// Sequential route (everything else jq_traceobjgrad_hvp serves: Ntot 7, 8, Ntot > 16 without that structure or with NT = 7, 8, embedded
+// structures, options lane=0 / quad=0, more than JQ_MAXNC controls): the nodes one after the other through hvp_run with the drift
+// Hconst + eps_i diag(shift) -- correct and no faster.
 static double ens_hvp_shift(const double* shift, int i) { return shift ? shift[i] : (i >= 1 ? 0.01 * pow(10.0, (double)(i - 1)) : 0.0); }
 
 struct EnsHvpArgs {
@@ -34,8 +39,8 @@ static void ens_hvp_outputs(const jq_handle* h, const EnsHvpArgs& x, const doubl
 
 // What the driver needs to know about a kernel family: the handle's images in its layout, the geometry of a wave and of the state file.
 struct EnsHvpLayout {
-    int route;                  // ens_hvp_route: 1 lane, 3 row-lane
-    int family, size;           // jq_last_timing: kernel_family, kernel_size (NP / NPJ)
+    int route;                  // ens_hvp_route: 1 lane, 3 row-lane, 4 quad
+    int family, size, band;     // jq_last_timing: kernel_family, kernel_size (NP / NPJ / NT), kernel_band
     const char* label;          // JQ_DEBUG_TIMING
     size_t stride;              // doubles per operator image
     const double *himg, *cimg, *uinit, *vtr, *vti;
@@ -44,17 +49,25 @@ struct EnsHvpLayout {
     bool slabs_are_waves;       // PropArgs::nslabs: waves (row-lane kernels) or padded columns (lane kernels)
     int tab_off;                // tables [wd(tab_off) | ws(tab_off)]
     size_t lds_fwd, lds_bwd;    // dynamic LDS bytes of the sweep kernels
+    int wpg;                    // most waves of one direction per workgroup of the sweep kernels (they share its LDS)
+    bool modes;                 // the backward kernel multiplies a trace image in the T4 mode of its control (PropArgs::bw_trace)
 };
 static EnsHvpLayout ens_hvp_layout_lane(const jq_handle* h)
 {
-    return {1, KF_LANE, h->lane_np, "tangent-linear lane", (size_t)h->lane_stride, h->d_himg_l, h->d_cimg_l, h->d_uinit_l, h->d_vtr_l, h->d_vti_l,
-            64, JQ_LANE_TL_ROWS(h->lane_np), false, h->lane_np, 0, 0};
+    return {1, KF_LANE, h->lane_np, 0, "tangent-linear lane", (size_t)h->lane_stride, h->d_himg_l, h->d_cimg_l, h->d_uinit_l, h->d_vtr_l, h->d_vti_l,
+            64, JQ_LANE_TL_ROWS(h->lane_np), false, h->lane_np, 0, 0, 1, false};
 }
 static EnsHvpLayout ens_hvp_layout_rowlane(const jq_handle* h)
 {
     const size_t rings = JQ_ROWLANE_TL_RINGS(h->rl_npj);
-    return {3, KF_ROWLANE, h->rl_npj, "tangent-linear row-lane", (size_t)h->rl_stride, h->d_himg_r, h->d_cimg_r, h->d_uinit_r, h->d_vtr_r, h->d_vti_r,
-            4, JQ_ROWLANE_TL_ROWS, true, 16, rings, rings + (size_t)2 * h->Nc * h->rl_stride * sizeof(double)};
+    return {3, KF_ROWLANE, h->rl_npj, 0, "tangent-linear row-lane", (size_t)h->rl_stride, h->d_himg_r, h->d_cimg_r, h->d_uinit_r, h->d_vtr_r, h->d_vti_r,
+            4, JQ_ROWLANE_TL_ROWS, true, 16, rings, rings + (size_t)2 * h->Nc * h->rl_stride * sizeof(double), 1, false};
+}
+static EnsHvpLayout ens_hvp_layout_quad(const jq_handle* h)
+{
+    const size_t rings = JQ_QUAD_TL_RINGS(h->mat_elems);
+    return {4, KF_QUAD, h->NT, JQ_BW_T4Q, "tangent-linear quad", (size_t)h->mat_elems, h->d_himg, h->d_cimg, h->d_uimg, h->d_vtr, h->d_vti,
+            4, JQ_QUAD_TL_ROWS(h->NT), true, 16 * h->NT, rings, rings + (size_t)2 * h->Nc * h->mat_elems * sizeof(double), JQ_QUAD_TL_WAVES, true};
 }
 
 static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& lay, prop_kernel_t kinit, prop_kernel_t kfwd, prop_kernel_t kterm, prop_kernel_t kbwd,
@@ -105,6 +118,7 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
     a.stream = d_stream.p; a.stream_gstride = (long long)b.gstride; a.group_units = 1; a.state = d_state.p; a.state_stride = (long long)sstride;
     a.colinfo = d_col.p; a.tabs = d_tabs.p; a.traces = d_tr.p; a.cimg = lay.cimg; a.stride = (long long)stride; a.m = h->m; a.nslabs = lay.slabs_are_waves ? nwaves : (int)ncols;
     a.Ncoupled = Nc; a.Ntot = h->Ntot; a.N = h->N; a.parts = 1; a.nsamples = nquad; a.sps = 1; a.tinv = 1.0 / h->T; a.use_shift = use_shift ? 1 : 0;
+    for (int q = 0; q < JQ_MAXNC && lay.modes; ++q) a.bw_trace[q] = q < Nc ? h->bw_trace[q] : 0;
     PropArgs ai = a, at = a;      // the init and terminal kernels read their images and scalars through the fields their headers name
     ai.cimg = lay.uinit;
     at.cimg = lay.vtr; at.tabs = lay.vti; at.traces = d_res.p; at.h = 0.5 * dt * (1.0 / h->T);
@@ -116,6 +130,9 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
     std::vector<double> res((size_t)nquad * 4), blk((size_t)nvec * ncoeff), gbuf((size_t)2 * nvec * ncoeff);
     std::vector<double> g0(ncoeff), g1(two_pass ? ncoeff : 0), v0((size_t)ncoeff * ndir), v1(two_pass ? (size_t)ncoeff * ndir : 0);
     const dim3 grid((unsigned)nwaves, (unsigned)dpl);
+    // the sweep kernels: wpg consecutive waves of a direction per workgroup (1 on the lane and row-lane routes: the launch it always was)
+    const int wpg = std::min(lay.wpg, nwaves);
+    const dim3 sgrid((unsigned)((nwaves + wpg - 1) / wpg), (unsigned)dpl), sblock((unsigned)(64 * wpg));
     for (int r = 0; r < rounds; ++r) {
         const int j0 = r * dpl, nd = std::min(dpl, ndir - j0);
         if ((rc = tl_upload_round(h, blk, d_pc.p, x.pcof, x.dirs, j0, nd, dpl, ncoeff))) return rc;
@@ -128,7 +145,7 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
             tl_generate(h, gen, n0, nc, dt);
             a.nsteps_chunk = nc; a.step0 = n0; a.first_chunk = (n0 == 0);
             if ((rc = tm.begin(false))) return rc;
-            hipLaunchKernelGGL(kfwd, grid, dim3(64), lay.lds_fwd, s, a);
+            hipLaunchKernelGGL(kfwd, sgrid, sblock, lay.lds_fwd, s, a);
             if ((rc = tm.end())) return rc;
         }
         hipLaunchKernelGGL(kterm, dim3((unsigned)((nquad + 63) / 64), (unsigned)dpl), dim3(64), 0, s, at);
@@ -144,7 +161,7 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
                 tl_generate(h, gen, n0, nc, -dt);
                 a.nsteps_chunk = nc; a.step0 = n0; a.first_chunk = (n0 == 0);
                 if ((rc = tm.begin(true))) return rc;
-                hipLaunchKernelGGL(kbwd, grid, dim3(64), lay.lds_bwd, s, a);
+                hipLaunchKernelGGL(kbwd, sgrid, sblock, lay.lds_bwd, s, a);
                 if ((rc = tm.end())) return rc;
                 tl_reduce_chunk(h, gen.sp, r == 0, d_tr.p, nwaves, dpl, n0, nc, 0, Nc, d_R.p, d_R.p + (size_t)cs * ntr, d_g.p + (size_t)pass * nvec * ncoeff);
             }
@@ -168,7 +185,7 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
     h->timing.svts = (long long)ndir * nquad * h->N * h->nsteps;
     h->timing.kernel_family = lay.family;
     h->timing.kernel_size = lay.size;
-    h->timing.kernel_band = 0;
+    h->timing.kernel_band = lay.band;
     h->last_kernels = sel;
     return JQ_OK;
 }
@@ -246,6 +263,14 @@ extern "C" int jq_eval_f_g_grad_hvp(jq_handle* h, const double* pcof, int32_t nc
             const int np = h->rl_npj;
             const prop_kernel_t kfwd = pick(sel.fwd, np, -1, "k_forward_rowlane_tl", {np}), kbwd = pick(sel.bwd, np, -1, "k_backward_rowlane_tl", {np});
             if (kfwd && kbwd) return ens_hvp_lane(h, x, ens_hvp_layout_rowlane(h), k_init_rowlane_tl, kfwd, k_terminal_rowlane_tl, kbwd, sel);
+        }
+        // quad route: Ntot > 16 with the 4 x 4 x n structure of the handle's own plan (never an embedded twin) and its quad-layout kernels enabled
+        // (option quad=0 switches the route off); NT = 7, 8 have no tangent kernels (their backward kernels need scratch) and stay sequential
+        if (h->BW == JQ_BW_T4 && h->quad_max_slabs > 0 && h->NT >= 2 && h->Nc <= JQ_MAXNC && h->mat_elems == (long long)JQ_T4_ELEMS(h->NT)) {
+            KernelSel sel = sel_start();
+            const int nt = h->NT;
+            const prop_kernel_t kfwd = pick(sel.fwd, nt, JQ_BW_T4Q, "k_forward_quad_tl", {nt}), kbwd = pick(sel.bwd, nt, JQ_BW_T4Q, "k_backward_quad_tl", {nt});
+            if (kfwd && kbwd) return ens_hvp_lane(h, x, ens_hvp_layout_quad(h), k_init_quad_tl, kfwd, k_terminal_quad_tl, kbwd, sel);
         }
         return ens_hvp_sequential(h, x);
     });

@@ -183,7 +183,7 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
         kv("hvp", std::string("{\"directions_per_launch\": ") + num(h->hvp_per_launch) + ", \"chunk_steps\": " + num(h->hvp_chunk) + ", \"rounds\": " + num(h->hvp_rounds) + "}");
     // jq_eval_f_g_grad_hvp (after a call): the route its nodes took and the same three
     if (h->ens_hvp_route > 0)
-        kv("ens_hvp", std::string("{\"route\": \"") + (h->ens_hvp_route == 1 ? "lane" : h->ens_hvp_route == 3 ? "rowlane" : "sequential") + "\", \"directions_per_launch\": " + num(h->ens_hvp_per_launch) +
+        kv("ens_hvp", std::string("{\"route\": \"") + (h->ens_hvp_route == 1 ? "lane" : h->ens_hvp_route == 3 ? "rowlane" : h->ens_hvp_route == 4 ? "quad" : "sequential") + "\", \"directions_per_launch\": " + num(h->ens_hvp_per_launch) +
                           ", \"chunk_steps\": " + num(h->ens_hvp_chunk) + ", \"rounds\": " + num(h->ens_hvp_rounds) + "}");
     o += "}";
     if (buflen > 0) {

@@ -6,7 +6,9 @@ typedef void (*lane_init_t)(JQ_LANE_INIT_ARGS);
 typedef void (*lane_term_t)(JQ_LANE_TERM_ARGS);
 
 // templates whose definitions the host does not include (jq_cq_kernels.h, jq_cq_split_kernels.h, jq_quad_split_kernels.h, jq_quad_imr_kernels.h,
-// jq_cq_imr_kernels.h; jq_coop_imr_kernels.h)
+// jq_cq_imr_kernels.h; jq_coop_imr_kernels.h; jq_quad_tl_kernels.h, whose kernels need the quad layout's row type)
+template <int NT> __global__ void k_forward_quad_tl(PropArgs);
+template <int NT> __global__ void k_backward_quad_tl(PropArgs);
 template <int NT, bool MODD, int NS, bool WLR = false, bool DN = false> __global__ void k_forward_cq(PropArgs);
 template <int NT, bool MODD, bool ORD, bool WLR = false, bool DN = false> __global__ void k_backward_cq(PropArgs);
 template <int NT, bool MODD, bool ORD, int NR = 3, bool WLR = false, bool DN = false> __global__ void k_backward_cq3(PropArgs);

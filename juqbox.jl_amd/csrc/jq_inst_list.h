@@ -58,6 +58,10 @@
 #define JQ_INST_P(X, nt, bw)                                                                                            \
     X(k_backward_qsplit, nt, false, 4) X(k_backward_qsplit, nt, true, 4) X(k_backward_qsplit, nt, false, 2)             \
     X(k_backward_qsplit, nt, true, 2) X(k_backward_qsplit, nt, true, 4, true) X(k_backward_qsplit, nt, true, 2, true)
+// t_: tangent-linear twins of the quad-layout kernels (jq_quad_tl_kernels.h; jq_eval_f_g_grad_hvp at Ntot > 16): column quads x directions.
+// (JQ_INST_T: what every t_ object of the Makefile's QUAD list holds -- nothing: t_1_7 is empty)
+#define JQ_INST_T(X, nt, bw)
+#define JQ_INST_T_TL(X, nt, bw) X(k_forward_quad_tl, nt) X(k_backward_quad_tl, nt)
 // v_: cooperative-quad kernels of the implicit-midpoint integrator -- <NT, DN>; imr3: three workgroups per evaluation; imr2: state and
 // adjoint chain on two sets of waves (NT <= 6); v_2_7 also: the dense policy
 #define JQ_INST_V(X, nt, bw) X(k_forward_cq_imr, nt) X(k_backward_cq_imr, nt) X(k_backward_cq_imr3, nt)
@@ -108,6 +112,9 @@
     L(A, 16, 2) L(A, 16, 15)
 #define JQ_SIZES_QUAD(L, A) L(A, 1, 7) L(A, 2, 7) L(A, 3, 7) L(A, 4, 7) L(A, 5, 7) L(A, 6, 7)
 #define JQ_SIZES_QUADBIG(L, A) L(A, 7, 7) L(A, 8, 7)
+// (the tangent-linear kernels of the t_ objects: none at NT = 1 -- Ntot <= 16, the lane and row-lane routes -- and none at NT = 7, 8, whose
+// backward kernels do not build without scratch)
+#define JQ_SIZES_QUAD_TL(L, A) L(A, 2, 7) L(A, 3, 7) L(A, 4, 7) L(A, 5, 7) L(A, 6, 7)
 #define JQ_SIZES_LANE(L, A) L(A, 2) L(A, 4) L(A, 6) L(A, 8)
 // (the tangent-linear kernels of the l_ objects: none at NP = 8, whose backward kernel does not fit the 512 registers of a wave without scratch)
 #define JQ_SIZES_LANE_TL(L, A) L(A, 2) L(A, 4) L(A, 6)
@@ -126,7 +133,8 @@
     Y(k, JQ_SIZES_SLAB, JQ_INST_K) Y(j, JQ_SIZES_SLAB, JQ_INST_J) Y(k, JQ_SIZES_QUAD8, JQ_INST_KQ)                      \
     Y(s, JQ_SIZES_QUAD8, JQ_INST_S) Y(w, JQ_SIZES_QUAD8, JQ_INST_WQ) Y(w, JQ_SIZES_WX, JQ_INST_W)                       \
     Y(x, JQ_SIZES_WX, JQ_INST_X) Y(u, JQ_SIZES_QUAD7, JQ_INST_U) Y(u, JQ_SIZES_DENSE, JQ_INST_U_DENSE)                  \
-    Y(p, JQ_SIZES_QUAD, JQ_INST_P) Y(v, JQ_SIZES_QUAD7, JQ_INST_V) Y(v, JQ_SIZES_QUAD, JQ_INST_V_IMR2)                  \
+    Y(p, JQ_SIZES_QUAD, JQ_INST_P) Y(t, JQ_SIZES_QUAD, JQ_INST_T) Y(t, JQ_SIZES_QUAD_TL, JQ_INST_T_TL)                  \
+    Y(v, JQ_SIZES_QUAD7, JQ_INST_V) Y(v, JQ_SIZES_QUAD, JQ_INST_V_IMR2)                                                 \
     Y(v, JQ_SIZES_DENSE, JQ_INST_V_DENSE) Y(q, JQ_SIZES_QUAD8, JQ_INST_Q) Y(i, JQ_SIZES_I, JQ_INST_I)                   \
     Y(i, JQ_SIZES_C, JQ_INST_I_PARTS) Y(i, JQ_SIZES_HBM, JQ_INST_I_HBM) Y(m, JQ_SIZES_ROWLANE, JQ_INST_M)               \
     Y(r, JQ_SIZES_ROWLANE, JQ_INST_R) Y(r, JQ_SIZES_ROWLANE_TL, JQ_INST_R_TL) Y(l, JQ_SIZES_LANE, JQ_INST_L)            \

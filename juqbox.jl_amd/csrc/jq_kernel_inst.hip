@@ -11,9 +11,10 @@
 //             11: kernels with the low-rank full leakage weights compiled in: quad layout with one slab per workgroup (JQ_BW = 7),
 //                 slab kernels (other JQ_BW; built for <1, 0> and <6, 5>, which have no cooperative sibling)
 //             13: variant 11's slab kernels with the Jacobi solver
+//             14: tangent-linear twins of the quad-layout kernels (JQ_BW = 7; jq_eval_f_g_grad_hvp at Ntot > 16)
 //             12: quad-layout backward sweep with the state and the adjoint chain of a column quad on two waves (JQ_BW = 7)
 #if !defined(JQ_NT) || !defined(JQ_BW) || !defined(JQ_VARIANT)
-#error "compile with -DJQ_NT=<tiles> -DJQ_BW=<band> -DJQ_VARIANT=<0..13>"
+#error "compile with -DJQ_NT=<tiles> -DJQ_BW=<band> -DJQ_VARIANT=<0..14>"
 #endif
 #include "jq_inst_list.h"
 #define JQ_DEF(name, ...) template __global__ void name<__VA_ARGS__>(PropArgs);
@@ -26,6 +27,12 @@ JQ_INST_U_DENSE(JQ_DEF, JQ_NT, JQ_BW)
 #elif JQ_VARIANT == 12  // quad layout, backward sweep split over two waves per column quad (mid-size ensembles)
 #include "jq_quad_split_kernels.h"
 JQ_INST_P(JQ_DEF, JQ_NT, JQ_BW)
+#elif JQ_VARIANT == 14  // quad layout, tangent-linear twins: column quads x directions
+#include "jq_quad_tl_kernels.h"
+JQ_INST_T(JQ_DEF, JQ_NT, JQ_BW)
+#if JQ_NT >= 2                    // (JQ_SIZES_QUAD_TL: NT = 1 is Ntot <= 16, which has the lane and row-lane kernels' twins)
+JQ_INST_T_TL(JQ_DEF, JQ_NT, JQ_BW)
+#endif
 #elif JQ_VARIANT == 10  // cooperative-quad kernels of the implicit-midpoint integrator (JQ_BW = 7, N = 4)
 #include "jq_cq_imr_kernels.h"
 JQ_INST_V(JQ_DEF, JQ_NT, JQ_BW)

@@ -204,8 +204,11 @@ def eval_f_g_grad_hvp(pcof, dirs, params, wa, nodes=(0.0,), weights=(1.0,), shif
     eps = 0 -- exact derivatives of the gradients eval_f_g_grad returns, truncated Neumann series included (not symmetric at truncation
     level, traceobjgrad_hvp).  Ntot <= 6 with at most four controls: tangent-linear lane kernels, every node and every direction of a
     round in ONE launch per chunk (route "lane"); Ntot 9 .. 16 with at most four controls: the same on the tangent-linear row-lane
-    kernels, four columns per wave (route "rowlane"); everything else traceobjgrad_hvp serves (Ntot 7, 8 and > 16, option lane=0, more
-    than four controls): the nodes one after the other (route "sequential"; wa.plan_info()["ens_hvp"]["route"] says which).
+    kernels, four columns per wave (route "rowlane"); Ntot > 16 with the 4 x 4 x n structure in the handle's own plan (NT = 2 .. 6 blocks
+    of 16 rows, e.g. cnot3) and at most four controls: the same on the tangent-linear quad-layout kernels (route "quad"; option quad=0
+    switches it off); everything else traceobjgrad_hvp serves (Ntot 7, 8, Ntot > 16 without that structure, with NT = 7, 8 or through an
+    embedded twin, options lane=0 / quad=0, more than four controls): the nodes one after the other (route "sequential";
+    wa.plan_info()["ens_hvp"]["route"] says which).
 
     dirs: an ncoeff x ndir array (one direction per column) or a single vector.  Returns a dict: infidelity, leak, infid_grad[ncoeff],
     leak_grad[ncoeff] (as eval_f_g_grad leaves them in params.last_*; objFuncType == 1: infid_grad is the total gradient, leak_grad
@@ -256,7 +259,7 @@ def eval_hessvec_par(pcof, d, params, wa, nodes=(0.0,), weights=(1.0,)):
     """The derivative along d of what eval_grad_f_par returns (the exact-Hessian callback of setup_ipopt_problem(hessian="exact")):
     hv_infid of eval_f_g_grad_hvp -- objFuncType == 1: the derivative of the total gradient, which that call returns as hv_infid with
     hv_leak zero -- plus the second derivative of the Tikhonov term.  The routes are eval_f_g_grad_hvp's: lane kernels (Ntot <= 6),
-    row-lane kernels (Ntot 9 .. 16), else the nodes one after the other."""
+    row-lane kernels (Ntot 9 .. 16), quad-layout kernels (Ntot > 16 with the 4 x 4 x n structure), else the nodes one after the other."""
     d = np.asarray(d, dtype=np.float64)
     r = eval_f_g_grad_hvp(pcof, d, params, wa, nodes, weights)
     hv = r["hv_infid"][:, 0]
@@ -490,8 +493,8 @@ def setup_ipopt_problem(params, wa, nCoeff, minCoeff, maxCoeff, maxIter=50, lbfg
     the callbacks memoise through eval_f_g_grad_members -- the risk-neutral objective over miscalibrated amplitudes / crosstalk.  drifts and
     ctrl_mix may be given together (member i has both) with ONE weight vector, under either keyword; giving both weight keywords is an error.
     hessian: "limited-memory" (the reference's L-BFGS approximation; the default changes nothing) or "exact": prob.eval_hessvec(pcof, d) =
-    eval_hessvec_par over the nodes (one launch per chunk on the lane kernels at Ntot <= 6 and on the row-lane kernels at Ntot 9 .. 16,
-    the nodes one after the other otherwise), and run_optimizer drives scipy's trust-constr with it.  "exact" with objFuncType == 3 (the leakage
+    eval_hessvec_par over the nodes (one launch per chunk on the lane kernels at Ntot <= 6, on the row-lane kernels at Ntot 9 .. 16 and on
+    the quad-layout kernels at Ntot > 16 with the 4 x 4 x n structure, the nodes one after the other otherwise), and run_optimizer drives scipy's trust-constr with it.  "exact" with objFuncType == 3 (the leakage
     is a constraint), drifts or ctrl_mix raises ValueError: those Hessians are not built.
     Shape errors raise ValueError before any library call."""
     if hessian not in ("limited-memory", "exact"):
