@@ -1643,18 +1643,22 @@ __device__ __forceinline__ void horner_add(Arr<NT>& out, const Arr<NT>& bpa, con
     int rem = m - 1;  // Horner updates before the final product
     if constexpr (SC) {
         static_assert(!SC || (BW == JQ_BW_T4Q && !JAC), "SC: quad layout, Neumann solver");
-        if (rem == 0) {
-            mm_t4s<NT, false>(out, bpa, S, A);
-            return;
-        }
+        // ONE final product for every m, entered with the iterate in Ya, and the odd product in FRONT of the pair loop: with a final
+        // product per path (m == 1 on the LDS operand, the tail behind the loop) hipcc formed the result in spare registers and
+        // copied it home where the paths join -- six v_mov_b64 per chain, four chains per backward step.  m == 1 copies A instead.
         OpS<NT> op;
         t4s_load(op, S);
-        mm_t4s_regs(Ya, A, op, A);
-        for (--rem; rem >= 2; rem -= 2) {      // (two products per iteration: see below)
-            mm_t4s_regs(Ya, A, op, Ya);
-            mm_t4s_regs(Ya, A, op, Ya);
+        if (rem == 0) {
+            asm volatile("");      // (keeps the copy in this block: hipcc otherwise makes it in front of the branch, for every m)
+            Ya = A;
+        } else {
+            mm_t4s_regs(Ya, A, op, A);
+            if (--rem & 1) mm_t4s_regs(Ya, A, op, Ya);
+            for (; rem >= 2; rem -= 2) {       // (two products per iteration: see below)
+                mm_t4s_regs(Ya, A, op, Ya);
+                mm_t4s_regs(Ya, A, op, Ya);
+            }
         }
-        if (rem > 0) mm_t4s_regs(Ya, A, op, Ya);
         mm_t4s_regs(out, bpa, op, Ya);
         return;
     }

@@ -13,7 +13,7 @@ EXP_OBJ=${EXP_OBJ:-k_6_7}; EXP_VARIANT=${EXP_VARIANT:-0}
 SCHED=${EXP_SCHED-$([ "$EXP_VARIANT" = 0 ] && echo "-mllvm -amdgpu-sched-strategy=iterative-maxocc")}
 # register form of the MFMA results as the Makefile builds the object: k_*_7 ships in hipcc's default form, the others in VGPR form
 FORM=${EXP_FORM-$([ "$EXP_VARIANT" = 0 ] || echo "-mllvm -amdgpu-mfma-vgpr-form=1")}
-OBJS=$(ls build/*.o | grep -v "build/$EXP_OBJ.o")
+OBJS=$(ls build/*.o | grep -v -e "build/$EXP_OBJ.o" -e "build/dump_host.o")      # (dump_host.o: the host code again, for build/dump_selection)
 for spec in "$@"; do
   tag=${spec%%:*}; flags=${spec#*:}
   ( /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -DJQ_NT=6 -DJQ_BW=7 -DJQ_VARIANT=$EXP_VARIANT $flags \
