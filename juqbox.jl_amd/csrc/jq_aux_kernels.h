@@ -595,248 +595,182 @@ __global__ __launch_bounds__(256) void k_pop_max(const double* __restrict__ hr, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Row-lane kernels (jq_rowlane_kernels.h): initial state and terminal condition in their state-file layout
-// state file <- (Uinit, 0, ...).  uinit: [N][16] (column ic of Uinit, zero padded).  grid = waves, block = 64
+// Column-layout state files (lane, row-lane and tangent-linear quad kernels): initial state and terminal condition.  A sample's N columns
+// may lie anywhere in the file, so the terminal kernel is a thread per sample that walks them through a column map -- where element
+// (array, row, column) of a layout lives.  Arrays 0 .. 3 are U, V, MU, NB, arrays 4 .. 7 their tangents (tangent-linear files).
+//   at(arr, R, col)  offset of row R, column col of state array arr
+//   leak(col, k)     the k-th of the column's nleak leak partials, k < nleak
+//   target(ic, R)    offset of element (R, ic) in the target / dVds images of the layout
+//   nrows            rows summed per column
+// (The slab-layout kernels above -- k_init_state, k_terminal, k_terminal_parts, k_terminal_imr -- and k_init_tl / k_terminal_tl /
+// k_terminal_hvp are a different algorithm: a workgroup per slab or sample that reduces across its lanes through LDS, in another order.)
+
+// lane kernels (jq_lane_kernels.h, jq_lane_tl_kernels.h): [array][row][column] with the column fastest; images [N][NP]
+struct LaneMap {
+    static constexpr int nleak = 1;
+    int nrows;              // NP
+    long long ncols;        // padded columns
+    int leak_row;           // the last row of the file
+    __device__ __forceinline__ size_t at(int arr, int R, long long col) const { return ((size_t)arr * nrows + R) * ncols + col; }
+    __device__ __forceinline__ size_t leak(long long col, int) const { return (size_t)leak_row * ncols + col; }
+    __device__ __forceinline__ size_t target(int ic, int R) const { return ic * nrows + R; }
+};
+// row-lane kernels (jq_rowlane_kernels.h, jq_rowlane_tl_kernels.h, jq_rowlane_imr_kernels.h): [array][wave][16 column + row]; images [N][16].
 // Column packing: every `cpw` consecutive columns start at a fresh group of `wpg` waves and fill its 4 wpg slots from the front.
 // wpg = 1: columns per wave (4, or N*floor(4/N) in the sample-aligned packing of the implicit-midpoint kernels); grouped batches: cpw = the
-// columns of one control vector (a multiple of N), wpg = the waves it owns
-__global__ void k_init_state_rowlane(double* state, long long nw, const double* __restrict__ uinit, int N, long long ncols_used,
-                                     int cpw, int wpg)
+// columns of one control vector (a multiple of N), wpg = the waves it owns, so that no wave holds the columns of two.  (The implicit-midpoint
+// route has no grouped batches: its plan sets wpg = 1, jq_host_plan.h, and init and terminal kernel both take the plan's value.)
+struct RowlaneMap {
+    static constexpr int nleak = 16, nrows = 16;
+    long long nw;           // waves
+    int cpw, wpg, leak_row;
+    __device__ __forceinline__ size_t at(int arr, int R, long long col) const
+    {
+        return (size_t)arr * nw * 64 + (size_t)(col / cpw) * wpg * 64 + (size_t)(col % cpw) * 16 + R;
+    }
+    __device__ __forceinline__ size_t leak(long long col, int k) const { return at(leak_row, k, col); }
+    __device__ __forceinline__ size_t target(int ic, int R) const { return ic * 16 + R; }
+};
+// tangent-linear quad-layout kernels (jq_quad_tl_kernels.h): [row][quad][lane 16 i + 4 b + j <-> row 16 mt + 4 b + i, column j], NT rows of
+// 64 doubles per array; the handle's slab images are read where they are (element (R, c) of an Ntot x N array:
+// ((c / 16) KT + R / 4) 64 + 16 (R % 4) + c % 16, KT = 4 NT)
+struct QuadMap {
+    static constexpr int nleak = 16;
+    int nrows;              // Ntot
+    int NT;
+    long long nq;           // quads
+    int leak_row;
+    size_t astride;         // NT nq 64, the doubles of an array.  (A member: spelled NT * nq * 64 in at(), hipcc folds the array index into the
+                            // row term -- (arr NT + R / 16) nq 64 -- and forms every array's offset anew with a 64-bit multiply per row.)
+    __device__ __forceinline__ size_t elem(int R, long long col) const
+    {
+        return (size_t)(R / 16) * ((size_t)nq * 64) + (size_t)(col / 4) * 64 + 16 * (R % 4) + 4 * ((R % 16) / 4) + (size_t)(col % 4);
+    }
+    __device__ __forceinline__ size_t at(int arr, int R, long long col) const { return arr * astride + elem(R, col); }
+    __device__ __forceinline__ size_t leak(long long col, int k) const { return (size_t)leak_row * ((size_t)nq * 64) + elem(k, col); }
+    __device__ __forceinline__ size_t target(int ic, int R) const { return ((size_t)(ic / 16) * 4 * NT + R / 4) * 64 + 16 * (R % 4) + ic % 16; }
+};
+
+// state files <- (Uinit, 0 ...): one file per grid row, dstride doubles apart (the directions of jq_eval_f_g_grad_hvp; an evaluation has one).
+// uinit: [N][NP] (column ic of Uinit, zero padded); rows: rows of the file.  thread per column, grid = (columns / 64, files)
+__global__ void k_init_lane(double* state, long long ncols, int NP, int rows, long long dstride, const double* __restrict__ uinit, int N,
+                            long long ncols_used)
+{
+    const long long col = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (col >= ncols) return;
+    double* st = state + (size_t)blockIdx.y * (size_t)dstride;
+    const int ic = (int)(col % N);
+    for (int r = 0; r < rows; ++r) st[(size_t)r * ncols + col] = (r < NP && col < ncols_used) ? uinit[ic * NP + r] : 0.0;
+}
+
+// ... in the row-lane layout.  uinit: [N][16]; cpw, wpg: the column packing (RowlaneMap).  grid = (waves, files), block = 64
+__global__ void k_init_rowlane(double* state, long long nw, int rows, long long dstride, const double* __restrict__ uinit, int N,
+                               long long ncols_used, int cpw, int wpg)
 {
     const int lane = threadIdx.x;
     const long long w = blockIdx.x;
     const int c = 4 * (int)(w % wpg) + (lane >> 4);      // slot inside the group
     const long long col = (w / wpg) * cpw + c;
-    for (int r = 0; r < JQ_ROWLANE_ROWS; ++r) {
-        double val = 0.0;
-        if (r == 0 && c < cpw && col < ncols_used) val = uinit[(col % N) * 16 + (lane & 15)];
-        state[((size_t)r * nw + w) * 64 + lane] = val;
+    double* st = state + (size_t)blockIdx.y * (size_t)dstride + w * 64 + lane;
+    const bool used = c < cpw && col < ncols_used;
+    for (int r = 0; r < rows; ++r) st[(size_t)r * nw * 64] = (r == 0 && used) ? uinit[(col % N) * 16 + (lane & 15)] : 0.0;
+}
+
+// ... in the tangent-linear quad layout.  uimg: the slab image of Uinit.  grid = (quads, directions), block = 64
+__global__ __launch_bounds__(64) void k_init_quad_tl(double* state, long long nq, long long dstride, const double* __restrict__ uimg, int NT,
+                                                     int N, long long ncols_used)
+{
+    const int lane = threadIdx.x;
+    const long long w = blockIdx.x;
+    const long long col = 4 * w + (lane & 3);
+    const int rowb = 4 * ((lane >> 2) & 3) + (lane >> 4);
+    double* st = state + (size_t)blockIdx.y * (size_t)dstride + w * 64 + lane;
+    const bool used = col < ncols_used;
+    const int c = (int)(col % N);
+    for (int r = 0; r < JQ_QUAD_TL_ROWS(NT); ++r) {
+        const int R = 16 * r + rowb;
+        st[(size_t)r * nq * 64] = (r < NT && used) ? uimg[((size_t)(c / 16) * 4 * NT + R / 4) * 64 + 16 * (R % 4) + c % 16] : 0.0;
     }
 }
 
-// fidelity, leak and adjoint terminal condition per sample (thread per sample; see k_terminal)
-// (mode, dvr, dvi: see k_terminal; the dVds image has the layout of vtr / vti)
-// cpw, wpg: the column packing of k_init_state_rowlane (4, 1; grouped batches: the columns and the waves of one control vector, so that
-// no wave holds the columns of two)
-__global__ void k_terminal_rowlane(double* state, long long nw, const double* __restrict__ vtr, const double* __restrict__ vti,
-                                   int N, int nsamples, double leak_scale, double* res, const double* __restrict__ dvr,
-                                   const double* __restrict__ dvi, int mode, int cpw, int wpg)
+// Fidelity, leak integral and adjoint terminal condition per sample (see k_terminal), thread per sample; grid = (ceil(samples / 64), files),
+// block = 64.  File blockIdx.y lies dstride doubles behind the one before and writes res[blockIdx.y][sample][4].  vtr, vti (dvr, dvi:
+// the dVds image, read only when mode != 1): the images of the map's layout.
+//   EP_SV   Stormer-Verlet, mode 1 .. 4 as in k_terminal
+//   EP_IMR  implicit midpoint (src/evalobjgrad.jl:1221-1271): secondaryobjf = dt * tinv / 4 * sum(penal_m) (leak_scale),
+//           lambda(T) = -2/N^2 (s1 Vtr + s2 Vti),  -2/N^2 (-s1 Vti + s2 Vtr)  with s1 + i s2 = N s  (true lambda_i, not negated)
+//   EP_TL   tangent-linear files: mode 1 and its derivative, sd = tr(Vtg' Vd) / N and the tangent sd conj(Vtg) / N of lambda(T) in arrays 6, 7
+// Every sum is a serial chain over the sample's columns in order and their rows in order.
+enum { EP_SV, EP_IMR, EP_TL };
+template <class Map, int FLAVOR>
+__global__ __launch_bounds__(64) void k_terminal_cols(Map m, double* state, long long dstride, const double* __restrict__ vtr,
+                                                      const double* __restrict__ vti, const double* __restrict__ dvr,
+                                                      const double* __restrict__ dvi, int mode, int N, int nsamples, double leak_scale,
+                                                      double* res)
 {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = blockIdx.x * 64 + threadIdx.x;
     if (s >= nsamples) return;
-    double re = 0.0, im = 0.0, lk = 0.0;
-    for (int ic = 0; ic < N; ++ic) {
-        const long long col = (long long)s * N + ic;
-        const size_t base = (size_t)(col / cpw) * wpg * 64 + (size_t)(col % cpw) * 16;
-        for (int r = 0; r < 16; ++r) {
-            const double u = state[base + r], v = state[(size_t)nw * 64 + base + r];
-            const double tr = vtr[ic * 16 + r], ti = vti[ic * 16 + r];
-            re += jq_det2(u, tr, v, ti);
-            im += jq_dot2(u, ti, v, tr);
-            lk += state[(size_t)(JQ_ROWLANE_ARRAYS + JQ_MAXNC) * nw * 64 + base + r];
-        }
-    }
-    re /= N;
-    im /= N;
-    double dre = 0.0, dim = 0.0;
-    if (mode >= 3) {      // s_D: the same sums against the dVds image
+    state += (size_t)blockIdx.y * (size_t)dstride;
+    res += ((size_t)blockIdx.y * nsamples + s) * 4;
+    constexpr bool TL = FLAVOR == EP_TL;
+    if (FLAVOR != EP_SV) mode = 1;
+    // the second trace (dre, dim): the tangent state against the target (EP_TL), the state against the dVds image (s_D, modes 3 and 4)
+    // (the nest is compiled with and without it: tested at run time inside the row loop, it keeps hipcc from merging a column's loads)
+    double re = 0.0, im = 0.0, lk = 0.0, dre = 0.0, dim = 0.0;
+    auto sums = [&](auto second) {
         for (int ic = 0; ic < N; ++ic) {
             const long long col = (long long)s * N + ic;
-            const size_t base = (size_t)(col / cpw) * wpg * 64 + (size_t)(col % cpw) * 16;
-            for (int r = 0; r < 16; ++r) {
-                const double u = state[base + r], v = state[(size_t)nw * 64 + base + r];
-                const double tr = dvr[ic * 16 + r], ti = dvi[ic * 16 + r];
-                dre += jq_det2(u, tr, v, ti);
-                dim += jq_dot2(u, ti, v, tr);
+            for (int R = 0; R < m.nrows; ++R) {
+                const double u = state[m.at(0, R, col)], v = state[m.at(1, R, col)];
+                const double tr = vtr[m.target(ic, R)], ti = vti[m.target(ic, R)];
+                re += jq_det2(u, tr, v, ti);
+                im += jq_dot2(u, ti, v, tr);
+                if constexpr (decltype(second)::value) {
+                    const double a = TL ? state[m.at(4, R, col)] : u, b = TL ? state[m.at(5, R, col)] : v;
+                    const double xr = TL ? tr : dvr[m.target(ic, R)], xi = TL ? ti : dvi[m.target(ic, R)];
+                    dre += jq_det2(a, xr, b, xi);
+                    dim += jq_dot2(a, xi, b, xr);
+                }
             }
+            for (int k = 0; k < Map::nleak; ++k) lk += state[m.leak(col, k)];
         }
-        dre /= N;
-        dim /= N;
-    }
+    };
+    if (TL || mode >= 3) sums(std::true_type{});
+    else sums(std::false_type{});
+    re /= N, im /= N, dre /= N, dim /= N;
+    // lambda(T) = a conj(X)/N  (+ s_D conj(T)/N in mode 4): a = s_D in mode 3, X = D in modes 2 and 4
     const double are = (mode == 3) ? dre : re, aim = (mode == 3) ? dim : im;
     const bool from_d = (mode == 2 || mode == 4);
     const double *xr = from_d ? dvr : vtr, *xi = from_d ? dvi : vti;
     for (int ic = 0; ic < N; ++ic) {
         const long long col = (long long)s * N + ic;
-        const size_t base = (size_t)(col / cpw) * wpg * 64 + (size_t)(col % cpw) * 16;
-        for (int r = 0; r < 16; ++r) {
-            const double tr = xr[ic * 16 + r], ti = xi[ic * 16 + r];
-            double lr = jq_dot2(aim, ti, are, tr) / N, nb = -(jq_det2(aim, tr, are, ti) / N);
+        for (int R = 0; R < m.nrows; ++R) {
+            const double tr = xr[m.target(ic, R)], ti = xi[m.target(ic, R)];
+            double lr = jq_dot2(aim, ti, are, tr), nb = jq_det2(aim, tr, are, ti);
+            if constexpr (FLAVOR == EP_IMR) {
+                // (k_terminal_rowlane_imr spelled these and the sums above a b + c d and left the fusion to the compiler; its code object fused
+                // u tr and v tr of the trace, re tr and im tr here and im im of |s|^2, and rounded the other product: the calls of the other flavours)
+                lr = -2.0 / N * lr;      // lambda_r
+                nb = -2.0 / N * nb;      // the true lambda_i
+            } else {
+                lr = lr / N;             // lambda_r
+                nb = -(nb / N);          // nb = -lambda_i
+            }
             if (mode == 4) {
-                const double yr = vtr[ic * 16 + r], yi = vti[ic * 16 + r];
+                const double yr = vtr[m.target(ic, R)], yi = vti[m.target(ic, R)];
                 lr += jq_dot2(dim, yi, dre, yr) / N;
                 nb += -(jq_det2(dim, yr, dre, yi) / N);
             }
-            state[(size_t)2 * nw * 64 + base + r] = lr;      // lambda_r
-            state[(size_t)3 * nw * 64 + base + r] = nb;      // nb = -lambda_i
+            state[m.at(2, R, col)] = lr;
+            state[m.at(3, R, col)] = nb;
+            if constexpr (TL) {
+                state[m.at(6, R, col)] = jq_dot2(dim, ti, dre, tr) / N;
+                state[m.at(7, R, col)] = -(jq_det2(dim, tr, dre, ti) / N);
+            }
         }
     }
-    res[(size_t)s * 4 + 0] = 1.0 - jq_dot2(re, re, im, im);
-    res[(size_t)s * 4 + 1] = leak_scale * lk;
-    res[(size_t)s * 4 + 2] = re;
-    res[(size_t)s * 4 + 3] = im;
-}
-
-// implicit-midpoint variant (src/evalobjgrad.jl:1221-1271): secondaryobjf = dt * tinv / 4 * sum(penal_m) (leak_scale),
-// lambda(T) = -2/N^2 (s1 Vtr + s2 Vti),  -2/N^2 (-s1 Vti + s2 Vtr)  with s1 + i s2 = N s  (true lambda_i, not negated)
-__global__ void k_terminal_rowlane_imr(double* state, long long nw, const double* __restrict__ vtr, const double* __restrict__ vti,
-                                       int N, int nsamples, double leak_scale, double* res, int cpw)
-{
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= nsamples) return;
-    double re = 0.0, im = 0.0, lk = 0.0;
-    for (int ic = 0; ic < N; ++ic) {
-        const long long col = (long long)s * N + ic;
-        const size_t base = (size_t)(col / cpw) * 64 + (size_t)(col % cpw) * 16;
-        for (int r = 0; r < 16; ++r) {
-            const double u = state[base + r], v = state[(size_t)nw * 64 + base + r];
-            const double tr = vtr[ic * 16 + r], ti = vti[ic * 16 + r];
-            re += u * tr - v * ti;
-            im += u * ti + v * tr;
-            lk += state[(size_t)(JQ_ROWLANE_ARRAYS + JQ_MAXNC) * nw * 64 + base + r];
-        }
-    }
-    re /= N;
-    im /= N;
-    for (int ic = 0; ic < N; ++ic) {
-        const long long col = (long long)s * N + ic;
-        const size_t base = (size_t)(col / cpw) * 64 + (size_t)(col % cpw) * 16;
-        for (int r = 0; r < 16; ++r) {
-            const double tr = vtr[ic * 16 + r], ti = vti[ic * 16 + r];
-            state[(size_t)2 * nw * 64 + base + r] = -2.0 / N * (re * tr + im * ti);
-            state[(size_t)3 * nw * 64 + base + r] = -2.0 / N * (-re * ti + im * tr);
-        }
-    }
-    res[(size_t)s * 4 + 0] = 1.0 - (re * re + im * im);
-    res[(size_t)s * 4 + 1] = leak_scale * lk;
-    res[(size_t)s * 4 + 2] = re;
-    res[(size_t)s * 4 + 3] = im;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Tangent-linear row-lane kernels (jq_rowlane_tl_kernels.h; jq_eval_f_g_grad_hvp): initial state and terminal condition of every direction
-// state files <- (Uinit, 0 ...) for every direction.  a.cimg: uinit [N][16]; a.nslabs: waves; a.nsamples N columns in use.
-// grid = (waves, directions)
-__global__ __launch_bounds__(64) void k_init_rowlane_tl(PropArgs a)
-{
-    const int lane = threadIdx.x;
-    const long long w = blockIdx.x, nw = a.nslabs;
-    const long long col = 4 * w + (lane >> 4);
-    double* st = a.state + (size_t)blockIdx.y * (size_t)a.state_stride + w * 64 + lane;
-    const bool used = col < (long long)a.nsamples * a.N;
-    for (int r = 0; r < JQ_ROWLANE_TL_ROWS; ++r) st[(size_t)r * nw * 64] = (r == 0 && used) ? a.cimg[(col % a.N) * 16 + (lane & 15)] : 0.0;
-}
-
-// Fidelity, leak, lambda(T) and its tangent per (sample, direction): k_terminal_rowlane (mode 1) and its derivative.
-//   s = tr(Vtg' V) / N, sd = tr(Vtg' Vd) / N ; lambda(T) = s conj(Vtg) / N, its tangent sd conj(Vtg) / N
-// a.cimg: vtr [N][16], a.tabs: vti [N][16], a.h: leak scale, a.nslabs: waves, a.traces: res [direction][sample][4] = { primary,
-// secondary, Re s, Im s }.  Thread per sample -- its columns are read wherever their waves are; grid = (ceil(samples / 64), directions)
-__global__ __launch_bounds__(64) void k_terminal_rowlane_tl(PropArgs a)
-{
-    const int s = blockIdx.x * 64 + threadIdx.x;
-    if (s >= a.nsamples) return;
-    const size_t arr = (size_t)a.nslabs * 64;
-    const int N = a.N;
-    double* state = a.state + (size_t)blockIdx.y * (size_t)a.state_stride;
-    const double *vtr = a.cimg, *vti = a.tabs;
-    double re = 0.0, im = 0.0, dre = 0.0, dim = 0.0, lk = 0.0;
-    for (int ic = 0; ic < N; ++ic) {
-        const long long col = (long long)s * N + ic;
-        const size_t base = (size_t)(col / 4) * 64 + (size_t)(col % 4) * 16;
-        for (int r = 0; r < 16; ++r) {
-            const double u = state[base + r], v = state[arr + base + r];
-            const double ud = state[4 * arr + base + r], vd = state[5 * arr + base + r];
-            const double tr = vtr[ic * 16 + r], ti = vti[ic * 16 + r];
-            re += jq_det2(u, tr, v, ti);
-            im += jq_dot2(u, ti, v, tr);
-            dre += jq_det2(ud, tr, vd, ti);
-            dim += jq_dot2(ud, ti, vd, tr);
-            lk += state[(size_t)(JQ_ROWLANE_TL_ROWS - 1) * arr + base + r];
-        }
-    }
-    re /= N, im /= N, dre /= N, dim /= N;
-    for (int ic = 0; ic < N; ++ic) {
-        const long long col = (long long)s * N + ic;
-        const size_t base = (size_t)(col / 4) * 64 + (size_t)(col % 4) * 16;
-        for (int r = 0; r < 16; ++r) {
-            const double tr = vtr[ic * 16 + r], ti = vti[ic * 16 + r];
-            state[2 * arr + base + r] = jq_dot2(im, ti, re, tr) / N;         // lambda_r
-            state[3 * arr + base + r] = -(jq_det2(im, tr, re, ti) / N);      // nb = -lambda_i
-            state[6 * arr + base + r] = jq_dot2(dim, ti, dre, tr) / N;
-            state[7 * arr + base + r] = -(jq_det2(dim, tr, dre, ti) / N);
-        }
-    }
-    double* res = a.traces + ((size_t)blockIdx.y * a.nsamples + s) * 4;
     res[0] = 1.0 - jq_dot2(re, re, im, im);
-    res[1] = a.h * lk;
-    res[2] = re;
-    res[3] = im;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Tangent-linear quad-layout kernels (jq_quad_tl_kernels.h; jq_eval_f_g_grad_hvp at Ntot > 16): initial state and terminal condition of
-// every direction.  New kernels: the state file is [row][quad][lane 16 i + 4 b + j <-> row 16 mt + 4 b + i, column j], not the
-// [row][wave][16 column + row] of the row-lane twins; the handle's slab images are read where they are (element (R, c) of an Ntot x N array:
-// ((c / 16) KT + R / 4) 64 + 16 (R % 4) + c % 16).
-// state files <- (Uinit, 0 ...) for every direction.  a.cimg: the slab image of Uinit; a.nslabs: quads; a.nsamples N columns in use.
-// grid = (quads, directions)
-__global__ __launch_bounds__(64) void k_init_quad_tl(PropArgs a)
-{
-    const int lane = threadIdx.x, NT = (a.Ntot + 15) / 16;
-    const long long w = blockIdx.x, nw = a.nslabs;
-    const long long col = 4 * w + (lane & 3);
-    const int rowb = 4 * ((lane >> 2) & 3) + (lane >> 4);
-    double* st = a.state + (size_t)blockIdx.y * (size_t)a.state_stride + w * 64 + lane;
-    const bool used = col < (long long)a.nsamples * a.N;
-    const int c = (int)(col % a.N);
-    for (int r = 0; r < JQ_QUAD_TL_ROWS(NT); ++r) {
-        const int R = 16 * r + rowb;
-        st[(size_t)r * nw * 64] = (r < NT && used) ? a.cimg[((size_t)(c / 16) * 4 * NT + R / 4) * 64 + 16 * (R % 4) + c % 16] : 0.0;
-    }
-}
-
-// Fidelity, leak, lambda(T) and its tangent per (sample, direction): k_terminal_rowlane_tl on the quad-layout state file.
-// a.cimg / a.tabs: the slab images of the target (real / imaginary part), a.h: leak scale, a.nslabs: quads, a.traces: res [direction][sample][4].
-// Thread per sample -- its columns are read wherever their quads are; grid = (ceil(samples / 64), directions)
-__global__ __launch_bounds__(64) void k_terminal_quad_tl(PropArgs a)
-{
-    const int s = blockIdx.x * 64 + threadIdx.x;
-    if (s >= a.nsamples) return;
-    const int N = a.N, NT = (a.Ntot + 15) / 16;
-    const size_t rs = (size_t)a.nslabs * 64, arr = (size_t)NT * rs;
-    double* state = a.state + (size_t)blockIdx.y * (size_t)a.state_stride;
-    const double *vtr = a.cimg, *vti = a.tabs;
-    auto at = [&](long long col, int R) { return (size_t)(R / 16) * rs + (size_t)(col / 4) * 64 + 16 * (R % 4) + 4 * ((R % 16) / 4) + (size_t)(col % 4); };
-    auto tg = [&](int ic, int R) { return ((size_t)(ic / 16) * 4 * NT + R / 4) * 64 + 16 * (R % 4) + ic % 16; };
-    double re = 0.0, im = 0.0, dre = 0.0, dim = 0.0, lk = 0.0;
-    for (int ic = 0; ic < N; ++ic) {
-        const long long col = (long long)s * N + ic;
-        for (int R = 0; R < a.Ntot; ++R) {
-            const size_t e = at(col, R);
-            const double u = state[e], v = state[arr + e], ud = state[4 * arr + e], vd = state[5 * arr + e];
-            const double tr = vtr[tg(ic, R)], ti = vti[tg(ic, R)];
-            re += jq_det2(u, tr, v, ti);
-            im += jq_dot2(u, ti, v, tr);
-            dre += jq_det2(ud, tr, vd, ti);
-            dim += jq_dot2(ud, ti, vd, tr);
-        }
-        for (int r = 0; r < 16; ++r) lk += state[(size_t)(JQ_QUAD_TL_ROWS(NT) - 1) * rs + at(col, r)];
-    }
-    re /= N, im /= N, dre /= N, dim /= N;
-    for (int ic = 0; ic < N; ++ic) {
-        const long long col = (long long)s * N + ic;
-        for (int R = 0; R < a.Ntot; ++R) {
-            const size_t e = at(col, R);
-            const double tr = vtr[tg(ic, R)], ti = vti[tg(ic, R)];
-            state[2 * arr + e] = jq_dot2(im, ti, re, tr) / N;         // lambda_r
-            state[3 * arr + e] = -(jq_det2(im, tr, re, ti) / N);      // nb = -lambda_i
-            state[6 * arr + e] = jq_dot2(dim, ti, dre, tr) / N;
-            state[7 * arr + e] = -(jq_det2(dim, tr, dre, ti) / N);
-        }
-    }
-    double* res = a.traces + ((size_t)blockIdx.y * a.nsamples + s) * 4;
-    res[0] = 1.0 - jq_dot2(re, re, im, im);
-    res[1] = a.h * lk;
+    res[1] = leak_scale * lk;
     res[2] = re;
     res[3] = im;
 }

@@ -22,7 +22,7 @@ static const char* dump_spelling(const void* fn)
 {
 #define JQ_DUMP_ROW(name, ...) {#name "<" #__VA_ARGS__ ">", (const void*)name<__VA_ARGS__>},
     static const struct { const char* spelling; const void* fn; } other[] = {
-        JQ_SIZES_LANE(JQ_INST_L_INIT, JQ_DUMP_ROW) JQ_SIZES_LANE(JQ_INST_L_TERM, JQ_DUMP_ROW) JQ_INST_HOST(JQ_DUMP_ROW)
+        JQ_INST_HOST(JQ_DUMP_ROW)
         {"k_forward_huge", (const void*)k_forward_huge}, {"k_backward_huge", (const void*)k_backward_huge}};
 #undef JQ_DUMP_ROW
     for (const KernelInst& r : g_inst)
@@ -47,13 +47,12 @@ static void dump_line(const std::string& first, const char* names, const std::st
     if (!same_fn && !first.empty()) printf("# %s: %s\n", first.substr(0, first.find(' ')).c_str(), names);
     run_first = first, run_outcome = outcome, run = first.empty() ? 0 : 1;
 }
-static void dump(const char* inputs, const char* names, int rc, const KernelSel& s, const void* fwd, const void* bwd, const void* init = nullptr, const void* term = nullptr)
+static void dump(const char* inputs, const char* names, int rc, const KernelSel& s, const void* fwd, const void* bwd)
 {
     std::string o = "rc=" + std::to_string(rc);
     if (rc == 0) {
         if (fwd) o += std::string(" fwd=") + s.fwd + " " + dump_spelling(fwd);
         o += std::string(" bwd=") + s.bwd + " " + dump_spelling(bwd);
-        if (init) o += std::string(" init=") + dump_spelling(init) + " term=" + dump_spelling(term);
         const std::pair<const char*, int> ints[] = {{"spw", s.spw}, {"qs_qw", s.qs_qw}, {"bwd_wgs", s.bwd_wgs}};
         for (const auto& f : ints)
             if (f.second) o += std::string(" ") + f.first + "=" + std::to_string(f.second);
@@ -182,12 +181,10 @@ int main(int argc, char** argv)
             dump(in, "huge NT BWc", rc, s, (const void*)f, (const void*)b);
         }
     for (const DumpSize& z : lane) {
-        lane_init_t li = nullptr;
-        lane_term_t lt = nullptr;
         h.lane_np = z.a, s = KernelSel();
-        const int rc = JQ_SELECT(s, select_lane_kernels, &f, &b, &li, &lt);
+        const int rc = JQ_SELECT(s, select_lane_kernels, &f, &b);
         snprintf(in, sizeof in, "select_lane_kernels %d", z.a);
-        dump(in, "lane_np", rc, s, (const void*)f, (const void*)b, (const void*)li, (const void*)lt);
+        dump(in, "lane_np", rc, s, (const void*)f, (const void*)b);
     }
     for (const DumpSize& z : rowlane)
         for (int wrank = 0; wrank <= 1; ++wrank)

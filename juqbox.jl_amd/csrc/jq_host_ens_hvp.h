@@ -70,8 +70,7 @@ static EnsHvpLayout ens_hvp_layout_quad(const jq_handle* h)
             4, JQ_QUAD_TL_ROWS(h->NT), true, 16 * h->NT, rings, rings + (size_t)2 * h->Nc * h->mat_elems * sizeof(double), JQ_QUAD_TL_WAVES, true};
 }
 
-static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& lay, prop_kernel_t kinit, prop_kernel_t kfwd, prop_kernel_t kterm, prop_kernel_t kbwd,
-                        const KernelSel& sel)
+static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& lay, prop_kernel_t kfwd, prop_kernel_t kbwd, const KernelSel& sel)
 {
     const char* who = "jq_eval_f_g_grad_hvp";
     HIPCHK(h, hipSetDevice(h->device));
@@ -119,9 +118,6 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
     a.colinfo = d_col.p; a.tabs = d_tabs.p; a.traces = d_tr.p; a.cimg = lay.cimg; a.stride = (long long)stride; a.m = h->m; a.nslabs = lay.slabs_are_waves ? nwaves : (int)ncols;
     a.Ncoupled = Nc; a.Ntot = h->Ntot; a.N = h->N; a.parts = 1; a.nsamples = nquad; a.sps = 1; a.tinv = 1.0 / h->T; a.use_shift = use_shift ? 1 : 0;
     for (int q = 0; q < JQ_MAXNC && lay.modes; ++q) a.bw_trace[q] = q < Nc ? h->bw_trace[q] : 0;
-    PropArgs ai = a, at = a;      // the init and terminal kernels read their images and scalars through the fields their headers name
-    ai.cimg = lay.uinit;
-    at.cimg = lay.vtr; at.tabs = lay.vti; at.traces = d_res.p; at.h = 0.5 * dt * (1.0 / h->T);
     if (lay.lds_fwd) HIPCHK(h, hipFuncSetAttribute((const void*)kfwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.lds_fwd));
     if (lay.lds_bwd) HIPCHK(h, hipFuncSetAttribute((const void*)kbwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.lds_bwd));
 
@@ -133,12 +129,34 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
     // the sweep kernels: wpg consecutive waves of a direction per workgroup (1 on the lane and row-lane routes: the launch it always was)
     const int wpg = std::min(lay.wpg, nwaves);
     const dim3 sgrid((unsigned)((nwaves + wpg - 1) / wpg), (unsigned)dpl), sblock((unsigned)(64 * wpg));
+    // The two launches that bracket a forward sweep, the one place where the driver tells the routes apart.  init: the state files <- (Uinit, 0 ...);
+    // else fidelity, leak, lambda(T) and its tangent per (node, direction).  The leak partials are in the last row of a file; lay.size is NP / NT.
+    const auto endpoint = [&](bool init) {
+        const auto terminal = [&](auto map) {
+            terminal_cols<EP_TL>(s, map, dpl, d_state.p, sstride, lay.vtr, lay.vti, nullptr, nullptr, 1, h->N, nquad, 0.5 * dt * (1.0 / h->T), d_res.p);
+        };
+        const long long nw = nwaves, ss = (long long)sstride;
+        const int last = lay.state_rows - 1;
+        switch (lay.route) {
+        case 1:
+            if (init) hipLaunchKernelGGL(k_init_lane, grid, dim3(64), 0, s, d_state.p, ncols, lay.size, lay.state_rows, ss, lay.uinit, h->N, ncols_used);
+            else terminal(LaneMap{lay.size, ncols, last});
+            break;
+        case 3:
+            if (init) hipLaunchKernelGGL(k_init_rowlane, grid, dim3(64), 0, s, d_state.p, nw, lay.state_rows, ss, lay.uinit, h->N, ncols_used, lay.cpw, 1);
+            else terminal(RowlaneMap{nw, lay.cpw, 1, last});
+            break;
+        default:
+            if (init) hipLaunchKernelGGL(k_init_quad_tl, grid, dim3(64), 0, s, d_state.p, nw, ss, lay.uinit, lay.size, h->N, ncols_used);
+            else terminal(QuadMap{h->Ntot, lay.size, nw, last, (size_t)lay.size * nwaves * 64});
+        }
+    };
     for (int r = 0; r < rounds; ++r) {
         const int j0 = r * dpl, nd = std::min(dpl, ndir - j0);
         if ((rc = tl_upload_round(h, blk, d_pc.p, x.pcof, x.dirs, j0, nd, dpl, ncoeff))) return rc;
         HIPCHK(h, hipMemsetAsync(d_g.p, 0, (size_t)2 * nvec * ncoeff * sizeof(double), s));
         // ---- forward sweep of (state, tangent) ----
-        hipLaunchKernelGGL(kinit, grid, dim3(64), 0, s, ai);
+        endpoint(true);
         a.h = dt; a.forced = 1;
         for (int n0 = 0; n0 < h->nsteps; n0 += cs) {
             const int nc = std::min(cs, h->nsteps - n0);
@@ -148,7 +166,7 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
             hipLaunchKernelGGL(kfwd, sgrid, sblock, lay.lds_fwd, s, a);
             if ((rc = tm.end())) return rc;
         }
-        hipLaunchKernelGGL(kterm, dim3((unsigned)((nquad + 63) / 64), (unsigned)dpl), dim3(64), 0, s, at);
+        endpoint(false);
         HIPCHK(h, hipGetLastError());
         if (r == 0) HIPCHK(h, hipMemcpyAsync(res.data(), d_res.p, (size_t)nquad * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
         // ---- backward sweeps: forced, then (objFuncType != 1) unforced from the saved terminal state ----
@@ -250,11 +268,9 @@ extern "C" int jq_eval_f_g_grad_hvp(jq_handle* h, const double* pcof, int32_t nc
         // bounds of the lane GRADIENT kernels (options lane_min / lane_max): one node is served here too
         if (h->lane_np > 0 && h->Nc <= JQ_MAXNC) {
             KernelSel sel = sel_start();
-            char unused[JQ_SEL_TAG];
             const int np = h->lane_np;
             const prop_kernel_t kfwd = pick(sel.fwd, np, -1, "k_forward_lane_tl", {np}), kbwd = pick(sel.bwd, np, -1, "k_backward_lane_tl", {np});
-            const prop_kernel_t kinit = pick(unused, np, -1, "k_init_lane_tl", {np}), kterm = pick(unused, np, -1, "k_terminal_lane_tl", {np});
-            if (kfwd && kbwd && kinit && kterm) return ens_hvp_lane(h, x, ens_hvp_layout_lane(h), kinit, kfwd, kterm, kbwd, sel);
+            if (kfwd && kbwd) return ens_hvp_lane(h, x, ens_hvp_layout_lane(h), kfwd, kbwd, sel);
         }
         // row-lane route: Ntot 9 .. 16 (rl_npj is 0 under option lane=0 and on embedded twins; NPJ <= 8 has no tangent kernels: Ntot <= 6 went
         // the lane route above, Ntot 7 and 8 stay sequential)
@@ -262,7 +278,7 @@ extern "C" int jq_eval_f_g_grad_hvp(jq_handle* h, const double* pcof, int32_t nc
             KernelSel sel = sel_start();
             const int np = h->rl_npj;
             const prop_kernel_t kfwd = pick(sel.fwd, np, -1, "k_forward_rowlane_tl", {np}), kbwd = pick(sel.bwd, np, -1, "k_backward_rowlane_tl", {np});
-            if (kfwd && kbwd) return ens_hvp_lane(h, x, ens_hvp_layout_rowlane(h), k_init_rowlane_tl, kfwd, k_terminal_rowlane_tl, kbwd, sel);
+            if (kfwd && kbwd) return ens_hvp_lane(h, x, ens_hvp_layout_rowlane(h), kfwd, kbwd, sel);
         }
         // quad route: Ntot > 16 with the 4 x 4 x n structure of the handle's own plan (never an embedded twin) and its quad-layout kernels enabled
         // (option quad=0 switches the route off); NT = 7, 8 have no tangent kernels (their backward kernels need scratch) and stay sequential
@@ -270,7 +286,7 @@ extern "C" int jq_eval_f_g_grad_hvp(jq_handle* h, const double* pcof, int32_t nc
             KernelSel sel = sel_start();
             const int nt = h->NT;
             const prop_kernel_t kfwd = pick(sel.fwd, nt, JQ_BW_T4Q, "k_forward_quad_tl", {nt}), kbwd = pick(sel.bwd, nt, JQ_BW_T4Q, "k_backward_quad_tl", {nt});
-            if (kfwd && kbwd) return ens_hvp_lane(h, x, ens_hvp_layout_quad(h), k_init_quad_tl, kfwd, k_terminal_quad_tl, kbwd, sel);
+            if (kfwd && kbwd) return ens_hvp_lane(h, x, ens_hvp_layout_quad(h), kfwd, kbwd, sel);
         }
         return ens_hvp_sequential(h, x);
     });

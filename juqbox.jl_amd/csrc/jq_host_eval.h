@@ -142,6 +142,15 @@ static void pack_backward_schedule(PropArgs& a, const int (*rows)[8], int ng)
         sched_pack(&a.pro_bits, q, 2, q);
     }
 }
+// k_terminal_cols (jq_aux_kernels.h) on `files` state files, dstride doubles apart: a thread per sample and file
+template <int FLAVOR, class Map>
+static void terminal_cols(hipStream_t s, Map m, int files, double* state, size_t dstride, const double* vtr, const double* vti, const double* dvr,
+                          const double* dvi, int mode, int N, int nsamples, double leak_scale, double* res)
+{
+    hipLaunchKernelGGL((k_terminal_cols<Map, FLAVOR>), dim3((unsigned)((nsamples + 63) / 64), (unsigned)files), dim3(64), 0, s, m, state,
+                       (long long)dstride, vtr, vti, dvr, dvi, mode, N, nsamples, leak_scale, res);
+}
+
 static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
 {
     const double *const pcof = rq.pcof, *const shift = rq.shift, *eps = rq.eps, *wgt = rq.wgt;      // (eps, wgt: a grouped batch expands them below)
@@ -394,10 +403,11 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     HIPCHK(h, hipEventRecord(h->ev[0], s));
 
     if (p.layout == SL_ROWLANE)
-        hipLaunchKernelGGL(k_init_state_rowlane, dim3((unsigned)p.nwaves_rl), dim3(64), 0, s, h->d_state, p.nwaves_rl, h->d_uinit_r, h->N,
-                           ncols_used, p.cpw, p.wpg);
+        hipLaunchKernelGGL(k_init_rowlane, dim3((unsigned)p.nwaves_rl), dim3(64), 0, s, h->d_state, p.nwaves_rl, JQ_ROWLANE_ROWS, 0LL, h->d_uinit_r,
+                           h->N, ncols_used, p.cpw, p.wpg);
     else if (p.layout == SL_LANE)
-        hipLaunchKernelGGL(p.klinit, dim3((unsigned)(p.ncols / 64)), dim3(64), 0, s, h->d_state, p.ncols, h->d_uinit_l, h->N, ncols_used);
+        hipLaunchKernelGGL(k_init_lane, dim3((unsigned)(p.ncols / 64)), dim3(64), 0, s, h->d_state, p.ncols, h->lane_np, JQ_LANE_ROWS(h->lane_np), 0LL,
+                           h->d_uinit_l, h->N, ncols_used);
     else
         hipLaunchKernelGGL(k_init_state, dim3(p.nslabs), dim3(64), 0, s, h->d_state, h->state_stride, h->d_uimg, h->KT, h->parts);
 
@@ -435,14 +445,14 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
         hipLaunchKernelGGL(k_terminal_imr, dim3(p.nslabs), dim3(64), 0, s, h->d_state, h->state_stride, h->d_vtr, h->d_vti, h->KT,
                            h->N, h->sps, nsamples, leak_scale, h->d_res);
     else if (p.term == TK_ROWLANE_IMR)
-        hipLaunchKernelGGL(k_terminal_rowlane_imr, dim3((nsamples + 63) / 64), dim3(64), 0, s, h->d_state, p.nwaves_rl, h->d_vtr_r,
-                           h->d_vti_r, h->N, nsamples, leak_scale, h->d_res, p.cpw);
+        terminal_cols<EP_IMR>(s, RowlaneMap{p.nwaves_rl, p.cpw, p.wpg, JQ_ROWLANE_ROWS - 1}, 1, h->d_state, 0, h->d_vtr_r, h->d_vti_r, nullptr, nullptr, 1,
+                              h->N, nsamples, leak_scale, h->d_res);
     else if (p.term == TK_ROWLANE)
-        hipLaunchKernelGGL(k_terminal_rowlane, dim3((nsamples + 63) / 64), dim3(64), 0, s, h->d_state, p.nwaves_rl, h->d_vtr_r,
-                           h->d_vti_r, h->N, nsamples, leak_scale, h->d_res, h->d_dvr_r, h->d_dvi_r, sv_mode, p.cpw, p.wpg);
+        terminal_cols<EP_SV>(s, RowlaneMap{p.nwaves_rl, p.cpw, p.wpg, JQ_ROWLANE_ROWS - 1}, 1, h->d_state, 0, h->d_vtr_r, h->d_vti_r, h->d_dvr_r, h->d_dvi_r,
+                             sv_mode, h->N, nsamples, leak_scale, h->d_res);
     else if (p.term == TK_LANE)
-        hipLaunchKernelGGL(p.klterm, dim3((nsamples + 63) / 64), dim3(64), 0, s, h->d_state, p.ncols, h->d_vtr_l, h->d_vti_l, h->N,
-                           nsamples, leak_scale, h->d_res, h->d_dvr_l, h->d_dvi_l, sv_mode);
+        terminal_cols<EP_SV>(s, LaneMap{h->lane_np, p.ncols, JQ_LANE_ROWS(h->lane_np) - 1}, 1, h->d_state, 0, h->d_vtr_l, h->d_vti_l, h->d_dvr_l, h->d_dvi_l,
+                             sv_mode, h->N, nsamples, leak_scale, h->d_res);
     else
         hipLaunchKernelGGL(k_terminal, dim3(p.nslabs), dim3(64), 0, s, h->d_state, h->state_stride, h->d_vtr, h->d_vti, h->KT,
                            h->N, h->sps, nsamples, leak_scale, h->d_res, h->d_dvr, h->d_dvi, sv_mode);

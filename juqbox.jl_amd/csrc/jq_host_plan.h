@@ -139,9 +139,7 @@ struct BatchPlan {
     // (4 / 2) -- 0: not taken; row-lane backward waves (1 .. 3); implicit-midpoint cooperative quad: 1 / 2 sets of waves, 3 workgroups
     int spw, cq_nr, qs_qw, rl_waves, imr_cq_bwd;
     bool fwd2, dense, parts, hbm, jac_wg, huge;
-    prop_kernel_t kfwd, kbwd;   // kernels (+ the lane kernels' own initial-state and terminal kernels)
-    lane_init_t klinit;
-    lane_term_t klterm;
+    prop_kernel_t kfwd, kbwd;   // kernels
     TermKernel term;
     // geometry (prop_nslabs: PropArgs::nslabs -- waves of the row-lane kernels, columns of the lane kernels; bwd_block_ng2: backward
     // sweeps of two or more controls)
@@ -345,7 +343,7 @@ static int plan_batch(jq_handle* h, int nsamples, bool adjoint, bool hist, GateH
     case KF_COOP_IMR: rc = p->parts ? select_coop_imr_parts_kernels(h, p->hbm, &p->kfwd, &p->kbwd, &p->sel) : select_coop_imr_kernels(h, p->hbm, &p->kfwd, &p->kbwd, &p->sel); break;
     case KF_ROWLANE_IMR: rc = select_rowlane_imr_kernels(h, rl_split, &p->kfwd, &p->kbwd, &p->sel); break;
     case KF_ROWLANE: rc = select_rowlane_kernels(h, p->rl_waves, hist, &p->kfwd, &p->kbwd, &p->sel); break;
-    case KF_LANE: rc = select_lane_kernels(h, &p->kfwd, &p->kbwd, &p->klinit, &p->klterm, &p->sel); break;
+    case KF_LANE: rc = select_lane_kernels(h, &p->kfwd, &p->kbwd, &p->sel); break;
     case KF_CQ: rc = select_cq_kernels(h, p->fwd2, p->cq_nr, wfull, cq_dn, &p->kfwd, &p->kbwd, &p->sel); break;
     case KF_COOP: rc = select_coop_kernels(h, &p->kfwd, &p->kbwd, &p->sel); break;
     case KF_QUAD: rc = wfull ? select_quad_w_kernels(h, &p->kfwd, &p->kbwd, &p->sel) : select_quad_kernels(h, p->spw, &p->kfwd, &p->kbwd, &p->sel); break;

@@ -2,8 +2,6 @@
 // the kernel instantiations (compiled in their own translation units, listed in jq_inst_list.h) and the functions that pick one.
 // ---------------------------------------------------------------------------------------------
 typedef void (*prop_kernel_t)(PropArgs);
-typedef void (*lane_init_t)(JQ_LANE_INIT_ARGS);
-typedef void (*lane_term_t)(JQ_LANE_TERM_ARGS);
 
 // templates whose definitions the host does not include (jq_cq_kernels.h, jq_cq_split_kernels.h, jq_quad_split_kernels.h, jq_quad_imr_kernels.h,
 // jq_cq_imr_kernels.h; jq_coop_imr_kernels.h; jq_quad_tl_kernels.h, whose kernels need the quad layout's row type)
@@ -26,12 +24,8 @@ template <int NT, int BW, bool HBM> __global__ void k_backward_coop_imr_parts(Pr
 
 // Every instantiation of the list is compiled in its own object: declared here, so that none is instantiated into this translation unit ...
 #define JQ_EXT(name, ...) extern template __global__ void name<__VA_ARGS__>(PropArgs);
-#define JQ_EXT_INIT(name, ...) extern template __global__ void name<__VA_ARGS__>(JQ_LANE_INIT_ARGS);
-#define JQ_EXT_TERM(name, ...) extern template __global__ void name<__VA_ARGS__>(JQ_LANE_TERM_ARGS);
 #define JQ_EXT_FAMILY(letter, SIZES, INST) SIZES(INST, JQ_EXT)
 JQ_OBJECT_FAMILIES(JQ_EXT_FAMILY)
-JQ_SIZES_LANE(JQ_INST_L_INIT, JQ_EXT_INIT)
-JQ_SIZES_LANE(JQ_INST_L_TERM, JQ_EXT_TERM)
 
 // ... and a row of g_inst: its spelling, its template, the values of its template arguments (those left out: false) and the kernel.  A
 // row without a kernel starts the rows of the objects with the letter it names.
@@ -184,20 +178,12 @@ static int select_coop_kernels(jq_handle* h, prop_kernel_t* fwd, prop_kernel_t* 
 }
 
 // lane kernels (one lane per column), NP = padded Hilbert dimension
-static int select_lane_kernels(jq_handle* h, prop_kernel_t* fwd, prop_kernel_t* bwd, lane_init_t* init, lane_term_t* term, KernelSel* s)
+static int select_lane_kernels(jq_handle* h, prop_kernel_t* fwd, prop_kernel_t* bwd, KernelSel* s)
 {
-#define JQ_ROW_NP(name, np) {np, name<np>},
-    static const struct { int np; lane_init_t fn; } inits[] = {JQ_SIZES_LANE(JQ_INST_L_INIT, JQ_ROW_NP)};
-    static const struct { int np; lane_term_t fn; } terms[] = {JQ_SIZES_LANE(JQ_INST_L_TERM, JQ_ROW_NP)};
-#undef JQ_ROW_NP
-    *s = sel_start(), *init = nullptr, *term = nullptr;
+    *s = sel_start();
     *fwd = pick(s->fwd, h->lane_np, -1, "k_forward_lane", {h->lane_np});
     *bwd = pick(s->bwd, h->lane_np, -1, "k_backward_lane", {h->lane_np});
-    for (const auto& r : inits)
-        if (r.np == h->lane_np) *init = r.fn;
-    for (const auto& r : terms)
-        if (r.np == h->lane_np) *term = r.fn;
-    return (*fwd && *bwd && *init && *term) ? JQ_OK : fail(h, JQ_EUNSUPPORTED, "no lane kernel for this Hilbert dimension");
+    return (*fwd && *bwd) ? JQ_OK : fail(h, JQ_EUNSUPPORTED, "no lane kernel for this Hilbert dimension");
 }
 
 // row-lane kernels (one lane per (row, column)), NPJ = padded row length.  split: waves of the backward sweep (1, 2, 3)

@@ -84,14 +84,10 @@
     X(k_backward_rowlane3, np) X(k_forward_rowlane, np, true, true) X(k_backward_rowlane, np, true)
 // ... and the tangent-linear twins of the one-wave kernels (jq_rowlane_tl_kernels.h; jq_eval_f_g_grad_hvp at Ntot 9 .. 16): waves x directions
 #define JQ_INST_R_TL(X, np) X(k_forward_rowlane_tl, np) X(k_backward_rowlane_tl, np)
-// l_: lane kernels (np = padded Hilbert dimension NP); their init / terminal kernels have signatures of their own
+// l_: lane kernels (np = padded Hilbert dimension NP)
 #define JQ_INST_L(X, np) X(k_forward_lane, np) X(k_backward_lane, np)
-#define JQ_INST_L_INIT(X, np) X(k_init_state_lane, np)
-#define JQ_INST_L_TERM(X, np) X(k_terminal_lane, np)
-// ... and their tangent-linear twins (jq_lane_tl_kernels.h; jq_eval_f_g_grad_hvp): columns x directions, every kernel on PropArgs
-#define JQ_INST_L_TL(X, np) X(k_init_lane_tl, np) X(k_forward_lane_tl, np) X(k_terminal_lane_tl, np) X(k_backward_lane_tl, np)
-#define JQ_LANE_INIT_ARGS double*, long long, const double*, int, long long
-#define JQ_LANE_TERM_ARGS double*, long long, const double*, const double*, int, int, double, double*, const double*, const double*, int
+// ... and their tangent-linear twins (jq_lane_tl_kernels.h; jq_eval_f_g_grad_hvp): columns x directions
+#define JQ_INST_L_TL(X, np) X(k_forward_lane_tl, np) X(k_backward_lane_tl, np)
 // c_: cooperative (row-split) kernels
 #define JQ_INST_C(X, nt, bw) X(k_forward_coop, nt, bw) X(k_backward_coop, nt, bw)
 

@@ -68,11 +68,7 @@ JQ_INST_R_TL(JQ_DEF, JQ_NT)
 #endif
 #elif JQ_VARIANT == 3
 #include "jq_lane_tl_kernels.h"
-#define JQ_DEF_INIT(name, ...) template __global__ void name<__VA_ARGS__>(JQ_LANE_INIT_ARGS);
-#define JQ_DEF_TERM(name, ...) template __global__ void name<__VA_ARGS__>(JQ_LANE_TERM_ARGS);
 JQ_INST_L(JQ_DEF, JQ_NT)
-JQ_INST_L_INIT(JQ_DEF_INIT, JQ_NT)
-JQ_INST_L_TERM(JQ_DEF_TERM, JQ_NT)
 #if JQ_NT <= 6                    // (JQ_SIZES_LANE_TL: NP = 8 spills; jq_eval_f_g_grad_hvp runs it on the sequential route)
 JQ_INST_L_TL(JQ_DEF, JQ_NT)
 #endif

@@ -370,76 +370,3 @@ __global__ __launch_bounds__(64) void k_backward_lane(PropArgs a)
     for (int q = 0; q < JQ_MAXNC; ++q)
         if (q < Nc) a.state[((size_t)JQ_LANE_ARRAYS * NP + q) * ncols + col] = carry[q];
 }
-
-// state file <- (Uinit, 0, 0, 0, 0...).  uinit: [N][NP] (column i of Uinit, zero padded).  thread per column
-template <int NP>
-__global__ void k_init_state_lane(double* state, long long ncols, const double* __restrict__ uinit, int N, long long ncols_used)
-{
-    const long long col = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (col >= ncols) return;
-    const int ic = (int)(col % N);
-    for (int r = 0; r < JQ_LANE_ROWS(NP); ++r) {
-        double val = 0.0;
-        if (r < NP && col < ncols_used) val = uinit[ic * NP + r];
-        state[(size_t)r * ncols + col] = val;
-    }
-}
-
-// fidelity, leak and adjoint terminal condition per sample (thread per sample; see k_terminal)
-// (mode, dvr, dvi: see k_terminal; the dVds image has the layout of vtr / vti)
-template <int NP>
-__global__ void k_terminal_lane(double* state, long long ncols, const double* __restrict__ vtr, const double* __restrict__ vti,
-                                int N, int nsamples, double leak_scale, double* res, const double* __restrict__ dvr,
-                                const double* __restrict__ dvi, int mode)
-{
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= nsamples) return;
-    double re = 0.0, im = 0.0, lk = 0.0;
-    for (int ic = 0; ic < N; ++ic) {
-        const long long col = (long long)s * N + ic;
-        for (int r = 0; r < NP; ++r) {
-            const double u = state[(size_t)r * ncols + col], v = state[((size_t)NP + r) * ncols + col];
-            const double tr = vtr[ic * NP + r], ti = vti[ic * NP + r];
-            re += jq_det2(u, tr, v, ti);
-            im += jq_dot2(u, ti, v, tr);
-        }
-        lk += state[((size_t)JQ_LANE_ARRAYS * NP + JQ_MAXNC) * ncols + col];
-    }
-    re /= N;
-    im /= N;
-    double dre = 0.0, dim = 0.0;
-    if (mode >= 3) {      // s_D: the same sums against the dVds image
-        for (int ic = 0; ic < N; ++ic) {
-            const long long col = (long long)s * N + ic;
-            for (int r = 0; r < NP; ++r) {
-                const double u = state[(size_t)r * ncols + col], v = state[((size_t)NP + r) * ncols + col];
-                const double tr = dvr[ic * NP + r], ti = dvi[ic * NP + r];
-                dre += jq_det2(u, tr, v, ti);
-                dim += jq_dot2(u, ti, v, tr);
-            }
-        }
-        dre /= N;
-        dim /= N;
-    }
-    const double are = (mode == 3) ? dre : re, aim = (mode == 3) ? dim : im;
-    const bool from_d = (mode == 2 || mode == 4);
-    const double *xr = from_d ? dvr : vtr, *xi = from_d ? dvi : vti;
-    for (int ic = 0; ic < N; ++ic) {
-        const long long col = (long long)s * N + ic;
-        for (int r = 0; r < NP; ++r) {
-            const double tr = xr[ic * NP + r], ti = xi[ic * NP + r];
-            double lr = jq_dot2(aim, ti, are, tr) / N, nb = -(jq_det2(aim, tr, are, ti) / N);
-            if (mode == 4) {
-                const double yr = vtr[ic * NP + r], yi = vti[ic * NP + r];
-                lr += jq_dot2(dim, yi, dre, yr) / N;
-                nb += -(jq_det2(dim, yr, dre, yi) / N);
-            }
-            state[((size_t)2 * NP + r) * ncols + col] = lr;      // lambda_r
-            state[((size_t)3 * NP + r) * ncols + col] = nb;      // nb = -lambda_i
-        }
-    }
-    res[(size_t)s * 4 + 0] = 1.0 - jq_dot2(re, re, im, im);
-    res[(size_t)s * 4 + 1] = leak_scale * lk;
-    res[(size_t)s * 4 + 2] = re;
-    res[(size_t)s * 4 + 3] = im;
-}

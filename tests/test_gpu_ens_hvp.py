@@ -1,5 +1,5 @@
 """GPU (-m gpu): jq_eval_f_g_grad_hvp -- Hessian-vector products of a risk-neutral ensemble on the tangent-linear lane kernels
-(k_forward_lane_tl, k_terminal_lane_tl, k_backward_lane_tl; Ntot <= 6) and on the sequential route (everything else), against the CPU
+(k_forward_lane_tl, k_terminal_cols<LaneMap, EP_TL>, k_backward_lane_tl; Ntot <= 6) and on the sequential route (everything else), against the CPU
 reference of tests/ensemble_hessian_reference.py: sum_i w_i HessianReference(p_i).hvp(pcof, d) over the nodes' problems.
 
 Random dense problems from the generator of the block-band tests at one tile row, 7 time steps, where a lane kernel can go wrong: every

@@ -1,5 +1,5 @@
 """GPU (-m gpu): jq_eval_f_g_grad_hvp on the quad route -- Hessian-vector products of a risk-neutral ensemble at Ntot > 16 with the
-4 x 4 x n structure on the tangent-linear quad-layout kernels (k_init_quad_tl, k_forward_quad_tl, k_terminal_quad_tl,
+4 x 4 x n structure on the tangent-linear quad-layout kernels (k_init_quad_tl, k_forward_quad_tl, k_terminal_cols<QuadMap, EP_TL>,
 k_backward_quad_tl; objects t_<NT>_7), against the CPU reference of tests/ensemble_hessian_reference.py.
 
 Random 4 x 4 x n problems from tests/subsystem_problem.py (control q on subsystem q only: every T4 mode of the trace products), 7 time

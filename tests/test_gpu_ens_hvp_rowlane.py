@@ -1,5 +1,5 @@
 """GPU (-m gpu): jq_eval_f_g_grad_hvp on the row-lane route -- Hessian-vector products of a risk-neutral ensemble at Ntot 9 .. 16 on the
-tangent-linear row-lane kernels (k_init_rowlane_tl, k_forward_rowlane_tl, k_terminal_rowlane_tl, k_backward_rowlane_tl; NPJ 12 / 16),
+tangent-linear row-lane kernels (k_init_rowlane, k_forward_rowlane_tl, k_terminal_cols<RowlaneMap, EP_TL>, k_backward_rowlane_tl; NPJ 12 / 16),
 against the CPU reference of tests/ensemble_hessian_reference.py.
 
 Random dense problems from the generator of the block-band tests at one tile row, 7 time steps, where a row-lane kernel can go wrong:

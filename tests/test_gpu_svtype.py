@@ -110,7 +110,7 @@ def _inputs(case):
 
 
 @pytest.mark.parametrize("case,option_sets", [
-    ("swap02", [({}, 3)]),                                                      # row-lane: k_terminal_rowlane
+    ("swap02", [({}, 3)]),                                                      # row-lane: k_terminal_cols<RowlaneMap, EP_SV>
     # two sweeps (objFuncType 3); lane=0: the 16-level twin problem on the MFMA kernels (k_terminal)
     ("cnot2-leakieq", [({}, 3), ({"lane": 0}, MFMA)]),
     # the embedded twin (4 x 4 x 1) for every batch, and no twin at all on the MFMA kernels
@@ -136,8 +136,8 @@ def test_reference_cases_on_every_terminal_kernel(jq, case, option_sets):
 # Ntot, N, Nc, Nfreq, nsteps, m, objFuncType, structure; options; family; full leakage weights
 RANDOM = [
     ((40, 20, 2, 1, 7, 3, 3, False), {}, MFMA, False),                      # N > 16: k_terminal_parts (two slabs per sample)
-    ((8, 3, 2, 2, 9, 2, 2, False), {"rowlane_max": 0}, 2, False),            # lane kernels: k_terminal_lane<8>
-    ((6, 2, 1, 1, 11, 3, 1, False), {"rowlane_max": 0}, 2, False),           # ... k_terminal_lane<6>, one gradient
+    ((8, 3, 2, 2, 9, 2, 2, False), {"rowlane_max": 0}, 2, False),            # lane kernels: k_terminal_cols<LaneMap, EP_SV> at NP = 8
+    ((6, 2, 1, 1, 11, 3, 1, False), {"rowlane_max": 0}, 2, False),           # ... at NP = 6, one gradient
     ((48, 4, 2, 1, 6, 3, 3, "t4"), {}, 6, True),                             # full leakage weights (jq_update_wmat; complex: quad layout)
     ((12, 4, 2, 1, 8, 2, 1, False), {}, 3, True),                            # ... on the row-lane kernels
 ]
