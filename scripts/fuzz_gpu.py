@@ -8,16 +8,22 @@ compared with the same run of ANOTHER BUILD of the library (JQ_LIB; scripts/cmp_
 the oracle-based run had found an object that hipcc miscompiles in one register form;
 FUZZ_FOCUS=slab: every draw forced onto the slab kernels (family 0: no cooperative, quad-layout, lane or row-lane kernels) -- the
 objects k_*, j_*, w_* of every size and band, which small ensembles otherwise rarely reach; FUZZ_FOCUS=wfull: full weights in every
-Stormer-Verlet draw)"""
+Stormer-Verlet draw;
+FUZZ_UNCOUPLED=<share>: the share of the Stormer-Verlet draws that are converted to UNCOUPLED controls (tests/uncoupled_problem.py
+to_uncoupled: Hunc_ops[q] = Hsym_ops[q] or Hanti_ops[q] -- all symmetric, all antisymmetric or mixed, a third each -- and Rfreq with
+0.2 <= |Rfreq| <= 2); default 0.15.  The conversion draws from a generator of its own, seeded by (seed, draw), so the other 85 % of a
+seed's draws -- and everything else about the converted ones -- are what they were before uncoupled draws existed)"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, "."); sys.path.insert(0, "tests")
 import juqbox_jl_amd as jq
 from oracle.oracle import Oracle
 from test_gpu_random import random_problem
+from uncoupled_problem import to_uncoupled
 
 
 RTOL, ATOL = 1e-10, 1e-14      # the reference's tolerances (test/evalGrad.jl:4-5): the ONLY ones this script and tests/test_gpu_fuzz.py use
+UNCOUPLED_SHARE = 0.15         # of the Stormer-Verlet draws (implicit midpoint: the gradient with uncoupled controls is refused); FUZZ_UNCOUPLED overrides
 IMR_TOL = 1e-12                # fixed-point solver of the implicit-midpoint draws: the reference's own test setting (test/runtests.jl:69-70)
 
 
@@ -120,6 +126,11 @@ def run(n_cases=50, seed=1, verbose=True):
             k, v = mode.split("=")
             env[k] = v
         p, pcof = random_problem(jq, rng, Ntot, N, Nc, Nfreq, nsteps, m, oft, structure)
+        unc_rng = np.random.default_rng([seed, case, 0x756E63])      # (its own stream: the main one draws what it always drew)
+        kinds = None
+        if not imr and unc_rng.random() < float(os.environ.get("FUZZ_UNCOUPLED", UNCOUPLED_SHARE)):
+            kinds = ("s" * Nc, "a" * Nc, "".join(unc_rng.choice(["s", "a"], Nc)))[int(unc_rng.integers(0, 3))]
+            p = to_uncoupled(jq, p, kinds, unc_rng)
         jac = (not imr) and N <= 16 and rng.random() < 0.15      # (round 3: the Jacobi solver with a loose tolerance -- per-sample convergence;
         #                                                             N > 16 converges per 16-column part: O(tol), tests/test_gpu_round4.py)
         if focus_w:
@@ -152,8 +163,8 @@ def run(n_cases=50, seed=1, verbose=True):
         replan = rng.random() < 0.1                  # (round 3: a drift outside the planned structure before the evaluation)
         only = os.environ.get("FUZZ_ONLY")           # replay ONE case of a run (same n_cases and seed): the others only draw
         if only and os.environ.get("FUZZ_DRY") and case in [int(x) for x in only.split(",")]:
-            print("%d Ntot=%d N=%d Nc=%d Nf=%d steps=%d m=%d oft=%d %s imr=%s mode=%s env=%s replan=%s" % (
-                case, Ntot, N, Nc, Nfreq, nsteps, m, oft, structure, imr, mode, env, replan), flush=True)
+            print("%d Ntot=%d N=%d Nc=%d Nf=%d steps=%d m=%d oft=%d %s imr=%s mode=%s env=%s replan=%s uncoupled=%s" % (
+                case, Ntot, N, Nc, Nfreq, nsteps, m, oft, structure, imr, mode, env, replan, kinds), flush=True)
         if only and (os.environ.get("FUZZ_DRY") or case not in [int(x) for x in only.split(",")]):
             if replan:
                 rng.standard_normal((Ntot, Ntot))
@@ -249,9 +260,9 @@ def run(n_cases=50, seed=1, verbose=True):
         compared += 1
         flag = (("   (fixed-point iteration not converged: loose bound %.0e)" % loose) if err < loose else "   <<<<<< MISMATCH (unconverged draw, above its loose bound)") \
             if unconv else ("" if err < RTOL else "   <<<<<< MISMATCH")
-        nonlocal_print("%3d Ntot=%2d N=%2d Nc=%d Nf=%d steps=%2d m=%d oft=%d %-5s %s nq=%2d fam=%d %-18s env=%s%s%s err=%.1e%s" % (
+        nonlocal_print("%3d Ntot=%2d N=%2d Nc=%d Nf=%d steps=%2d m=%d oft=%d %-5s %s nq=%2d fam=%d %-18s env=%s%s%s%s err=%.1e%s" % (
             case, Ntot, N, Nc, Nfreq, nsteps, m, oft, structure, "IMR" if imr else ("JAC" if jac else ("SVW" if wfull else "SV ")), nq, fam, mode,
-            env.get("JQ_CHUNK_STEPS", "-"), " replan" if replan else "", (" tol=%.0e" % jtol) if jac else "", err, flag), flush=True)
+            env.get("JQ_CHUNK_STEPS", "-"), " replan" if replan else "", (" tol=%.0e" % jtol) if jac else "", (" Hunc=" + kinds) if kinds else "", err, flag), flush=True)
         wa.close()
     nonlocal_print("worst relative error %.2e over %d compared cases (of %d drawn; %d implicit-midpoint draws with an unconverged fixed-point "
                    "iteration held to their loose bound only) in %.0f s" % (worst, compared, n_cases, n_unconv, time.time() - t0))
