@@ -49,7 +49,8 @@ extern "C" {
  *     controls -- amplitude miscalibration, crosstalk -- or in both), jq_traceobj_jvp (the tangent of the discrete forward map along
  *     directions of coefficient space: the reference's verbose && evaladjoint forward-sensitivity sweep), jq_traceobjgrad_hvp (the
  *     derivative of the gradient along directions of coefficient space: Hessian-vector products), jq_eval_f_g_grad_hvp (the same for
- *     the two gradients of a risk-neutral ensemble: the nodes in the lanes, the directions in the grid). */
+ *     the two gradients of a risk-neutral ensemble: the nodes in the lanes, the directions in the grid), jq_eval_f_g_grad_drifts_hvp (the
+ *     same for an ensemble of arbitrary drift Hamiltonians: every wave reads the operator stream of its own member). */
 #define JQ_ABI_VERSION 6
 
 #define JQ_MAX_CONTROLS 16 /* control Hamiltonians the fast kernels hold in registers; more: cooperative kernels (no limit)    */
@@ -434,6 +435,31 @@ int jq_traceobjgrad_hvp(jq_handle *h, const double *pcof, int32_t ncoeff, const 
 int jq_eval_f_g_grad_hvp(jq_handle *h, const double *pcof, int32_t ncoeff, const double *dirs, int32_t ndir, const double *nodes,
                          const double *weights, int32_t nquad, const double *shift, double *out2, double *infid_grad, double *leak_grad,
                          double *hv_infid, double *hv_leak);
+
+/*
+ * jq_eval_f_g_grad_hvp over the members of a drift ensemble instead of over eps-nodes: the weighted sums sum_i w_i of infidelity and leak,
+ * of the two gradients and of their derivatives along ndir directions, member i being the handle's problem with Hconst = drifts[:, :, i]
+ * (the members of jq_traceobjgrad_drifts / jq_eval_f_g_grad_drifts).
+ *   dirs    : [ncoeff x ndir] column-major, one direction per column
+ *   drifts  : [Ntot x Ntot x ndrift] column-major member drifts; weights : [ndrift]
+ *   out2, infid_grad, leak_grad, hv_infid, hv_leak : as jq_eval_f_g_grad_hvp
+ * Routes as jq_eval_f_g_grad_hvp (lane, row-lane, quad), with a member where that call has a node: a member brings an operator stream of
+ * its own and its N columns start at fresh waves -- lane route: a wave of 64 column lanes per member; row-lane and quad routes:
+ * ceil(N / 4) waves per member, on the quad route padded to whole workgroups (a workgroup shares its operator images) -- and as many
+ * members as the stream budget (option stream_bytes) leaves streams for next to the directions share a launch; the others follow in
+ * further member rounds.  Every member must lie inside the structure the handle was planned for (what jq_update_hconst would accept
+ * without re-planning); otherwise, and wherever jq_eval_f_g_grad_hvp runs its nodes one after the other, the members run one after the
+ * other on the run-time-size sweeps (route "sequential").  The call never re-plans the handle and never touches its drift or operator
+ * images.  jq_plan_info "drift_hvp": {route, members_per_launch, directions_per_launch, chunk_steps, rounds} after a call (rounds:
+ * direction rounds x member rounds); "ens_hvp", "hvp" and "drift_batch" keep the values of their own calls.  jq_last_timing and
+ * "last_kernels" as jq_eval_f_g_grad_hvp.  Refused with JQ_EUNSUPPORTED: what that call refuses.  JQ_EINVAL for NULL pointers (all are
+ * required), ndir < 1 or ndrift < 1; the codes of jq_traceobjgrad for the coefficient count.  A refused call writes nothing and leaves
+ * the handle as it was.  Multi-device handles run the call on their first device.  Not served: control mixes, members x eps-nodes,
+ * sharding over devices.
+ */
+int jq_eval_f_g_grad_drifts_hvp(jq_handle *h, const double *pcof, int32_t ncoeff, const double *dirs, int32_t ndir, const double *drifts,
+                                const double *weights, int32_t ndrift, double *out2, double *infid_grad, double *leak_grad,
+                                double *hv_infid, double *hv_leak);
 
 /*
  * Device-side consumers of the state history, so that the [Ntot x N x (nsteps+1)] arrays (199 MB at cnot3)

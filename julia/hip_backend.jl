@@ -365,6 +365,31 @@ function eval_f_g_grad_hvp(pcof::Vector{Float64}, dirs::VecOrMat{Float64}, param
     return (infidelity = out2[1], leak = out2[2], infid_grad = ig, leak_grad = lg, hv_infid = hvi, hv_leak = hvl)
 end
 
+# eval_f_g_grad_hvp over the members of a drift ensemble instead of over eps-nodes (jq_eval_f_g_grad_drifts_hvp): the weighted sums of
+# infidelity and leak, of the two gradients and of their derivatives along the columns of dirs, member i being the evaluation with
+# params.Hconst = Hconsts[:, :, i].  The routes of eval_f_g_grad_hvp with a member where that call has a node -- every wave reads the
+# operator stream of its own member; a member outside the structure the handle was planned for sends the members one after the other
+# (jq_plan_info "drift_hvp").  The handle's drift and plan are left alone.  Returns what eval_f_g_grad_hvp returns.
+function eval_f_g_grad_drifts_hvp(pcof::Vector{Float64}, dirs::VecOrMat{Float64}, params::objparams, wa::AbstractWorkingArraysHIP,
+                                  Hconsts::Array{Float64, 3}, weights::Vector{Float64})
+    ncoeff = length(pcof)
+    D = dirs isa Vector ? reshape(dirs, :, 1) : Matrix{Float64}(dirs)
+    size(D, 1) == ncoeff || throw(DimensionMismatch("eval_f_g_grad_drifts_hvp: dirs must have length(pcof) rows"))
+    nd = size(D, 2)
+    nd >= 1 || throw(ArgumentError("eval_f_g_grad_drifts_hvp: need at least one direction"))
+    Ntot = params.N + params.Nguard
+    nm = size(Hconsts, 3)
+    (size(Hconsts, 1) == Ntot && size(Hconsts, 2) == Ntot && nm >= 1) || throw(DimensionMismatch("eval_f_g_grad_drifts_hvp: Hconsts must be Ntot x Ntot x ndrift, ndrift >= 1"))
+    length(weights) == nm || throw(ArgumentError("eval_f_g_grad_drifts_hvp: need one weight per member drift"))
+    sync!(wa, params)
+    out2 = zeros(2); ig = zeros(ncoeff); lg = zeros(ncoeff); hvi = zeros(ncoeff, nd); hvl = zeros(ncoeff, nd)
+    jqcheck(wa, ccall((:jq_eval_f_g_grad_drifts_hvp, libjq), Cint,
+                      (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64},
+                       Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                      wa.handle, pcof, ncoeff, D, nd, Hconsts, weights, nm, out2, ig, lg, hvi, hvl))
+    return (infidelity = out2[1], leak = out2[2], infid_grad = ig, leak_grad = lg, hv_infid = hvi, hv_leak = hvl)
+end
+
 # All unit directions through one traceobjgrad_hvp call: the ncoeff x ncoeff Jacobian of totalgrad, (J + J')/2 with symmetrize.
 function hessian(pcof::Vector{Float64}, params::objparams, wa::AbstractWorkingArraysHIP, symmetrize::Bool = false)
     J = traceobjgrad_hvp(pcof, Matrix{Float64}(LinearAlgebra.I, length(pcof), length(pcof)), params, wa).hv

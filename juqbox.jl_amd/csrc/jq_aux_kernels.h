@@ -651,16 +651,33 @@ struct QuadMap {
     __device__ __forceinline__ size_t target(int ic, int R) const { return ((size_t)(ic / 16) * 4 * NT + R / 4) * 64 + 16 * (R % 4) + ic % 16; }
 };
 
+// A drift ensemble's tangent-linear files (jq_eval_f_g_grad_drifts_hvp): a member's N columns start at a fresh group of `cpg` column slots
+// -- whole waves, a wave propagates with one member's operators -- so sample s, column ic is column slot s cpg + ic of the base layout.
+template <class Base>
+struct MemberMap {
+    static constexpr int nleak = Base::nleak;
+    Base b;
+    int nrows, N;
+    long long cpg;
+    __device__ __forceinline__ long long slot(long long col) const { return (col / N) * cpg + col % N; }
+    __device__ __forceinline__ size_t at(int arr, int R, long long col) const { return b.at(arr, R, slot(col)); }
+    __device__ __forceinline__ size_t leak(long long col, int k) const { return b.leak(slot(col), k); }
+    __device__ __forceinline__ size_t target(int ic, int R) const { return b.target(ic, R); }
+};
+
 // state files <- (Uinit, 0 ...): one file per grid row, dstride doubles apart (the directions of jq_eval_f_g_grad_hvp; an evaluation has one).
 // uinit: [N][NP] (column ic of Uinit, zero padded); rows: rows of the file.  thread per column, grid = (columns / 64, files)
+// Every group of cpg column slots holds ncols_used columns in front (one group of all the slots: the packed columns of an evaluation or of
+// an ensemble over eps-nodes; a group per member of a drift ensemble: MemberMap).
 __global__ void k_init_lane(double* state, long long ncols, int NP, int rows, long long dstride, const double* __restrict__ uinit, int N,
-                            long long ncols_used)
+                            long long ncols_used, long long cpg)
 {
     const long long col = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (col >= ncols) return;
     double* st = state + (size_t)blockIdx.y * (size_t)dstride;
-    const int ic = (int)(col % N);
-    for (int r = 0; r < rows; ++r) st[(size_t)r * ncols + col] = (r < NP && col < ncols_used) ? uinit[ic * NP + r] : 0.0;
+    const long long c = col % cpg;
+    const int ic = (int)(c % N);
+    for (int r = 0; r < rows; ++r) st[(size_t)r * ncols + col] = (r < NP && c < ncols_used) ? uinit[ic * NP + r] : 0.0;
 }
 
 // ... in the row-lane layout.  uinit: [N][16]; cpw, wpg: the column packing (RowlaneMap).  grid = (waves, files), block = 64
@@ -676,13 +693,14 @@ __global__ void k_init_rowlane(double* state, long long nw, int rows, long long 
     for (int r = 0; r < rows; ++r) st[(size_t)r * nw * 64] = (r == 0 && used) ? uinit[(col % N) * 16 + (lane & 15)] : 0.0;
 }
 
-// ... in the tangent-linear quad layout.  uimg: the slab image of Uinit.  grid = (quads, directions), block = 64
+// ... in the tangent-linear quad layout.  uimg: the slab image of Uinit; cpg: the column slots of a group (k_init_lane).
+// grid = (quads, directions), block = 64
 __global__ __launch_bounds__(64) void k_init_quad_tl(double* state, long long nq, long long dstride, const double* __restrict__ uimg, int NT,
-                                                     int N, long long ncols_used)
+                                                     int N, long long ncols_used, long long cpg)
 {
     const int lane = threadIdx.x;
     const long long w = blockIdx.x;
-    const long long col = 4 * w + (lane & 3);
+    const long long col = (4 * w + (lane & 3)) % cpg;
     const int rowb = 4 * ((lane >> 2) & 3) + (lane >> 4);
     double* st = state + (size_t)blockIdx.y * (size_t)dstride + w * 64 + lane;
     const bool used = col < ncols_used;

@@ -19,11 +19,23 @@
 // Sequential route (everything else jq_traceobjgrad_hvp serves: Ntot 7, 8, Ntot > 16 without that structure or with NT = 7, 8, embedded
 // structures, options lane=0 / quad=0, more than JQ_MAXNC controls): the nodes one after the other through hvp_run with the drift
 // Hconst + eps_i diag(shift) -- correct and no faster.
+//
+// jq_eval_f_g_grad_drifts_hvp -- the same sums over the members of a drift ensemble, member i being the handle's problem with
+// Hconst = drifts[:, :, i]: the same driver and routes with another notion of a sample.  A sample of the eps ensemble is a node: its N
+// columns follow the node before it, every wave reads ONE primal stream and the node shift tells the columns apart.  A sample of a drift
+// ensemble is a member: it brings a primal stream of its own (its drift image in the route's layout in front of k_stream), its columns
+// start at fresh waves -- a wave propagates with one member's operators; quad route: a workgroup shares its operator rings, so a member
+// is padded to whole workgroups -- and P members share a launch ([member 0 .. P - 1 | direction ...] streams, PropArgs::nprimal).
+// Members beyond the stream budget run in further member rounds that accumulate into the same gradient blocks, in member order.  A
+// member outside the structure the handle was planned for (hconst_fits_plan) sends the whole call down the sequential route: the call
+// never re-plans the handle and never touches its operator images.
 static double ens_hvp_shift(const double* shift, int i) { return shift ? shift[i] : (i >= 1 ? 0.01 * pow(10.0, (double)(i - 1)) : 0.0); }
 
 struct EnsHvpArgs {
+    const char* who;            // the entry point that runs
     const double *pcof, *dirs, *nodes, *weights, *shift;
-    int ncoeff, ndir, nquad;
+    const double* drifts;       // NULL: nquad eps-nodes (nodes, shift); else HOST [Ntot x Ntot x nquad] member drifts (nodes, shift unused)
+    int ncoeff, ndir, nquad;    // nquad: samples -- nodes or members
     double *out2, *infid_grad, *leak_grad, *hv_infid, *hv_leak;
 };
 // the four outputs from the forced (g0, v0) and unforced (g1, v1; objFuncType != 1 only) gradients and products (out_grads' rule)
@@ -72,89 +84,127 @@ static EnsHvpLayout ens_hvp_layout_quad(const jq_handle* h)
 
 static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& lay, prop_kernel_t kfwd, prop_kernel_t kbwd, const KernelSel& sel)
 {
-    const char* who = "jq_eval_f_g_grad_hvp";
+    const char* who = x.who;
     HIPCHK(h, hipSetDevice(h->device));
-    const int Nc = h->Nc, ncoeff = x.ncoeff, ndir = x.ndir, nquad = x.nquad;
-    const size_t stride = lay.stride;
-    const long long ncols_used = (long long)nquad * h->N, ncols = (ncols_used + lay.cpw - 1) / lay.cpw * lay.cpw;
-    const int nwaves = (int)(ncols / lay.cpw), ntr = Nc * JQ_NTR;
+    const int Nc = h->Nc, ncoeff = x.ncoeff, ndir = x.ndir, nquad = x.nquad, ntr = Nc * JQ_NTR;
+    const bool members = x.drifts != nullptr;
+    const size_t stride = lay.stride, nn = (size_t)h->Ntot * h->Ntot;
+    // What a sample is.  wps: the waves that read one primal stream -- all the waves of the packed node columns, or a member's ceil(N / cpw)
+    // padded to whole workgroups of the sweep kernels; gcols: the columns in front of such a group of wps cpw column slots.
+    const long long gcols = members ? h->N : (long long)nquad * h->N;
+    int wps = (int)((gcols + lay.cpw - 1) / lay.cpw);
+    if (members) wps = (wps + std::min(lay.wpg, wps) - 1) / std::min(lay.wpg, wps) * std::min(lay.wpg, wps);
+    const long long cpg = (long long)wps * lay.cpw;
     const double dt = h->T / h->nsteps;
     const bool two_pass = h->objFuncType != 1;
     const int npass = two_pass ? 2 : 1;
+    const TlBudget b = tl_budget(h, stride, ndir, JQ_JVP_MAX_DIRS, (size_t)wps * ntr, members ? nquad : 1);      // (the directions are a grid dimension of their own)
+    // P primal streams (members) and spl samples per launch, mrounds launches per direction round; ngb gradient blocks [primal | direction ...]
+    const int dpl = b.dpl, cs = b.cs, rounds = b.rounds, P = b.mpl, mrounds = b.mrounds, nvec = P + dpl, ngb = 1 + dpl;
+    const int spl = members ? P : nquad, nwaves = P * wps;
+    const long long ncols = (long long)nwaves * lay.cpw;
     const size_t sstride = (size_t)lay.state_rows * (size_t)nwaves * 64;      // doubles of one direction's state file
-    const TlBudget b = tl_budget(h, stride, ndir, JQ_JVP_MAX_DIRS, (size_t)nwaves * ntr);      // (the directions are a grid dimension of their own)
-    const int dpl = b.dpl, cs = b.cs, rounds = b.rounds, nvec = 1 + dpl;
 
-    // tables [wd | ws], column info [eps | weight] (run_eval's for the layout), drift images of the groups [H0 | 0 ...]
-    std::vector<double> tabs((size_t)2 * lay.tab_off, 0.0), colinfo((size_t)2 * ncols, 0.0);
+    // tables [wd | ws]; per member round the column info [eps | weight] per column slot (run_eval's for the layout) and the drift images
+    // of its members in the route's layout (the builders and the bits of upload_operators' image 0; a short last round repeats its last
+    // member with weight 0: every group has a stream)
+    std::vector<double> tabs((size_t)2 * lay.tab_off, 0.0), colinfo((size_t)mrounds * 2 * ncols, 0.0), mimg(members ? (size_t)mrounds * P * stride : 0, 0.0);
     bool use_shift = false;
     for (int i = 0; i < h->Ntot; ++i) tabs[i] = h->wd[i], tabs[lay.tab_off + i] = ens_hvp_shift(x.shift, i);
-    for (long long c = 0; c < ncols_used; ++c) {
-        const int smp = (int)(c / h->N);
-        colinfo[c] = x.nodes[smp];
-        colinfo[ncols + c] = x.weights[smp];
-        if (x.nodes[smp] != 0.0) use_shift = true;
-    }
+    for (int mr = 0; mr < mrounds; ++mr)
+        for (int sl = 0; sl < spl; ++sl) {
+            const int smp = mr * spl + sl;
+            if (members) {
+                const double* M = x.drifts + nn * std::min(smp, nquad - 1);
+                double* img = mimg.data() + ((size_t)mr * P + sl) * stride;
+                if (lay.route == 1) plain_image(M, h->Ntot, lay.size, img);
+                else if (lay.route == 3) rowlane_image(M, h->Ntot, lay.size, img);
+                else tile_image(M, h->Ntot, lay.size, JQ_BW_T4, img);
+            }
+            if (smp >= nquad) continue;
+            for (int ic = 0; ic < h->N; ++ic) {
+                const long long c = (size_t)mr * 2 * ncols + (members ? sl * cpg + ic : (long long)sl * h->N + ic);
+                colinfo[c] = members ? 0.0 : x.nodes[smp];
+                colinfo[ncols + c] = x.weights[smp];
+                if (!members && x.nodes[smp] != 0.0) use_shift = true;
+            }
+        }
     DevBuf d_h0, d_pc, d_pq, d_stream, d_state, d_save, d_tabs, d_col, d_res, d_tr, d_R, d_g;
     int rc;
     if ((rc = d_h0.alloc(h, who, (size_t)nvec * stride)) || (rc = d_pc.alloc(h, who, (size_t)nvec * ncoeff)) ||
         (rc = d_pq.alloc(h, who, (size_t)nvec * (2 * cs + 1) * 2 * Nc)) || (rc = d_stream.alloc(h, who, (size_t)nvec * b.gstride)) ||
         (rc = d_state.alloc(h, who, (size_t)dpl * sstride)) || (rc = d_save.alloc(h, who, two_pass ? (size_t)dpl * sstride : 1)) ||
-        (rc = d_tabs.alloc(h, who, tabs.size())) || (rc = d_col.alloc(h, who, colinfo.size())) || (rc = d_res.alloc(h, who, (size_t)dpl * nquad * 4)) ||
-        (rc = d_tr.alloc(h, who, (size_t)2 * dpl * nwaves * cs * ntr)) || (rc = d_R.alloc(h, who, (size_t)nvec * cs * ntr)) ||
-        (rc = d_g.alloc(h, who, (size_t)2 * nvec * ncoeff)))
+        (rc = d_tabs.alloc(h, who, tabs.size())) || (rc = d_col.alloc(h, who, (size_t)2 * ncols)) || (rc = d_res.alloc(h, who, (size_t)dpl * spl * 4)) ||
+        (rc = d_tr.alloc(h, who, (size_t)2 * dpl * nwaves * cs * ntr)) || (rc = d_R.alloc(h, who, (size_t)ngb * cs * ntr)) ||
+        (rc = d_g.alloc(h, who, (size_t)2 * ngb * ncoeff)))
         return rc;
     // d_g: [pass][primal | direction ...][ncoeff]
     hipStream_t s = h->stream;
     HIPCHK(h, hipMemsetAsync(d_h0.p, 0, (size_t)nvec * stride * sizeof(double), s));
-    HIPCHK(h, hipMemcpyAsync(d_h0.p, lay.himg, stride * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (!members) HIPCHK(h, hipMemcpyAsync(d_h0.p, lay.himg, stride * sizeof(double), hipMemcpyDeviceToDevice, s));
     HIPCHK(h, hipMemcpyAsync(d_tabs.p, tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d_col.p, colinfo.data(), colinfo.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    // the samples of member round mr: column info, drift images [H_0 .. H_{P - 1} | 0 ...]
+    const auto upload_samples = [&](int mr) -> int {
+        HIPCHK(h, hipMemcpyAsync(d_col.p, colinfo.data() + (size_t)mr * 2 * ncols, (size_t)2 * ncols * sizeof(double), hipMemcpyHostToDevice, s));
+        if (members) HIPCHK(h, hipMemcpyAsync(d_h0.p, mimg.data() + (size_t)mr * P * stride, (size_t)P * stride * sizeof(double), hipMemcpyHostToDevice, s));
+        return JQ_OK;
+    };
+    if (mrounds == 1 && (rc = upload_samples(0))) return rc;
 
     const TlGen gen = {tl_spline(h, d_pc.p, ncoeff, nullptr), lay.himg, d_h0.p, d_pq.p, d_stream.p, stride, b.gstride, nvec};
     PropArgs a;
     memset(&a, 0, sizeof a);
-    a.stream = d_stream.p; a.stream_gstride = (long long)b.gstride; a.group_units = 1; a.state = d_state.p; a.state_stride = (long long)sstride;
+    a.stream = d_stream.p; a.stream_gstride = (long long)b.gstride; a.group_units = wps; a.nprimal = P; a.state = d_state.p; a.state_stride = (long long)sstride;
     a.colinfo = d_col.p; a.tabs = d_tabs.p; a.traces = d_tr.p; a.cimg = lay.cimg; a.stride = (long long)stride; a.m = h->m; a.nslabs = lay.slabs_are_waves ? nwaves : (int)ncols;
-    a.Ncoupled = Nc; a.Ntot = h->Ntot; a.N = h->N; a.parts = 1; a.nsamples = nquad; a.sps = 1; a.tinv = 1.0 / h->T; a.use_shift = use_shift ? 1 : 0;
+    a.Ncoupled = Nc; a.Ntot = h->Ntot; a.N = h->N; a.parts = 1; a.nsamples = spl; a.sps = 1; a.tinv = 1.0 / h->T; a.use_shift = use_shift ? 1 : 0;
     for (int q = 0; q < JQ_MAXNC && lay.modes; ++q) a.bw_trace[q] = q < Nc ? h->bw_trace[q] : 0;
     if (lay.lds_fwd) HIPCHK(h, hipFuncSetAttribute((const void*)kfwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.lds_fwd));
     if (lay.lds_bwd) HIPCHK(h, hipFuncSetAttribute((const void*)kbwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.lds_bwd));
 
     LaunchTimer tm{h};
-    if ((rc = tm.start((size_t)b.nchunks * rounds * (1 + npass)))) return rc;
-    std::vector<double> res((size_t)nquad * 4), blk((size_t)nvec * ncoeff), gbuf((size_t)2 * nvec * ncoeff);
+    if ((rc = tm.start((size_t)b.nchunks * rounds * mrounds * (1 + npass)))) return rc;
+    std::vector<double> res((size_t)nquad * 4), blk((size_t)nvec * ncoeff), gbuf((size_t)2 * ngb * ncoeff);
     std::vector<double> g0(ncoeff), g1(two_pass ? ncoeff : 0), v0((size_t)ncoeff * ndir), v1(two_pass ? (size_t)ncoeff * ndir : 0);
     const dim3 grid((unsigned)nwaves, (unsigned)dpl);
     // the sweep kernels: wpg consecutive waves of a direction per workgroup (1 on the lane and row-lane routes: the launch it always was)
-    const int wpg = std::min(lay.wpg, nwaves);
+    const int wpg = std::min(lay.wpg, wps);
     const dim3 sgrid((unsigned)((nwaves + wpg - 1) / wpg), (unsigned)dpl), sblock((unsigned)(64 * wpg));
     // The two launches that bracket a forward sweep, the one place where the driver tells the routes apart.  init: the state files <- (Uinit, 0 ...);
     // else fidelity, leak, lambda(T) and its tangent per (node, direction).  The leak partials are in the last row of a file; lay.size is NP / NT.
     const auto endpoint = [&](bool init) {
-        const auto terminal = [&](auto map) {
-            terminal_cols<EP_TL>(s, map, dpl, d_state.p, sstride, lay.vtr, lay.vti, nullptr, nullptr, 1, h->N, nquad, 0.5 * dt * (1.0 / h->T), d_res.p);
+        // (a drift ensemble's members start at fresh groups of cpg column slots: the layout's map behind MemberMap)
+        const auto terminal = [&](auto map, int nrows) {
+            if (members)
+                terminal_cols<EP_TL>(s, MemberMap<decltype(map)>{map, nrows, h->N, cpg}, dpl, d_state.p, sstride, lay.vtr, lay.vti, nullptr, nullptr, 1, h->N, spl,
+                                     0.5 * dt * (1.0 / h->T), d_res.p);
+            else terminal_cols<EP_TL>(s, map, dpl, d_state.p, sstride, lay.vtr, lay.vti, nullptr, nullptr, 1, h->N, spl, 0.5 * dt * (1.0 / h->T), d_res.p);
         };
         const long long nw = nwaves, ss = (long long)sstride;
         const int last = lay.state_rows - 1;
         switch (lay.route) {
         case 1:
-            if (init) hipLaunchKernelGGL(k_init_lane, grid, dim3(64), 0, s, d_state.p, ncols, lay.size, lay.state_rows, ss, lay.uinit, h->N, ncols_used);
-            else terminal(LaneMap{lay.size, ncols, last});
+            if (init) hipLaunchKernelGGL(k_init_lane, grid, dim3(64), 0, s, d_state.p, ncols, lay.size, lay.state_rows, ss, lay.uinit, h->N, gcols, cpg);
+            else terminal(LaneMap{lay.size, ncols, last}, lay.size);
             break;
-        case 3:
-            if (init) hipLaunchKernelGGL(k_init_rowlane, grid, dim3(64), 0, s, d_state.p, nw, lay.state_rows, ss, lay.uinit, h->N, ncols_used, lay.cpw, 1);
-            else terminal(RowlaneMap{nw, lay.cpw, 1, last});
+        case 3:      // (k_init_rowlane's packing: every gcols columns start at a fresh group of wps waves)
+            if (init)
+                hipLaunchKernelGGL(k_init_rowlane, grid, dim3(64), 0, s, d_state.p, nw, lay.state_rows, ss, lay.uinit, h->N, members ? spl * gcols : gcols,
+                                   members ? (int)gcols : lay.cpw, members ? wps : 1);
+            else terminal(RowlaneMap{nw, lay.cpw, 1, last}, RowlaneMap::nrows);
             break;
         default:
-            if (init) hipLaunchKernelGGL(k_init_quad_tl, grid, dim3(64), 0, s, d_state.p, nw, ss, lay.uinit, lay.size, h->N, ncols_used);
-            else terminal(QuadMap{h->Ntot, lay.size, nw, last, (size_t)lay.size * nwaves * 64});
+            if (init) hipLaunchKernelGGL(k_init_quad_tl, grid, dim3(64), 0, s, d_state.p, nw, ss, lay.uinit, lay.size, h->N, gcols, cpg);
+            else terminal(QuadMap{h->Ntot, lay.size, nw, last, (size_t)lay.size * nwaves * 64}, h->Ntot);
         }
     };
-    for (int r = 0; r < rounds; ++r) {
-        const int j0 = r * dpl, nd = std::min(dpl, ndir - j0);
-        if ((rc = tl_upload_round(h, blk, d_pc.p, x.pcof, x.dirs, j0, nd, dpl, ncoeff))) return rc;
-        HIPCHK(h, hipMemsetAsync(d_g.p, 0, (size_t)2 * nvec * ncoeff * sizeof(double), s));
+    // rounds of dpl directions; within one, mrounds launches of P members each accumulate into the round's gradient blocks, in member order
+    for (int it = 0; it < rounds * mrounds; ++it) {
+        const int r = it / mrounds, mr = it % mrounds, j0 = r * dpl, nd = std::min(dpl, ndir - j0);
+        if (mr == 0) {
+            if ((rc = tl_upload_round(h, blk, d_pc.p, x.pcof, x.dirs, j0, nd, dpl, ncoeff, P))) return rc;
+            HIPCHK(h, hipMemsetAsync(d_g.p, 0, (size_t)2 * ngb * ncoeff * sizeof(double), s));
+        }
+        if (mrounds > 1 && (rc = upload_samples(mr))) return rc;
         // ---- forward sweep of (state, tangent) ----
         endpoint(true);
         a.h = dt; a.forced = 1;
@@ -168,7 +218,8 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
         }
         endpoint(false);
         HIPCHK(h, hipGetLastError());
-        if (r == 0) HIPCHK(h, hipMemcpyAsync(res.data(), d_res.p, (size_t)nquad * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (r == 0)      // (the records of this launch's samples, from the first direction's file)
+            HIPCHK(h, hipMemcpyAsync(res.data() + (size_t)mr * spl * 4, d_res.p, (size_t)std::min(spl, nquad - mr * spl) * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
         // ---- backward sweeps: forced, then (objFuncType != 1) unforced from the saved terminal state ----
         if (two_pass) HIPCHK(h, hipMemcpyAsync(d_save.p, d_state.p, (size_t)dpl * sstride * sizeof(double), hipMemcpyDeviceToDevice, s));
         for (int pass = 0; pass < npass; ++pass) {
@@ -181,13 +232,14 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
                 if ((rc = tm.begin(true))) return rc;
                 hipLaunchKernelGGL(kbwd, sgrid, sblock, lay.lds_bwd, s, a);
                 if ((rc = tm.end())) return rc;
-                tl_reduce_chunk(h, gen.sp, r == 0, d_tr.p, nwaves, dpl, n0, nc, 0, Nc, d_R.p, d_R.p + (size_t)cs * ntr, d_g.p + (size_t)pass * nvec * ncoeff);
+                tl_reduce_chunk(h, gen.sp, r == 0, d_tr.p, nwaves, dpl, n0, nc, 0, Nc, d_R.p, d_R.p + (size_t)cs * ntr, d_g.p + (size_t)pass * ngb * ncoeff);
             }
         }
         HIPCHK(h, hipGetLastError());
+        if (mr < mrounds - 1) continue;
         HIPCHK(h, hipMemcpyAsync(gbuf.data(), d_g.p, gbuf.size() * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));      // (the host blocks are reused by the next round)
-        tl_copy_out(gbuf, nvec, ncoeff, two_pass, r == 0, j0, nd, g0.data(), two_pass ? g1.data() : nullptr, v0.data(), two_pass ? v1.data() : nullptr);
+        tl_copy_out(gbuf, ngb, ncoeff, two_pass, r == 0, j0, nd, g0.data(), two_pass ? g1.data() : nullptr, v0.data(), two_pass ? v1.data() : nullptr);
     }
     if ((rc = tm.stop())) return rc;
     double inf = 0.0, leak = 0.0;
@@ -197,7 +249,8 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
     }
     x.out2[0] = inf, x.out2[1] = leak;
     ens_hvp_outputs(h, x, g0.data(), g1.data(), v0.data(), v1.data());
-    h->ens_hvp_route = lay.route, h->ens_hvp_per_launch = dpl, h->ens_hvp_chunk = cs, h->ens_hvp_rounds = rounds;
+    if (members) h->drift_hvp_route = lay.route, h->drift_hvp_members = P, h->drift_hvp_per_launch = dpl, h->drift_hvp_chunk = cs, h->drift_hvp_rounds = rounds * mrounds;
+    else h->ens_hvp_route = lay.route, h->ens_hvp_per_launch = dpl, h->ens_hvp_chunk = cs, h->ens_hvp_rounds = rounds;
 
     if ((rc = tm.finish(lay.label))) return rc;
     h->timing.svts = (long long)ndir * nquad * h->N * h->nsteps;
@@ -220,9 +273,12 @@ static int ens_hvp_sequential(jq_handle* h, const EnsHvpArgs& x)
     const int keep[3] = {h->hvp_per_launch, h->hvp_chunk, h->hvp_rounds};      // ("hvp" of jq_plan_info stays jq_traceobjgrad_hvp's)
     int rc = JQ_OK, dpl = 0, cs = 0, rounds = 0;
     for (int i = 0; i < x.nquad && rc == JQ_OK; ++i) {
-        drift = h->Hconst;
-        for (int j = 0; j < Ntot; ++j) drift[(size_t)j * Ntot + j] += x.nodes[i] * ens_hvp_shift(x.shift, j);      // src/ipopt_interface.jl:41-44
-        rc = hvp_run(h, drift.data(), x.pcof, ncoeff, x.dirs, ndir, out4, gi.data(), vi.data(), vin.data(), gin.data(), "jq_eval_f_g_grad_hvp");
+        if (x.drifts) drift.assign(x.drifts + (size_t)i * Ntot * Ntot, x.drifts + (size_t)(i + 1) * Ntot * Ntot);      // member i
+        else {
+            drift = h->Hconst;
+            for (int j = 0; j < Ntot; ++j) drift[(size_t)j * Ntot + j] += x.nodes[i] * ens_hvp_shift(x.shift, j);      // src/ipopt_interface.jl:41-44
+        }
+        rc = hvp_run(h, drift.data(), x.pcof, ncoeff, x.dirs, ndir, out4, gi.data(), vi.data(), vin.data(), gin.data(), x.who);
         if (rc != JQ_OK) break;
         const double w = x.weights[i];
         inf += out4[1] * w, leak += out4[2] * w;
@@ -245,8 +301,44 @@ static int ens_hvp_sequential(jq_handle* h, const EnsHvpArgs& x)
     ens_hvp_outputs(h, x, g0.data(), g1.data(), v0.data(), v1.data());
     h->timing = sum;
     h->timing.ms_shard_min = h->timing.ms_shard_max = h->timing.ms_total;
-    h->ens_hvp_route = 2, h->ens_hvp_per_launch = dpl, h->ens_hvp_chunk = cs, h->ens_hvp_rounds = rounds;
+    if (x.drifts) h->drift_hvp_route = 2, h->drift_hvp_members = 1, h->drift_hvp_per_launch = dpl, h->drift_hvp_chunk = cs, h->drift_hvp_rounds = rounds;
+    else h->ens_hvp_route = 2, h->ens_hvp_per_launch = dpl, h->ens_hvp_chunk = cs, h->ens_hvp_rounds = rounds;
     return JQ_OK;
+}
+
+// The route of a call whose arguments have passed: lane, row-lane, quad, else sequential.
+static int ens_hvp_dispatch(jq_handle* h, const EnsHvpArgs& x)
+{
+    // a drift ensemble: every member inside the structure the handle's kernels and images were chosen for, or the members one after the
+    // other on the run-time-size kernels (which take any drift) -- never a re-plan
+    if (x.drifts)
+        for (int i = 0; i < x.nquad; ++i)
+            if (!hconst_fits_plan(h, x.drifts + (size_t)i * h->Ntot * h->Ntot)) return ens_hvp_sequential(h, x);
+    // lane route: the tangent-linear lane kernels exist for the handle's NP and one pass takes its controls; independent of the column
+    // bounds of the lane GRADIENT kernels (options lane_min / lane_max): one node is served here too
+    if (h->lane_np > 0 && h->Nc <= JQ_MAXNC) {
+        KernelSel sel = sel_start();
+        const int np = h->lane_np;
+        const prop_kernel_t kfwd = pick(sel.fwd, np, -1, "k_forward_lane_tl", {np}), kbwd = pick(sel.bwd, np, -1, "k_backward_lane_tl", {np});
+        if (kfwd && kbwd) return ens_hvp_lane(h, x, ens_hvp_layout_lane(h), kfwd, kbwd, sel);
+    }
+    // row-lane route: Ntot 9 .. 16 (rl_npj is 0 under option lane=0 and on embedded twins; NPJ <= 8 has no tangent kernels: Ntot <= 6 went
+    // the lane route above, Ntot 7 and 8 stay sequential)
+    if (h->rl_npj >= 12 && h->Nc <= JQ_MAXNC) {
+        KernelSel sel = sel_start();
+        const int np = h->rl_npj;
+        const prop_kernel_t kfwd = pick(sel.fwd, np, -1, "k_forward_rowlane_tl", {np}), kbwd = pick(sel.bwd, np, -1, "k_backward_rowlane_tl", {np});
+        if (kfwd && kbwd) return ens_hvp_lane(h, x, ens_hvp_layout_rowlane(h), kfwd, kbwd, sel);
+    }
+    // quad route: Ntot > 16 with the 4 x 4 x n structure of the handle's own plan (never an embedded twin) and its quad-layout kernels enabled
+    // (option quad=0 switches the route off); NT = 7, 8 have no tangent kernels (their backward kernels need scratch) and stay sequential
+    if (h->BW == JQ_BW_T4 && h->quad_max_slabs > 0 && h->NT >= 2 && h->Nc <= JQ_MAXNC && h->mat_elems == (long long)JQ_T4_ELEMS(h->NT)) {
+        KernelSel sel = sel_start();
+        const int nt = h->NT;
+        const prop_kernel_t kfwd = pick(sel.fwd, nt, JQ_BW_T4Q, "k_forward_quad_tl", {nt}), kbwd = pick(sel.bwd, nt, JQ_BW_T4Q, "k_backward_quad_tl", {nt});
+        if (kfwd && kbwd) return ens_hvp_lane(h, x, ens_hvp_layout_quad(h), kfwd, kbwd, sel);
+    }
+    return ens_hvp_sequential(h, x);
 }
 
 extern "C" int jq_eval_f_g_grad_hvp(jq_handle* h, const double* pcof, int32_t ncoeff, const double* dirs, int32_t ndir, const double* nodes,
@@ -263,31 +355,25 @@ extern "C" int jq_eval_f_g_grad_hvp(jq_handle* h, const double* pcof, int32_t nc
         if (int rc = tl_refuse(h, "jq_eval_f_g_grad_hvp", true)) return rc;
         if (int rc = check_ncoeff(h, ncoeff)) return rc;
         EvalGate gate(h);
-        const EnsHvpArgs x = {pcof, dirs, nodes, weights, shift, ncoeff, ndir, nquad, out2, infid_grad, leak_grad, hv_infid, hv_leak};
-        // lane route: the tangent-linear lane kernels exist for the handle's NP and one pass takes its controls; independent of the column
-        // bounds of the lane GRADIENT kernels (options lane_min / lane_max): one node is served here too
-        if (h->lane_np > 0 && h->Nc <= JQ_MAXNC) {
-            KernelSel sel = sel_start();
-            const int np = h->lane_np;
-            const prop_kernel_t kfwd = pick(sel.fwd, np, -1, "k_forward_lane_tl", {np}), kbwd = pick(sel.bwd, np, -1, "k_backward_lane_tl", {np});
-            if (kfwd && kbwd) return ens_hvp_lane(h, x, ens_hvp_layout_lane(h), kfwd, kbwd, sel);
-        }
-        // row-lane route: Ntot 9 .. 16 (rl_npj is 0 under option lane=0 and on embedded twins; NPJ <= 8 has no tangent kernels: Ntot <= 6 went
-        // the lane route above, Ntot 7 and 8 stay sequential)
-        if (h->rl_npj >= 12 && h->Nc <= JQ_MAXNC) {
-            KernelSel sel = sel_start();
-            const int np = h->rl_npj;
-            const prop_kernel_t kfwd = pick(sel.fwd, np, -1, "k_forward_rowlane_tl", {np}), kbwd = pick(sel.bwd, np, -1, "k_backward_rowlane_tl", {np});
-            if (kfwd && kbwd) return ens_hvp_lane(h, x, ens_hvp_layout_rowlane(h), kfwd, kbwd, sel);
-        }
-        // quad route: Ntot > 16 with the 4 x 4 x n structure of the handle's own plan (never an embedded twin) and its quad-layout kernels enabled
-        // (option quad=0 switches the route off); NT = 7, 8 have no tangent kernels (their backward kernels need scratch) and stay sequential
-        if (h->BW == JQ_BW_T4 && h->quad_max_slabs > 0 && h->NT >= 2 && h->Nc <= JQ_MAXNC && h->mat_elems == (long long)JQ_T4_ELEMS(h->NT)) {
-            KernelSel sel = sel_start();
-            const int nt = h->NT;
-            const prop_kernel_t kfwd = pick(sel.fwd, nt, JQ_BW_T4Q, "k_forward_quad_tl", {nt}), kbwd = pick(sel.bwd, nt, JQ_BW_T4Q, "k_backward_quad_tl", {nt});
-            if (kfwd && kbwd) return ens_hvp_lane(h, x, ens_hvp_layout_quad(h), kfwd, kbwd, sel);
-        }
-        return ens_hvp_sequential(h, x);
+        return ens_hvp_dispatch(h, {"jq_eval_f_g_grad_hvp", pcof, dirs, nodes, weights, shift, nullptr, ncoeff, ndir, nquad, out2, infid_grad, leak_grad, hv_infid, hv_leak});
+    });
+}
+
+extern "C" int jq_eval_f_g_grad_drifts_hvp(jq_handle* h, const double* pcof, int32_t ncoeff, const double* dirs, int32_t ndir, const double* drifts,
+                                           const double* weights, int32_t ndrift, double* out2, double* infid_grad, double* leak_grad, double* hv_infid,
+                                           double* hv_leak)
+{
+    if (!h) return JQ_EINVAL;
+    return abi_guard(h, "jq_eval_f_g_grad_drifts_hvp", [&]() -> int {
+        if (!pcof || !dirs || !drifts || !weights || !out2 || !infid_grad || !leak_grad || !hv_infid || !hv_leak)
+            return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_drifts_hvp: NULL pointer");
+        if (ndir < 1) return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_drifts_hvp: ndir must be >= 1");
+        if (ndrift < 1) return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_drifts_hvp: the member count must be >= 1");
+        JQ_ON_FIRST(h, jq_eval_f_g_grad_drifts_hvp(s0_, pcof, ncoeff, dirs, ndir, drifts, weights, ndrift, out2, infid_grad, leak_grad, hv_infid, hv_leak))
+        if (int rc = tl_refuse(h, "jq_eval_f_g_grad_drifts_hvp", true)) return rc;
+        if (int rc = check_ncoeff(h, ncoeff)) return rc;
+        EvalGate gate(h);
+        return ens_hvp_dispatch(h, {"jq_eval_f_g_grad_drifts_hvp", pcof, dirs, nullptr, weights, nullptr, drifts, ncoeff, ndir, ndrift, out2, infid_grad, leak_grad, hv_infid,
+                                 hv_leak});
     });
 }

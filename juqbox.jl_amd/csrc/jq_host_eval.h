@@ -407,7 +407,7 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
                            h->N, ncols_used, p.cpw, p.wpg);
     else if (p.layout == SL_LANE)
         hipLaunchKernelGGL(k_init_lane, dim3((unsigned)(p.ncols / 64)), dim3(64), 0, s, h->d_state, p.ncols, h->lane_np, JQ_LANE_ROWS(h->lane_np), 0LL,
-                           h->d_uinit_l, h->N, ncols_used);
+                           h->d_uinit_l, h->N, ncols_used, p.ncols);
     else
         hipLaunchKernelGGL(k_init_state, dim3(p.nslabs), dim3(64), 0, s, h->d_state, h->state_stride, h->d_uimg, h->KT, h->parts);
 

@@ -185,6 +185,11 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
     if (h->ens_hvp_route > 0)
         kv("ens_hvp", std::string("{\"route\": \"") + (h->ens_hvp_route == 1 ? "lane" : h->ens_hvp_route == 3 ? "rowlane" : h->ens_hvp_route == 4 ? "quad" : "sequential") + "\", \"directions_per_launch\": " + num(h->ens_hvp_per_launch) +
                           ", \"chunk_steps\": " + num(h->ens_hvp_chunk) + ", \"rounds\": " + num(h->ens_hvp_rounds) + "}");
+    // jq_eval_f_g_grad_drifts_hvp (after a call): the route its members took, members and directions per launch, chunk length, launches'
+    // rounds (direction rounds x member rounds; sequential: one member per launch, the rounds of all members)
+    if (h->drift_hvp_route > 0)
+        kv("drift_hvp", std::string("{\"route\": \"") + (h->drift_hvp_route == 1 ? "lane" : h->drift_hvp_route == 3 ? "rowlane" : h->drift_hvp_route == 4 ? "quad" : "sequential") + "\", \"members_per_launch\": " + num(h->drift_hvp_members) +
+                          ", \"directions_per_launch\": " + num(h->drift_hvp_per_launch) + ", \"chunk_steps\": " + num(h->drift_hvp_chunk) + ", \"rounds\": " + num(h->drift_hvp_rounds) + "}");
     o += "}";
     if (buflen > 0) {
         const size_t n = std::min(o.size(), (size_t)buflen - 1);

@@ -45,20 +45,27 @@ static int tl_refuse(jq_handle* h, const char* who, bool with_adjoint)
 // same budget; never longer chunks than the handle's (option chunk_steps), never more than dir_cap directions.
 #define JQ_JVP_MIN_CHUNK 16      // directions per launch: as many as leave the stream budget room for chunks of this many steps
 #define JQ_JVP_MAX_DIRS 4096     // ... and at most this many workgroups in a launch's grid dimension (run-time-size kernels: directions x parts)
+// A drift ensemble (nmember > 1; jq_eval_f_g_grad_drifts_hvp) brings one primal stream per member: the directions are sized first, as for one
+// member, then as many members per launch (mpl) as the budget leaves streams for next to them, in mrounds rounds of equal size; trec is the
+// record of ONE member.  nmember == 1 is the budget it always was.
 struct TlBudget {
     int dpl, cs, rounds, nchunks;
     size_t gstride;      // doubles of one group's stream of a chunk
+    int mpl, mrounds;    // primal streams (members) per launch, member rounds
 };
-static TlBudget tl_budget(const jq_handle* h, size_t stride, int ndir, int dir_cap, size_t trec)
+static TlBudget tl_budget(const jq_handle* h, size_t stride, int ndir, int dir_cap, size_t trec, int nmember = 1)
 {
     const size_t budget = stream_budget_bytes(h) / sizeof(double);
     const long long want = 2LL * std::min(JQ_JVP_MIN_CHUNK, h->nsteps) + 1;
     const long long fit = (long long)(budget / (2 * stride * (size_t)want)) - 1;
     TlBudget b;
     b.dpl = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(ndir, dir_cap), fit));
-    const long long tps = (long long)(budget / ((size_t)(1 + b.dpl) * 2 * stride));
+    const long long mfit = std::max<long long>(1, std::min<long long>(nmember, fit + 1 - b.dpl));
+    b.mrounds = (int)((nmember + mfit - 1) / mfit);
+    b.mpl = (nmember + b.mrounds - 1) / b.mrounds;
+    const long long tps = (long long)(budget / ((size_t)(b.mpl + b.dpl) * 2 * stride));
     long long cs = std::min<long long>(std::min(h->chunk_steps, h->nsteps), (tps - 1) / 2);
-    if (trec) cs = std::min<long long>(cs, (long long)(budget / ((size_t)2 * b.dpl * trec)));
+    if (trec) cs = std::min<long long>(cs, (long long)(budget / ((size_t)2 * b.dpl * b.mpl * trec)));
     b.cs = (int)std::max<long long>(1, cs);
     b.rounds = (ndir + b.dpl - 1) / b.dpl;
     b.nchunks = (h->nsteps + b.cs - 1) / b.cs;
@@ -93,10 +100,11 @@ static void tl_generate(const jq_handle* h, const TlGen& g, int n0, int nc, doub
 }
 
 // the coefficient blocks [pcof | dirs[:, j0 + j] ...] of a round on the device (a short last round repeats its last direction: every group has a stream)
-static int tl_upload_round(jq_handle* h, std::vector<double>& blk, double* d_pc, const double* pcof, const double* dirs, int j0, int nd, int dpl, int ncoeff)
+// np primal streams (the members of a drift ensemble share ONE control vector): pcof in front np times
+static int tl_upload_round(jq_handle* h, std::vector<double>& blk, double* d_pc, const double* pcof, const double* dirs, int j0, int nd, int dpl, int ncoeff, int np = 1)
 {
-    std::copy(pcof, pcof + ncoeff, blk.begin());
-    for (int j = 0; j < dpl; ++j) std::copy_n(dirs + (size_t)(j0 + std::min(j, nd - 1)) * ncoeff, ncoeff, blk.begin() + (size_t)(1 + j) * ncoeff);
+    for (int g = 0; g < np; ++g) std::copy(pcof, pcof + ncoeff, blk.begin() + (size_t)g * ncoeff);
+    for (int j = 0; j < dpl; ++j) std::copy_n(dirs + (size_t)(j0 + std::min(j, nd - 1)) * ncoeff, ncoeff, blk.begin() + (size_t)(np + j) * ncoeff);
     HIPCHK(h, hipMemcpyAsync(d_pc, blk.data(), blk.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     return JQ_OK;
 }

@@ -1047,6 +1047,11 @@ struct PropArgs {
     // grouped.  No other kernel reads these fields.
     long long stream_gstride;
     int group_units;
+    // Tangent-linear sweeps (jq_lane_tl_kernels.h, jq_rowlane_tl_kernels.h, jq_quad_tl_kernels.h): the chunk holds `nprimal` primal streams
+    // [member 0 .. nprimal - 1] in front of the directions' streams.  A wave propagates with the stream of the member it belongs to, group_units
+    // waves per member (jq_group_stream; one member: every wave of the launch), and differentiates along direction blockIdx.y (jq_tl_dir_stream).
+    // 1: the ensemble over eps-nodes (jq_eval_f_g_grad_hvp), P: a launch of P drift members (jq_eval_f_g_grad_drifts_hvp).
+    int nprimal;
 };
 // The tile stream of the control vector that unit `unit` of the launch (row-lane kernels: wave, cooperative-quad kernels: column quad)
 // works for, a.group_units units per vector.  Wave-uniform by construction (block index and kernel arguments); the readfirstlane says so to the
@@ -1055,6 +1060,11 @@ __device__ __forceinline__ const double* jq_group_stream(const PropArgs& a, int 
 {
     const int g = __builtin_amdgcn_readfirstlane(unit / a.group_units);
     return a.stream + (size_t)g * (size_t)a.stream_gstride;
+}
+// The stream of direction blockIdx.y of a tangent-linear sweep, behind the a.nprimal primal streams (wave-uniform: block index and kernel arguments)
+__device__ __forceinline__ const double* jq_tl_dir_stream(const PropArgs& a)
+{
+    return a.stream + (size_t)(a.nprimal + blockIdx.y) * (size_t)a.stream_gstride;
 }
 #ifndef JQ_MAX_WRANK
 #define JQ_MAX_WRANK 16       // largest rank of a full weight matrix the kernels take (include/juqbox_hip.h)

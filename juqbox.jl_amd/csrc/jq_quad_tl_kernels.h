@@ -11,7 +11,9 @@
 // block mt, column j of the quad (the operand layout of v_mfma_f64_4x4x4_4b, mm_t4q).  blockIdx.y = the direction.  A workgroup is
 // blockDim.x / 64 (1 .. JQ_QUAD_TL_WAVES) consecutive quads of ONE direction: quad blockIdx.x * waves + wave; a wave past the last
 // quad only takes part in the staging.
-// The chunk holds 1 + gridDim.y operator streams of T4 images, a.stream_gstride doubles apart: group 0 at pcof, group 1 + j generated
+// The chunk holds P + gridDim.y operator streams of T4 images (P = a.nprimal), a.stream_gstride doubles apart: groups 0 .. P - 1 at
+// pcof (one per member of a drift ensemble, a.group_units quads each, a workgroup holds quads of one member; P = 1: one stream for
+// every quad), group P + j generated
 // by k_ctrl / k_stream with direction j as the coefficient vector and a zero drift image -- the controls are linear in the
 // coefficients, so that stream IS the derivative of the primal one.  Every product is mm_t4q on an image of one of the two, and
 //     y = c + M x   has the tangent   yd = cd + M xd + Md x      (two more mm_t4q).
@@ -44,7 +46,7 @@
 #if defined(JQ_BW) && JQ_BW == 7
 #include "jq_kernels.h"
 
-// the two rings of a workgroup: [primal | direction blockIdx.y], slots [t even | t odd | half point] of [K | S] each
+// the two rings of a workgroup: [primal stream of its member | direction blockIdx.y], slots [t even | t odd | half point] of [K | S] each
 template <int NT>
 struct QtlRings {
     static constexpr int IMG = JQ_T4_ELEMS(NT), PIECES = IMG / 128, SLOT_B = 2 * IMG * 8, RING_B = 3 * SLOT_B;
@@ -74,8 +76,9 @@ struct QtlRings {
         lds = ring + lane;
         lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)ring;
         lo16 = 16u * lane;
-        srcp = (const char*)a.stream;
-        srcd = (const char*)(a.stream + (size_t)(1 + blockIdx.y) * (size_t)a.stream_gstride);
+        // (the workgroup's quads belong to ONE member: a.group_units is a multiple of the quads per workgroup)
+        srcp = (const char*)jq_group_stream(a, (int)blockIdx.x * nwv_);
+        srcd = (const char*)jq_tl_dir_stream(a);
         wave = wave_, nwv = nwv_;
         issue(0, 0);
     }

@@ -323,6 +323,57 @@ def eval_f_g_grad_drifts(pcof, params, wa, Hconsts, weights, compute_adjoint=Tru
     return params.last_infidelity, params.last_leak
 
 
+def eval_f_g_grad_drifts_hvp(pcof, dirs, params, wa, drifts, weights):
+    """eval_f_g_grad_hvp over the members of a drift ensemble instead of over eps-nodes, in one library call
+    (jq_eval_f_g_grad_drifts_hvp): the weighted sums sum_i w_i of infidelity and leak, of the two gradients and of their derivatives
+    along the columns of dirs, member i being the evaluation with params.Hconst = drifts[:, :, i] (the members of eval_f_g_grad_drifts).
+    The routes are eval_f_g_grad_hvp's with a member where that call has a node: every wave reads the operator stream of its own member,
+    the members that the stream budget (option stream_bytes) has no room for follow in further member rounds.  A member outside the
+    structure the handle was planned for, and every problem whose nodes eval_f_g_grad_hvp runs one after the other, sends the members
+    one after the other (route "sequential"; wa.plan_info()["drift_hvp"] = {route, members_per_launch, directions_per_launch,
+    chunk_steps, rounds}).  The handle is never re-planned; params.Hconst, the handle's drift and params.last_* are left alone.
+
+    dirs: an ncoeff x ndir array (one direction per column) or a single vector; drifts: an Ntot x Ntot x ndrift array or a sequence
+    of Ntot x Ntot matrices; weights: one per member.  Returns the dict of eval_f_g_grad_hvp.  Not served: control mixes, members x
+    eps-nodes, sharding over devices.  Shape errors raise ValueError before any library call."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("eval_f_g_grad_drifts_hvp: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("eval_f_g_grad_drifts_hvp: wa was allocated for a different objparams")
+    ncoeff = int(wa.nCoeff)
+    try:
+        p = np.asarray(pcof, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("eval_f_g_grad_drifts_hvp: pcof must be a vector of numbers (%s)" % e)
+    if p.ndim != 1 or p.size != ncoeff:
+        raise ValueError("eval_f_g_grad_drifts_hvp: pcof has shape %r, expected (%d,) (wa.nCoeff)" % (p.shape, ncoeff))
+    H, w = _drift_ensemble(params, drifts, weights, "eval_f_g_grad_drifts_hvp")
+    D = _directions(dirs, ncoeff, "eval_f_g_grad_drifts_hvp")
+    p = _f64(p)
+    nd, nm = D.shape[0], H.shape[0]
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    out2 = np.zeros(2)
+    ig, lg = np.zeros(ncoeff), np.zeros(ncoeff)
+    hvi, hvl = np.zeros((nd, ncoeff)), np.zeros((nd, ncoeff))
+    _lib.check(L.jq_eval_f_g_grad_drifts_hvp(h, _ptr(p), ncoeff, _ptr(D), nd, _ptr(H), _ptr(w), nm, _ptr(out2), _ptr(ig), _ptr(lg), _ptr(hvi),
+                                             _ptr(hvl)), h)
+    return dict(infidelity=float(out2[0]), leak=float(out2[1]), infid_grad=ig, leak_grad=lg, hv_infid=np.ascontiguousarray(hvi.T),
+                hv_leak=np.ascontiguousarray(hvl.T))
+
+
+def eval_hessvec_drifts(pcof, d, params, wa, drifts, weights):
+    """eval_hessvec_par for a drift ensemble: the derivative along d of the ensemble's gradient (eval_grad_f_par with drifts=...), hv_infid
+    of eval_f_g_grad_drifts_hvp -- objFuncType == 1: the derivative of the total gradient -- plus the second derivative of the Tikhonov
+    term.  (setup_ipopt_problem(hessian="exact") does not take a drift ensemble; this is the callback for a caller's own trust-region loop.)"""
+    d = np.asarray(d, dtype=np.float64)
+    r = eval_f_g_grad_drifts_hvp(pcof, d, params, wa, drifts, weights)
+    hv = r["hv_infid"][:, 0]
+    if params.objFuncType == 1:
+        hv = hv + r["hv_leak"][:, 0]
+    return hv + tikhonov_hessvec(d, params.tik0)
+
+
 def eval_f_g_grad_members(pcof, params, wa, weights, Hconsts=None, ctrl_mix=None, compute_adjoint=True, per_member=False):
     """eval_f_g_grad_drifts over the members of traceobjgrad_members (jq_eval_f_g_grad_members): the weighted sums over members that differ
     in a real mixing matrix of the controls (ctrl_mix: Nc x Nc x nmember; amplitude_mix for miscalibrated amplitudes), in their drift
