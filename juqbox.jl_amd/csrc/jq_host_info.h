@@ -8,10 +8,25 @@ extern "C" int jq_set_option(jq_handle* h, const char* name, int64_t value)
     if (o < 0) return fail(h, JQ_EINVAL, (std::string("jq_set_option: unknown option '") + name + "'").c_str());
     const long long v = (value == JQ_OPTION_DEFAULT) ? JQ_OPT_UNSET : (long long)value;
     if (!h->subs.empty()) {
-        std::string err;
-        if (!h->opt.set(o, v, &err)) return fail(h, JQ_EUNSUPPORTED, ("jq_set_option: " + err).c_str());
+        // validate first (on a copy), apply to the sub-handles, commit h->opt only when every one of them accepted the value: after a
+        // refusal jq_get_option and jq_plan_info report what the sub-handles have
         if (o == O_MULTI_SAME_DEVICE) return fail(h, JQ_EINVAL, "jq_set_option: multi_same_device is an option of jq_create_multi_opts");
-        return multi_forall(h, [&](jq_handle* sub) { return jq_set_option(sub, name, value); });
+        JqOptions want = h->opt;
+        std::string err;
+        if (!want.set(o, v, &err)) return fail(h, JQ_EUNSUPPORTED, ("jq_set_option: " + err).c_str());
+        const long long old = h->opt.v[o];
+        const int64_t old_value = (old == JQ_OPT_UNSET) ? JQ_OPTION_DEFAULT : (int64_t)old;
+        const int rc = multi_forall(h, [&](jq_handle* sub) { return jq_set_option(sub, name, value); });
+        if (rc != JQ_OK) {      // nothing half-applied: the sub-handles that took the value get the old one back
+            std::string why = h->err;
+            // (a restore that fails itself -- a re-plan back that runs out of memory -- leaves that sub-handle on the new value: said in the message)
+            if (multi_forall(h, [&](jq_handle* sub) { return jq_set_option(sub, name, old_value); }) != JQ_OK)
+                why += " (and restoring the old value on the devices failed: " + h->err + "; destroy this handle)";
+            h->err = why;
+            return rc;
+        }
+        h->opt = want;
+        return JQ_OK;
     }
     const long long old = h->opt.v[o];
     if (old == v) return JQ_OK;
