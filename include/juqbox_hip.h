@@ -50,7 +50,9 @@ extern "C" {
  *     directions of coefficient space: the reference's verbose && evaladjoint forward-sensitivity sweep), jq_traceobjgrad_hvp (the
  *     derivative of the gradient along directions of coefficient space: Hessian-vector products), jq_eval_f_g_grad_hvp (the same for
  *     the two gradients of a risk-neutral ensemble: the nodes in the lanes, the directions in the grid), jq_eval_f_g_grad_drifts_hvp (the
- *     same for an ensemble of arbitrary drift Hamiltonians: every wave reads the operator stream of its own member). */
+ *     same for an ensemble of arbitrary drift Hamiltonians: every wave reads the operator stream of its own member),
+ *     jq_eval_f_g_grad_members_hvp (the same for members with a control mix as well: every wave reads the tangent stream of its own
+ *     member too). */
 #define JQ_ABI_VERSION 6
 
 #define JQ_MAX_CONTROLS 16 /* control Hamiltonians the fast kernels hold in registers; more: cooperative kernels (no limit)    */
@@ -454,12 +456,44 @@ int jq_eval_f_g_grad_hvp(jq_handle *h, const double *pcof, int32_t ncoeff, const
  * direction rounds x member rounds); "ens_hvp", "hvp" and "drift_batch" keep the values of their own calls.  jq_last_timing and
  * "last_kernels" as jq_eval_f_g_grad_hvp.  Refused with JQ_EUNSUPPORTED: what that call refuses.  JQ_EINVAL for NULL pointers (all are
  * required), ndir < 1 or ndrift < 1; the codes of jq_traceobjgrad for the coefficient count.  A refused call writes nothing and leaves
- * the handle as it was.  Multi-device handles run the call on their first device.  Not served: control mixes, members x eps-nodes,
- * sharding over devices.
+ * the handle as it was.  Multi-device handles run the call on their first device.  Not served: members x eps-nodes, sharding over
+ * devices; control mixes: jq_eval_f_g_grad_members_hvp.
  */
 int jq_eval_f_g_grad_drifts_hvp(jq_handle *h, const double *pcof, int32_t ncoeff, const double *dirs, int32_t ndir, const double *drifts,
                                 const double *weights, int32_t ndrift, double *out2, double *infid_grad, double *leak_grad,
                                 double *hv_infid, double *hv_leak);
+
+/*
+ * jq_eval_f_g_grad_drifts_hvp over the members of jq_traceobjgrad_members / jq_eval_f_g_grad_members: member i has the drift
+ * Hconsts[:, :, i] and the control mix ctrl_mix[:, :, i] -- an amplitude miscalibration or crosstalk between control lines.
+ *   dirs     : [ncoeff x ndir] column-major, one direction per column
+ *   Hconsts  : [Ntot x Ntot x nmember] column-major member drifts, or NULL: every member has the handle's drift
+ *   ctrl_mix : [Nc x Nc x nmember] column-major real mixing matrices, or NULL: every member has the identity mix.  Operator l of member i
+ *              is driven by sum_k C_i[l, k] (p_k, q_k); every control keeps its own carriers and coefficients
+ *   weights  : [nmember]
+ *   out2, infid_grad, leak_grad, hv_infid, hv_leak : as jq_eval_f_g_grad_hvp -- hv_infid the derivative of infid_grad, hv_leak that of
+ *              leak_grad (objFuncType 1: leak_grad and hv_leak are zeros), no Tikhonov term, not symmetrised
+ * Without a mix (ctrl_mix == NULL) the call IS jq_eval_f_g_grad_drifts_hvp: the same launches, the same bits.  With one, routes and
+ * packing stay that call's -- a mix never changes the route, operators and structure are the handle's -- but the tangent stream of a
+ * direction is no longer shared by the members: member i differentiates along sum_l (C_i d_j)_l H_l, so a member brings 1 + D streams into a
+ * launch of D directions, and as many members share a launch as the stream budget (option stream_bytes) has room for at that price; the
+ * others follow in further member rounds.  The traces of a member are reduced with its mix into a gradient block of its own and the
+ * blocks are added in member order: one member with the identity mix gives the bits of jq_eval_f_g_grad_drifts_hvp with that member,
+ * members of weight zero change no bit, and a column of zeros in every mix gives exactly zero blocks for that control.  Where that
+ * call runs its members one after the other (route "sequential": a member drift outside the plan, Ntot 7 or 8, options lane=0 / quad=0,
+ * more than four controls, ...) so does this one, every member with its mix.  The call never re-plans the handle and never touches its
+ * drift or operator images.  jq_plan_info "member_hvp": {route: "lane" | "rowlane" | "quad" | "sequential", members_per_launch,
+ * directions_per_launch, chunk_steps, rounds (direction rounds x member rounds), drifts: were member drifts given, ctrl_mix: were mixes
+ * given}, present after a call; "drift_hvp", "ens_hvp", "hvp" and "member_batch" keep the values of their own calls.  jq_last_timing
+ * and "last_kernels" as jq_eval_f_g_grad_hvp.  Refused with JQ_EUNSUPPORTED: what that call refuses.  JQ_EINVAL for NULL pointers (all
+ * but Hconsts and ctrl_mix are required; both NULL is the plain problem: jq_eval_f_g_grad_hvp with one node), a mix entry that is not
+ * finite, ndir < 1 or nmember < 1; the codes of jq_traceobjgrad for the coefficient count.  A refused call writes nothing and leaves
+ * the handle as it was.  Multi-device handles run the call on their first device.  Not served: members x eps-nodes, sharding over
+ * devices.
+ */
+int jq_eval_f_g_grad_members_hvp(jq_handle *h, const double *pcof, int32_t ncoeff, const double *dirs, int32_t ndir, const double *Hconsts,
+                                 const double *ctrl_mix, const double *weights, int32_t nmember, double *out2, double *infid_grad,
+                                 double *leak_grad, double *hv_infid, double *hv_leak);
 
 /*
  * Device-side consumers of the state history, so that the [Ntot x N x (nsteps+1)] arrays (199 MB at cnot3)

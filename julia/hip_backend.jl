@@ -390,6 +390,36 @@ function eval_f_g_grad_drifts_hvp(pcof::Vector{Float64}, dirs::VecOrMat{Float64}
     return (infidelity = out2[1], leak = out2[2], infid_grad = ig, leak_grad = lg, hv_infid = hvi, hv_leak = hvl)
 end
 
+# eval_f_g_grad_drifts_hvp over the members of eval_f_g_grad_members! (jq_eval_f_g_grad_members_hvp): members that differ in a real
+# Nc x Nc mixing matrix of the controls (ctrl_mix; operator l is driven by sum_k C[l, k] (p_k, q_k)), in their drift (Hconsts), or in both;
+# `nothing` for either means the handle's drift / the identity mix, ctrl_mix === nothing is eval_f_g_grad_drifts_hvp bit for bit.  With
+# mixes every wave reads the tangent stream of its own member as well (jq_plan_info "member_hvp").  The handle's drift and plan are left
+# alone.  Returns what eval_f_g_grad_hvp returns.
+function eval_f_g_grad_members_hvp(pcof::Vector{Float64}, dirs::VecOrMat{Float64}, params::objparams, wa::AbstractWorkingArraysHIP,
+                                   Hconsts::Union{Nothing,Array{Float64,3}}, ctrl_mix::Union{Nothing,Array{Float64,3}}, weights::Vector{Float64})
+    ncoeff = length(pcof)
+    D = dirs isa Vector ? reshape(dirs, :, 1) : Matrix{Float64}(dirs)
+    size(D, 1) == ncoeff || throw(DimensionMismatch("eval_f_g_grad_members_hvp: dirs must have length(pcof) rows"))
+    nd = size(D, 2)
+    nd >= 1 || throw(ArgumentError("eval_f_g_grad_members_hvp: need at least one direction"))
+    Ntot = params.N + params.Nguard
+    Nc = max(params.Ncoupled, params.Nunc)
+    (Hconsts === nothing && ctrl_mix === nothing) && throw(ArgumentError("eval_f_g_grad_members_hvp: give Hconsts, ctrl_mix or both"))
+    nm = ctrl_mix === nothing ? size(Hconsts, 3) : size(ctrl_mix, 3)
+    nm >= 1 || throw(ArgumentError("eval_f_g_grad_members_hvp: need at least one member"))
+    Hconsts === nothing || (size(Hconsts) == (Ntot, Ntot, nm)) || throw(DimensionMismatch("eval_f_g_grad_members_hvp: Hconsts must be Ntot x Ntot x nmember"))
+    ctrl_mix === nothing || (size(ctrl_mix) == (Nc, Nc, nm)) || throw(DimensionMismatch("eval_f_g_grad_members_hvp: ctrl_mix must be Nc x Nc x nmember"))
+    length(weights) == nm || throw(ArgumentError("eval_f_g_grad_members_hvp: need one weight per member"))
+    sync!(wa, params)
+    out2 = zeros(2); ig = zeros(ncoeff); lg = zeros(ncoeff); hvi = zeros(ncoeff, nd); hvl = zeros(ncoeff, nd)
+    jqcheck(wa, ccall((:jq_eval_f_g_grad_members_hvp, libjq), Cint,
+                      (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64},
+                       Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                      wa.handle, pcof, ncoeff, D, nd, Hconsts === nothing ? C_NULL : pointer(Hconsts),
+                      ctrl_mix === nothing ? C_NULL : pointer(ctrl_mix), weights, nm, out2, ig, lg, hvi, hvl))
+    return (infidelity = out2[1], leak = out2[2], infid_grad = ig, leak_grad = lg, hv_infid = hvi, hv_leak = hvl)
+end
+
 # All unit directions through one traceobjgrad_hvp call: the ncoeff x ncoeff Jacobian of totalgrad, (J + J')/2 with symmetrize.
 function hessian(pcof::Vector{Float64}, params::objparams, wa::AbstractWorkingArraysHIP, symmetrize::Bool = false)
     J = traceobjgrad_hvp(pcof, Matrix{Float64}(LinearAlgebra.I, length(pcof), length(pcof)), params, wa).hv

@@ -95,6 +95,7 @@ SYMBOLS = {
     "jq_traceobjgrad_hvp": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_i32, c_dp, c_i32, c_dp, c_dp, c_dp, c_dp]),
     "jq_eval_f_g_grad_hvp": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_i32, c_dp, c_i32, c_dp, c_dp, c_i32, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "jq_eval_f_g_grad_drifts_hvp": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_i32, c_dp, c_i32, c_dp, c_dp, c_i32, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "jq_eval_f_g_grad_members_hvp": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_i32, c_dp, c_i32, c_dp, c_dp, c_dp, c_i32, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "jq_last_timing": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(jq_timing)]),
     "jq_version": (ctypes.c_char_p, []),
     "jq_abi_version": (ctypes.c_int, []),

@@ -29,6 +29,13 @@
 // Members beyond the stream budget run in further member rounds that accumulate into the same gradient blocks, in member order.  A
 // member outside the structure the handle was planned for (hconst_fits_plan) sends the whole call down the sequential route: the call
 // never re-plans the handle and never touches its operator images.
+//
+// jq_eval_f_g_grad_members_hvp -- members that differ in a real Nc x Nc mix of the controls as well (operator l is driven by
+// sum_k C_i[l, k] (p_k, q_k)), with or without a drift of their own.  Without a mix it IS the drift ensemble above.  With one the tangent
+// stream of a direction is no longer shared: member i differentiates along sum_l (C_i d_j)_l H_l, so a member brings 1 + dpl streams
+// ([member 0 .. P - 1 | member 0: direction ... | member 1: ...], PropArgs::tl_dirs_per_member), k_ctrl mixes every stream with the mix of
+// its member, and the traces of a member are reduced apart with its mix (k_trace_reduce) into gradient blocks of their own, which the
+// host adds in member order.  A mix never changes the route: operators and structure are the handle's.
 static double ens_hvp_shift(const double* shift, int i) { return shift ? shift[i] : (i >= 1 ? 0.01 * pow(10.0, (double)(i - 1)) : 0.0); }
 
 struct EnsHvpArgs {
@@ -37,6 +44,8 @@ struct EnsHvpArgs {
     const double* drifts;       // NULL: nquad eps-nodes (nodes, shift); else HOST [Ntot x Ntot x nquad] member drifts (nodes, shift unused)
     int ncoeff, ndir, nquad;    // nquad: samples -- nodes or members
     double *out2, *infid_grad, *leak_grad, *hv_infid, *hv_leak;
+    const double* mix = nullptr;      // HOST [Nc x Nc x nquad] control mixes of the members (NULL: none); with drifts == NULL the members have the handle's drift
+    bool member_call = false;         // jq_eval_f_g_grad_members_hvp runs: the call is recorded as "member_hvp" of jq_plan_info, not as "drift_hvp"
 };
 // the four outputs from the forced (g0, v0) and unforced (g1, v1; objFuncType != 1 only) gradients and products (out_grads' rule)
 static void ens_hvp_outputs(const jq_handle* h, const EnsHvpArgs& x, const double* g0, const double* g1, const double* v0, const double* v1)
@@ -87,8 +96,8 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
     const char* who = x.who;
     HIPCHK(h, hipSetDevice(h->device));
     const int Nc = h->Nc, ncoeff = x.ncoeff, ndir = x.ndir, nquad = x.nquad, ntr = Nc * JQ_NTR;
-    const bool members = x.drifts != nullptr;
-    const size_t stride = lay.stride, nn = (size_t)h->Ntot * h->Ntot;
+    const bool members = x.drifts != nullptr || x.mix != nullptr, mixed = x.mix != nullptr;
+    const size_t stride = lay.stride, nn = (size_t)h->Ntot * h->Ntot, ncnc = (size_t)Nc * Nc;
     // What a sample is.  wps: the waves that read one primal stream -- all the waves of the packed node columns, or a member's ceil(N / cpw)
     // padded to whole workgroups of the sweep kernels; gcols: the columns in front of such a group of wps cpw column slots.
     const long long gcols = members ? h->N : (long long)nquad * h->N;
@@ -98,9 +107,11 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
     const double dt = h->T / h->nsteps;
     const bool two_pass = h->objFuncType != 1;
     const int npass = two_pass ? 2 : 1;
-    const TlBudget b = tl_budget(h, stride, ndir, JQ_JVP_MAX_DIRS, (size_t)wps * ntr, members ? nquad : 1);      // (the directions are a grid dimension of their own)
+    const TlBudget b = tl_budget(h, stride, ndir, JQ_JVP_MAX_DIRS, (size_t)wps * ntr, members ? nquad : 1, mixed);      // (the directions are a grid dimension of their own)
     // P primal streams (members) and spl samples per launch, mrounds launches per direction round; ngb gradient blocks [primal | direction ...]
-    const int dpl = b.dpl, cs = b.cs, rounds = b.rounds, P = b.mpl, mrounds = b.mrounds, nvec = P + dpl, ngb = 1 + dpl;
+    // (mixed: every member its own direction streams and its own gradient blocks, ndb of them, folded into the ngb on the host)
+    const int dpl = b.dpl, cs = b.cs, rounds = b.rounds, P = b.mpl, mrounds = b.mrounds, nvec = mixed ? P * (1 + dpl) : P + dpl, ngb = 1 + dpl;
+    const int ndb = mixed ? P * ngb : ngb, PR = mixed ? P : 1;
     const int spl = members ? P : nquad, nwaves = P * wps;
     const long long ncols = (long long)nwaves * lay.cpw;
     const size_t sstride = (size_t)lay.state_rows * (size_t)nwaves * 64;      // doubles of one direction's state file
@@ -108,13 +119,26 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
     // tables [wd | ws]; per member round the column info [eps | weight] per column slot (run_eval's for the layout) and the drift images
     // of its members in the route's layout (the builders and the bits of upload_operators' image 0; a short last round repeats its last
     // member with weight 0: every group has a stream)
-    std::vector<double> tabs((size_t)2 * lay.tab_off, 0.0), colinfo((size_t)mrounds * 2 * ncols, 0.0), mimg(members ? (size_t)mrounds * P * stride : 0, 0.0);
+    // mixed: per member round k_ctrl's mixes [C_0 .. C_{P - 1} | C_0 x dpl | C_1 x dpl | ...] and behind them the reducer's for the tangent
+    // records [C_0 .. C_{P - 1}] x dpl (its primal ones are the first P of k_ctrl's), nmix matrices in all
+    const size_t nmix = (size_t)nvec + (size_t)dpl * P;
+    std::vector<double> tabs((size_t)2 * lay.tab_off, 0.0), colinfo((size_t)mrounds * 2 * ncols, 0.0), mimg(x.drifts ? (size_t)mrounds * P * stride : 0, 0.0);
+    std::vector<double> mixtab(mixed ? (size_t)mrounds * nmix * ncnc : 0);
     bool use_shift = false;
     for (int i = 0; i < h->Ntot; ++i) tabs[i] = h->wd[i], tabs[lay.tab_off + i] = ens_hvp_shift(x.shift, i);
     for (int mr = 0; mr < mrounds; ++mr)
         for (int sl = 0; sl < spl; ++sl) {
             const int smp = mr * spl + sl;
-            if (members) {
+            if (mixed) {
+                const double* C = x.mix + ncnc * std::min(smp, nquad - 1);
+                double* t = mixtab.data() + (size_t)mr * nmix * ncnc;
+                std::copy_n(C, ncnc, t + sl * ncnc);
+                for (int j = 0; j < dpl; ++j) {
+                    std::copy_n(C, ncnc, t + ((size_t)P + (size_t)sl * dpl + j) * ncnc);
+                    std::copy_n(C, ncnc, t + ((size_t)nvec + (size_t)j * P + sl) * ncnc);
+                }
+            }
+            if (x.drifts) {
                 const double* M = x.drifts + nn * std::min(smp, nquad - 1);
                 double* img = mimg.data() + ((size_t)mr * P + sl) * stride;
                 if (lay.route == 1) plain_image(M, h->Ntot, lay.size, img);
@@ -129,32 +153,36 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
                 if (!members && x.nodes[smp] != 0.0) use_shift = true;
             }
         }
-    DevBuf d_h0, d_pc, d_pq, d_stream, d_state, d_save, d_tabs, d_col, d_res, d_tr, d_R, d_g;
+    DevBuf d_h0, d_pc, d_pq, d_stream, d_state, d_save, d_tabs, d_col, d_res, d_tr, d_R, d_g, d_mix, d_raw;
     int rc;
     if ((rc = d_h0.alloc(h, who, (size_t)nvec * stride)) || (rc = d_pc.alloc(h, who, (size_t)nvec * ncoeff)) ||
         (rc = d_pq.alloc(h, who, (size_t)nvec * (2 * cs + 1) * 2 * Nc)) || (rc = d_stream.alloc(h, who, (size_t)nvec * b.gstride)) ||
         (rc = d_state.alloc(h, who, (size_t)dpl * sstride)) || (rc = d_save.alloc(h, who, two_pass ? (size_t)dpl * sstride : 1)) ||
         (rc = d_tabs.alloc(h, who, tabs.size())) || (rc = d_col.alloc(h, who, (size_t)2 * ncols)) || (rc = d_res.alloc(h, who, (size_t)dpl * spl * 4)) ||
-        (rc = d_tr.alloc(h, who, (size_t)2 * dpl * nwaves * cs * ntr)) || (rc = d_R.alloc(h, who, (size_t)ngb * cs * ntr)) ||
-        (rc = d_g.alloc(h, who, (size_t)2 * ngb * ncoeff)))
+        (rc = d_tr.alloc(h, who, (size_t)2 * dpl * nwaves * cs * ntr)) || (rc = d_R.alloc(h, who, (size_t)ndb * cs * ntr)) ||
+        (rc = d_g.alloc(h, who, (size_t)2 * ndb * ncoeff)) ||
+        (mixed && ((rc = d_mix.alloc(h, who, nmix * ncnc)) || (rc = d_raw.alloc(h, who, (size_t)nvec * (2 * cs + 1) * 2 * Nc)))))
         return rc;
-    // d_g: [pass][primal | direction ...][ncoeff]
+    // d_g: [pass][primal | direction ...][ncoeff]; mixed: [pass][member 0 .. P - 1 | direction 0: member 0 .. P - 1 | ...][ncoeff] (tl_reduce_chunk)
     hipStream_t s = h->stream;
     HIPCHK(h, hipMemsetAsync(d_h0.p, 0, (size_t)nvec * stride * sizeof(double), s));
-    if (!members) HIPCHK(h, hipMemcpyAsync(d_h0.p, lay.himg, stride * sizeof(double), hipMemcpyDeviceToDevice, s));
+    // (the handle's own image 0: the one primal stream of the eps ensemble, or once per member of an ensemble of mixes alone)
+    for (int g = 0; g < (members ? P : 1) && !x.drifts; ++g) HIPCHK(h, hipMemcpyAsync(d_h0.p + (size_t)g * stride, lay.himg, stride * sizeof(double), hipMemcpyDeviceToDevice, s));
     HIPCHK(h, hipMemcpyAsync(d_tabs.p, tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice, s));
     // the samples of member round mr: column info, drift images [H_0 .. H_{P - 1} | 0 ...]
     const auto upload_samples = [&](int mr) -> int {
         HIPCHK(h, hipMemcpyAsync(d_col.p, colinfo.data() + (size_t)mr * 2 * ncols, (size_t)2 * ncols * sizeof(double), hipMemcpyHostToDevice, s));
-        if (members) HIPCHK(h, hipMemcpyAsync(d_h0.p, mimg.data() + (size_t)mr * P * stride, (size_t)P * stride * sizeof(double), hipMemcpyHostToDevice, s));
+        if (x.drifts) HIPCHK(h, hipMemcpyAsync(d_h0.p, mimg.data() + (size_t)mr * P * stride, (size_t)P * stride * sizeof(double), hipMemcpyHostToDevice, s));
+        if (mixed) HIPCHK(h, hipMemcpyAsync(d_mix.p, mixtab.data() + (size_t)mr * nmix * ncnc, nmix * ncnc * sizeof(double), hipMemcpyHostToDevice, s));
         return JQ_OK;
     };
     if (mrounds == 1 && (rc = upload_samples(0))) return rc;
 
-    const TlGen gen = {tl_spline(h, d_pc.p, ncoeff, nullptr), lay.himg, d_h0.p, d_pq.p, d_stream.p, stride, b.gstride, nvec};
+    const TlGen gen = {tl_spline(h, d_pc.p, ncoeff, nullptr), lay.himg, d_h0.p, d_pq.p, d_stream.p, stride, b.gstride, nvec, d_mix.p, d_raw.p};
+    const TlMix mx = {d_mix.p, d_mix.p + (size_t)nvec * ncnc, P};
     PropArgs a;
     memset(&a, 0, sizeof a);
-    a.stream = d_stream.p; a.stream_gstride = (long long)b.gstride; a.group_units = wps; a.nprimal = P; a.state = d_state.p; a.state_stride = (long long)sstride;
+    a.stream = d_stream.p; a.stream_gstride = (long long)b.gstride; a.group_units = wps; a.nprimal = P; a.tl_dirs_per_member = mixed ? 1 : 0; a.state = d_state.p; a.state_stride = (long long)sstride;
     a.colinfo = d_col.p; a.tabs = d_tabs.p; a.traces = d_tr.p; a.cimg = lay.cimg; a.stride = (long long)stride; a.m = h->m; a.nslabs = lay.slabs_are_waves ? nwaves : (int)ncols;
     a.Ncoupled = Nc; a.Ntot = h->Ntot; a.N = h->N; a.parts = 1; a.nsamples = spl; a.sps = 1; a.tinv = 1.0 / h->T; a.use_shift = use_shift ? 1 : 0;
     for (int q = 0; q < JQ_MAXNC && lay.modes; ++q) a.bw_trace[q] = q < Nc ? h->bw_trace[q] : 0;
@@ -163,7 +191,7 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
 
     LaunchTimer tm{h};
     if ((rc = tm.start((size_t)b.nchunks * rounds * mrounds * (1 + npass)))) return rc;
-    std::vector<double> res((size_t)nquad * 4), blk((size_t)nvec * ncoeff), gbuf((size_t)2 * ngb * ncoeff);
+    std::vector<double> res((size_t)nquad * 4), blk((size_t)nvec * ncoeff), gbuf((size_t)2 * ndb * ncoeff), fold(mixed ? (size_t)2 * ngb * ncoeff : 0);
     std::vector<double> g0(ncoeff), g1(two_pass ? ncoeff : 0), v0((size_t)ncoeff * ndir), v1(two_pass ? (size_t)ncoeff * ndir : 0);
     const dim3 grid((unsigned)nwaves, (unsigned)dpl);
     // the sweep kernels: wpg consecutive waves of a direction per workgroup (1 on the lane and row-lane routes: the launch it always was)
@@ -198,12 +226,14 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
         }
     };
     // rounds of dpl directions; within one, mrounds launches of P members each accumulate into the round's gradient blocks, in member order
+    // (mixed: every launch has fresh per-member blocks, which the host adds to the round's in member order)
     for (int it = 0; it < rounds * mrounds; ++it) {
         const int r = it / mrounds, mr = it % mrounds, j0 = r * dpl, nd = std::min(dpl, ndir - j0);
         if (mr == 0) {
-            if ((rc = tl_upload_round(h, blk, d_pc.p, x.pcof, x.dirs, j0, nd, dpl, ncoeff, P))) return rc;
-            HIPCHK(h, hipMemsetAsync(d_g.p, 0, (size_t)2 * ngb * ncoeff * sizeof(double), s));
+            if ((rc = tl_upload_round(h, blk, d_pc.p, x.pcof, x.dirs, j0, nd, dpl, ncoeff, P, mixed))) return rc;
+            std::fill(fold.begin(), fold.end(), 0.0);
         }
+        if (mr == 0 || mixed) HIPCHK(h, hipMemsetAsync(d_g.p, 0, (size_t)2 * ndb * ncoeff * sizeof(double), s));
         if (mrounds > 1 && (rc = upload_samples(mr))) return rc;
         // ---- forward sweep of (state, tangent) ----
         endpoint(true);
@@ -232,14 +262,17 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
                 if ((rc = tm.begin(true))) return rc;
                 hipLaunchKernelGGL(kbwd, sgrid, sblock, lay.lds_bwd, s, a);
                 if ((rc = tm.end())) return rc;
-                tl_reduce_chunk(h, gen.sp, r == 0, d_tr.p, nwaves, dpl, n0, nc, 0, Nc, d_R.p, d_R.p + (size_t)cs * ntr, d_g.p + (size_t)pass * ngb * ncoeff);
+                tl_reduce_chunk(h, gen.sp, r == 0, d_tr.p, mixed ? wps : nwaves, dpl, n0, nc, 0, Nc, d_R.p, d_R.p + (size_t)PR * cs * ntr, d_g.p + (size_t)pass * ndb * ncoeff,
+                                mixed ? &mx : nullptr);
             }
         }
         HIPCHK(h, hipGetLastError());
-        if (mr < mrounds - 1) continue;
+        if (mr < mrounds - 1 && !mixed) continue;
         HIPCHK(h, hipMemcpyAsync(gbuf.data(), d_g.p, gbuf.size() * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));      // (the host blocks are reused by the next round)
-        tl_copy_out(gbuf, ngb, ncoeff, two_pass, r == 0, j0, nd, g0.data(), two_pass ? g1.data() : nullptr, v0.data(), two_pass ? v1.data() : nullptr);
+        if (mixed) tl_fold_members(gbuf, fold, npass, P, std::min(P, nquad - mr * P), dpl, ncoeff);
+        if (mr < mrounds - 1) continue;
+        tl_copy_out(mixed ? fold : gbuf, ngb, ncoeff, two_pass, r == 0, j0, nd, g0.data(), two_pass ? g1.data() : nullptr, v0.data(), two_pass ? v1.data() : nullptr);
     }
     if ((rc = tm.stop())) return rc;
     double inf = 0.0, leak = 0.0;
@@ -249,7 +282,9 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
     }
     x.out2[0] = inf, x.out2[1] = leak;
     ens_hvp_outputs(h, x, g0.data(), g1.data(), v0.data(), v1.data());
-    if (members) h->drift_hvp_route = lay.route, h->drift_hvp_members = P, h->drift_hvp_per_launch = dpl, h->drift_hvp_chunk = cs, h->drift_hvp_rounds = rounds * mrounds;
+    if (x.member_call)
+        h->member_hvp = {lay.route, P, dpl, cs, rounds * mrounds, x.drifts != nullptr, mixed};
+    else if (members) h->drift_hvp_route = lay.route, h->drift_hvp_members = P, h->drift_hvp_per_launch = dpl, h->drift_hvp_chunk = cs, h->drift_hvp_rounds = rounds * mrounds;
     else h->ens_hvp_route = lay.route, h->ens_hvp_per_launch = dpl, h->ens_hvp_chunk = cs, h->ens_hvp_rounds = rounds;
 
     if ((rc = tm.finish(lay.label))) return rc;
@@ -275,10 +310,11 @@ static int ens_hvp_sequential(jq_handle* h, const EnsHvpArgs& x)
     for (int i = 0; i < x.nquad && rc == JQ_OK; ++i) {
         if (x.drifts) drift.assign(x.drifts + (size_t)i * Ntot * Ntot, x.drifts + (size_t)(i + 1) * Ntot * Ntot);      // member i
         else {
-            drift = h->Hconst;
-            for (int j = 0; j < Ntot; ++j) drift[(size_t)j * Ntot + j] += x.nodes[i] * ens_hvp_shift(x.shift, j);      // src/ipopt_interface.jl:41-44
+            drift = h->Hconst;      // (a member of an ensemble of mixes alone: the handle's drift)
+            for (int j = 0; j < Ntot && !x.mix; ++j) drift[(size_t)j * Ntot + j] += x.nodes[i] * ens_hvp_shift(x.shift, j);      // src/ipopt_interface.jl:41-44
         }
-        rc = hvp_run(h, drift.data(), x.pcof, ncoeff, x.dirs, ndir, out4, gi.data(), vi.data(), vin.data(), gin.data(), x.who);
+        rc = hvp_run(h, drift.data(), x.pcof, ncoeff, x.dirs, ndir, out4, gi.data(), vi.data(), vin.data(), gin.data(), x.who,
+                     x.mix ? x.mix + (size_t)i * h->Nc * h->Nc : nullptr);
         if (rc != JQ_OK) break;
         const double w = x.weights[i];
         inf += out4[1] * w, leak += out4[2] * w;
@@ -301,7 +337,8 @@ static int ens_hvp_sequential(jq_handle* h, const EnsHvpArgs& x)
     ens_hvp_outputs(h, x, g0.data(), g1.data(), v0.data(), v1.data());
     h->timing = sum;
     h->timing.ms_shard_min = h->timing.ms_shard_max = h->timing.ms_total;
-    if (x.drifts) h->drift_hvp_route = 2, h->drift_hvp_members = 1, h->drift_hvp_per_launch = dpl, h->drift_hvp_chunk = cs, h->drift_hvp_rounds = rounds;
+    if (x.member_call) h->member_hvp = {2, 1, dpl, cs, rounds, x.drifts != nullptr, x.mix != nullptr};
+    else if (x.drifts) h->drift_hvp_route = 2, h->drift_hvp_members = 1, h->drift_hvp_per_launch = dpl, h->drift_hvp_chunk = cs, h->drift_hvp_rounds = rounds;
     else h->ens_hvp_route = 2, h->ens_hvp_per_launch = dpl, h->ens_hvp_chunk = cs, h->ens_hvp_rounds = rounds;
     return JQ_OK;
 }
@@ -375,5 +412,24 @@ extern "C" int jq_eval_f_g_grad_drifts_hvp(jq_handle* h, const double* pcof, int
         EvalGate gate(h);
         return ens_hvp_dispatch(h, {"jq_eval_f_g_grad_drifts_hvp", pcof, dirs, nullptr, weights, nullptr, drifts, ncoeff, ndir, ndrift, out2, infid_grad, leak_grad, hv_infid,
                                  hv_leak});
+    });
+}
+
+extern "C" int jq_eval_f_g_grad_members_hvp(jq_handle* h, const double* pcof, int32_t ncoeff, const double* dirs, int32_t ndir, const double* Hconsts,
+                                            const double* ctrl_mix, const double* weights, int32_t nmember, double* out2, double* infid_grad,
+                                            double* leak_grad, double* hv_infid, double* hv_leak)
+{
+    if (!h) return JQ_EINVAL;
+    return abi_guard(h, "jq_eval_f_g_grad_members_hvp", [&]() -> int {
+        if (!dirs || !weights || !infid_grad || !leak_grad || !hv_infid || !hv_leak) return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_members_hvp: NULL pointer");
+        if (int rc = members_args(h, "jq_eval_f_g_grad_members_hvp", false, pcof, Hconsts, ctrl_mix, nmember, out2)) return rc;      // (jq_eval_f_g_grad_members' rules)
+        if (ndir < 1) return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_members_hvp: ndir must be >= 1");
+        JQ_ON_FIRST(h, jq_eval_f_g_grad_members_hvp(s0_, pcof, ncoeff, dirs, ndir, Hconsts, ctrl_mix, weights, nmember, out2, infid_grad, leak_grad, hv_infid, hv_leak))
+        if (int rc = tl_refuse(h, "jq_eval_f_g_grad_members_hvp", true)) return rc;
+        if (int rc = check_ncoeff(h, ncoeff)) return rc;
+        EvalGate gate(h);
+        EnsHvpArgs x = {"jq_eval_f_g_grad_members_hvp", pcof, dirs, nullptr, weights, nullptr, Hconsts, ncoeff, ndir, nmember, out2, infid_grad, leak_grad, hv_infid, hv_leak};
+        x.mix = ctrl_mix, x.member_call = true;
+        return ens_hvp_dispatch(h, x);
     });
 }

@@ -12,9 +12,11 @@
 // sweep from the saved terminal state.  The backward work area and state file are about twice the forward's.
 // drift: the Ntot x Ntot drift Hamiltonian of the sweeps (column-major; jq_traceobjgrad_hvp: the handle's, jq_eval_f_g_grad_hvp's sequential
 // route: a node's).  grad_infid (may be NULL): the gradient of the unforced pass where there is one, else the gradient.  who: the entry
-// point that runs.
+// point that runs.  mix (may be NULL; jq_eval_f_g_grad_members_hvp's sequential route: a member's): the HOST Nc x Nc control mix, column-major --
+// operator l is driven by sum_k C[l, k] (p_k, q_k), in the primal stream and in every direction's; k_ctrl and the reducer see it, the
+// operators stay the handle's.  A control group's sweep then contributes to the coefficients of ALL controls (k_trace_reduce's q0).
 static int hvp_run(jq_handle* h, const double* drift, const double* pcof, int ncoeff, const double* dirs, int ndir, double* out4, double* grad, double* hv,
-                   double* hv_infid, double* grad_infid = nullptr, const char* who = "jq_traceobjgrad_hvp")
+                   double* hv_infid, double* grad_infid = nullptr, const char* who = "jq_traceobjgrad_hvp", const double* mix = nullptr)
 {
     HIPCHK(h, hipSetDevice(h->device));
     const int NT = (h->Ntot + 15) / 16, KT = 4 * NT, Nc = h->Nc, parts = h->parts;
@@ -40,20 +42,28 @@ static int hvp_run(jq_handle* h, const double* drift, const double* pcof, int nc
     }
     std::vector<double> wd((size_t)16 * NT, 0.0);
     std::copy(h->wd.begin(), h->wd.begin() + h->Ntot, wd.begin());
-    DevBuf d_img, d_cimg, d_h0, d_pc, d_pq, d_stream, d_state, d_save, d_work, d_wd, d_res, d_tr, d_R, d_g;
+    DevBuf d_img, d_cimg, d_h0, d_pc, d_pq, d_stream, d_state, d_save, d_work, d_wd, d_res, d_tr, d_R, d_g, d_mix, d_raw;
+    const int ntr_R = mix ? Nc * JQ_NTR : ntr_max;      // a reduced record's doubles per step
     int rc;
     if ((rc = d_img.alloc(h, who, img.size())) || (rc = d_cimg.alloc(h, who, cimg.size())) || (rc = d_h0.alloc(h, who, (size_t)nvec * stride)) ||
         (rc = d_pc.alloc(h, who, (size_t)nvec * ncoeff)) || (rc = d_pq.alloc(h, who, (size_t)nvec * (2 * cs + 1) * 2 * Nc)) ||
         (rc = d_stream.alloc(h, who, (size_t)nvec * b.gstride)) || (rc = d_state.alloc(h, who, (size_t)nblocks * sstride)) ||
         (rc = d_save.alloc(h, who, nsweeps > 1 ? (size_t)nblocks * sstride : 1)) || (rc = d_work.alloc(h, who, (size_t)nblocks * JQ_TLB_WORK_VECS * KT * 64)) ||
         (rc = d_wd.alloc(h, who, wd.size())) || (rc = d_res.alloc(h, who, (size_t)dpl * 4)) || (rc = d_tr.alloc(h, who, (size_t)2 * dpl * rows * cs * ntr_max)) ||
-        (rc = d_R.alloc(h, who, (size_t)nvec * cs * ntr_max)) || (rc = d_g.alloc(h, who, (size_t)2 * nvec * ncoeff)))
+        (rc = d_R.alloc(h, who, (size_t)nvec * cs * ntr_R)) || (rc = d_g.alloc(h, who, (size_t)2 * nvec * ncoeff)) ||
+        (mix && ((rc = d_mix.alloc(h, who, (size_t)nvec * Nc * Nc)) || (rc = d_raw.alloc(h, who, (size_t)nvec * (2 * cs + 1) * 2 * Nc)))))
         return rc;
     // d_g: [pass][primal | direction ...][ncoeff]
     hipStream_t s = h->stream;
     if ((rc = tl_upload_dense(h, img, wd, stride, nvec, d_img.p, d_h0.p, d_wd.p))) return rc;
     HIPCHK(h, hipMemcpyAsync(d_cimg.p, cimg.data(), cimg.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    const TlGen gen = {tl_spline(h, d_pc.p, ncoeff, nullptr), d_img.p, d_h0.p, d_pq.p, d_stream.p, stride, b.gstride, nvec};
+    std::vector<double> mixes;      // the member's mix once per stream [primal | direction ...]: one group, one mix
+    if (mix) {
+        for (int g = 0; g < nvec; ++g) mixes.insert(mixes.end(), mix, mix + (size_t)Nc * Nc);
+        HIPCHK(h, hipMemcpyAsync(d_mix.p, mixes.data(), mixes.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    const TlMix mx = {d_mix.p, d_mix.p, 1};
+    const TlGen gen = {tl_spline(h, d_pc.p, ncoeff, nullptr), d_img.p, d_h0.p, d_pq.p, d_stream.p, stride, b.gstride, nvec, d_mix.p, d_raw.p};
     PropArgs a = tl_prop_args(h, gen, dpl, d_state.p, sstride, d_work.p, d_wd.p);
     a.traces = d_tr.p;
 
@@ -87,7 +97,8 @@ static int hvp_run(jq_handle* h, const double* drift, const double* pcof, int nc
                 if ((rc = tm.begin(true))) return rc;
                 hipLaunchKernelGGL(k_backward_tl<>, dim3(nblocks), dim3(64 * JQ_HUGE_WAVES), 0, s, a);
                 if ((rc = tm.end())) return rc;
-                tl_reduce_chunk(h, gen.sp, r == 0, d_tr.p, rows, dpl, n0, nc, q0, ng, d_R.p, d_R.p + (size_t)cs * ntr_max, d_g.p + (size_t)pass * nvec * ncoeff);
+                tl_reduce_chunk(h, gen.sp, r == 0, d_tr.p, rows, dpl, n0, nc, q0, ng, d_R.p, d_R.p + (size_t)cs * ntr_R, d_g.p + (size_t)pass * nvec * ncoeff,
+                                mix ? &mx : nullptr);
                 mfma_bwd += (long long)nblocks * nc * (6 * (8 + 2 * h->m) + 8 * ng) * NT * KT;      // (two MFMAs per tile of a trace product)
                 if (n0 == 0) mfma_bwd += (long long)nblocks * 2 * ng * NT * KT;
             }

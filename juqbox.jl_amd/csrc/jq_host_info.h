@@ -205,6 +205,14 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
     if (h->drift_hvp_route > 0)
         kv("drift_hvp", std::string("{\"route\": \"") + (h->drift_hvp_route == 1 ? "lane" : h->drift_hvp_route == 3 ? "rowlane" : h->drift_hvp_route == 4 ? "quad" : "sequential") + "\", \"members_per_launch\": " + num(h->drift_hvp_members) +
                           ", \"directions_per_launch\": " + num(h->drift_hvp_per_launch) + ", \"chunk_steps\": " + num(h->drift_hvp_chunk) + ", \"rounds\": " + num(h->drift_hvp_rounds) + "}");
+    // jq_eval_f_g_grad_members_hvp (after a call): the fields of "drift_hvp", and what differed between its members -- their drifts, their
+    // control mixes (with mixes a member brings 1 + directions_per_launch streams into a launch)
+    if (h->member_hvp.route > 0) {
+        const jq_handle::MemberHvp& m = h->member_hvp;
+        kv("member_hvp", std::string("{\"route\": \"") + (m.route == 1 ? "lane" : m.route == 3 ? "rowlane" : m.route == 4 ? "quad" : "sequential") + "\", \"members_per_launch\": " + num(m.members) +
+                           ", \"directions_per_launch\": " + num(m.per_launch) + ", \"chunk_steps\": " + num(m.chunk) + ", \"rounds\": " + num(m.rounds) + ", \"drifts\": " +
+                           (m.drifts ? "true" : "false") + ", \"ctrl_mix\": " + (m.mix ? "true" : "false") + "}");
+    }
     o += "}";
     if (buflen > 0) {
         const size_t n = std::min(o.size(), (size_t)buflen - 1);

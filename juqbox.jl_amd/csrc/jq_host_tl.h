@@ -48,22 +48,26 @@ static int tl_refuse(jq_handle* h, const char* who, bool with_adjoint)
 // A drift ensemble (nmember > 1; jq_eval_f_g_grad_drifts_hvp) brings one primal stream per member: the directions are sized first, as for one
 // member, then as many members per launch (mpl) as the budget leaves streams for next to them, in mrounds rounds of equal size; trec is the
 // record of ONE member.  nmember == 1 is the budget it always was.
+// Members with a control mix (per_member; jq_eval_f_g_grad_members_hvp) bring the streams of their own directions along: a member costs
+// 1 + dpl streams instead of 1, so (fit + 1) / (1 + dpl) members fit next to each other (in rounds of equal size again) and the chunk
+// length follows from mpl (1 + dpl) streams.
 struct TlBudget {
     int dpl, cs, rounds, nchunks;
     size_t gstride;      // doubles of one group's stream of a chunk
     int mpl, mrounds;    // primal streams (members) per launch, member rounds
 };
-static TlBudget tl_budget(const jq_handle* h, size_t stride, int ndir, int dir_cap, size_t trec, int nmember = 1)
+static TlBudget tl_budget(const jq_handle* h, size_t stride, int ndir, int dir_cap, size_t trec, int nmember = 1, bool per_member = false)
 {
     const size_t budget = stream_budget_bytes(h) / sizeof(double);
     const long long want = 2LL * std::min(JQ_JVP_MIN_CHUNK, h->nsteps) + 1;
     const long long fit = (long long)(budget / (2 * stride * (size_t)want)) - 1;
     TlBudget b;
     b.dpl = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(ndir, dir_cap), fit));
-    const long long mfit = std::max<long long>(1, std::min<long long>(nmember, fit + 1 - b.dpl));
+    const long long mfit = std::max<long long>(1, std::min<long long>(nmember, per_member ? (fit + 1) / (1 + b.dpl) : fit + 1 - b.dpl));
     b.mrounds = (int)((nmember + mfit - 1) / mfit);
     b.mpl = (nmember + b.mrounds - 1) / b.mrounds;
-    const long long tps = (long long)(budget / ((size_t)(b.mpl + b.dpl) * 2 * stride));
+    const size_t nstreams = per_member ? (size_t)b.mpl * (1 + b.dpl) : (size_t)(b.mpl + b.dpl);
+    const long long tps = (long long)(budget / (nstreams * 2 * stride));
     long long cs = std::min<long long>(std::min(h->chunk_steps, h->nsteps), (tps - 1) / 2);
     if (trec) cs = std::min<long long>(cs, (long long)(budget / ((size_t)2 * b.dpl * b.mpl * trec)));
     b.cs = (int)std::max<long long>(1, cs);
@@ -75,12 +79,15 @@ static TlBudget tl_budget(const jq_handle* h, size_t stride, int ndir, int dir_c
 
 // The generators of a chunk's 1 + dpl streams: k_ctrl over the coefficient blocks in sp.pcof, k_stream over the operator images
 // himg = [H0 | Hsym_q | Hanti_q] with the groups' drift images h0 = [H0 | 0 ...].  dt > 0: the forward time table, dt < 0: the backward one.
+// mix (NULL: none, the launches they always were): one Nc x Nc control mix per group for k_ctrl, raw: its unmixed values in pq's layout.
 struct TlGen {
     SplineArgs sp;
     const double *himg, *h0;
     double *pq, *stream;
     size_t stride, gstride;
     int nvec;
+    const double* mix = nullptr;
+    double* raw = nullptr;
 };
 static SplineArgs tl_spline(const jq_handle* h, const double* d_pcof, int ncoeff, const double* d_rfreq)
 {
@@ -93,18 +100,21 @@ static SplineArgs tl_spline(const jq_handle* h, const double* d_pcof, int ncoeff
 static void tl_generate(const jq_handle* h, const TlGen& g, int n0, int nc, double dt)
 {
     const int ntp = 2 * nc + 1;
-    hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, g.nvec), dim3(128), 0, h->stream, g.sp, dt > 0 ? h->d_tf : h->d_tb, n0, ntp, dt, g.pq, (const double*)nullptr,
-                       (double*)nullptr);
+    hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, g.nvec), dim3(128), 0, h->stream, g.sp, dt > 0 ? h->d_tf : h->d_tb, n0, ntp, dt, g.pq, g.mix, g.raw);
     hipLaunchKernelGGL(k_stream, dim3((unsigned)((g.stride + 255) / 256), ntp, g.nvec), dim3(256), 0, h->stream, g.himg, g.h0, (long long)g.stride, g.pq, h->Nc,
                        (long long)g.stride, 0.5 * dt, g.stream, (long long)g.gstride);
 }
 
 // the coefficient blocks [pcof | dirs[:, j0 + j] ...] of a round on the device (a short last round repeats its last direction: every group has a stream)
 // np primal streams (the members of a drift ensemble share ONE control vector): pcof in front np times
-static int tl_upload_round(jq_handle* h, std::vector<double>& blk, double* d_pc, const double* pcof, const double* dirs, int j0, int nd, int dpl, int ncoeff, int np = 1)
+// per_member (members with a control mix): the directions once per member, [pcof x np | member 0: direction ... | member 1: ...]
+static int tl_upload_round(jq_handle* h, std::vector<double>& blk, double* d_pc, const double* pcof, const double* dirs, int j0, int nd, int dpl, int ncoeff, int np = 1,
+                           bool per_member = false)
 {
     for (int g = 0; g < np; ++g) std::copy(pcof, pcof + ncoeff, blk.begin() + (size_t)g * ncoeff);
-    for (int j = 0; j < dpl; ++j) std::copy_n(dirs + (size_t)(j0 + std::min(j, nd - 1)) * ncoeff, ncoeff, blk.begin() + (size_t)(np + j) * ncoeff);
+    for (int g = 0; g < (per_member ? np : 1); ++g)
+        for (int j = 0; j < dpl; ++j)
+            std::copy_n(dirs + (size_t)(j0 + std::min(j, nd - 1)) * ncoeff, ncoeff, blk.begin() + (size_t)(np + (size_t)g * dpl + j) * ncoeff);
     HIPCHK(h, hipMemcpyAsync(d_pc, blk.data(), blk.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     return JQ_OK;
 }
@@ -223,21 +233,44 @@ static long long tl_forward_mfma(const jq_handle* h, int rounds, int nblocks)
 // After a backward launch over the steps [n0, n0 + nc) with the controls [q0, q0 + ng): k_trace_reduce / k_gradacc on the primal record
 // of the round's first direction (primal: first round only -- every direction recomputes the same primal) into gp[0] and on the tangent
 // records behind it into gp[1 + j]; gp = [primal | direction ...][ncoeff].  rows: trace rows per direction; R, Rd: the reduced records.
+// mx (members with a control mix): every direction has P members of `rows` trace rows each, reduced apart with the member's mix -- R, Rd
+// then hold rows for ALL Nc controls and the assembly covers all of them, the other control groups add theirs in their sweeps (run_eval's
+// rule) -- into gradient blocks of their own, gp = [member 0 .. P - 1 | direction 0: member 0 .. P - 1 | direction 1: ...][ncoeff], for
+// the caller to add in member order (tl_fold_members).  primal: [C_0 .. C_{P - 1}], dirs: that dpl times.
+struct TlMix {
+    const double *primal, *dirs;
+    int P;
+};
 static void tl_reduce_chunk(const jq_handle* h, const SplineArgs& sp, bool primal, const double* tr, int rows, int dpl, int n0, int nc, int q0, int ng, double* R,
-                            double* Rd, double* gp)
+                            double* Rd, double* gp, const TlMix* mx = nullptr)
 {
-    const int ntr = ng * JQ_NTR;
+    const int ntr = ng * JQ_NTR, P = mx ? mx->P : 1;
+    const int ntr_R = mx ? h->Nc * JQ_NTR : ntr, gq0 = mx ? 0 : q0, gng = mx ? h->Nc : ng;
     const double dt = h->T / h->nsteps;
-    const unsigned rblocks = (unsigned)(((long long)nc * ntr + 255) / 256), gblocks = (unsigned)(ng * 2 * h->Nfreq * sp.D1);
-    const double* trd = tr + (size_t)dpl * rows * nc * ntr;      // the tangents' record (k_backward_tl, k_backward_lane_tl)
+    const unsigned rblocks = (unsigned)(((long long)nc * ntr_R + 255) / 256), gblocks = (unsigned)(gng * 2 * h->Nfreq * sp.D1);
+    const double* trd = tr + (size_t)dpl * P * rows * nc * ntr;      // the tangents' record (k_backward_tl, k_backward_lane_tl)
     hipStream_t s = h->stream;
     if (primal) {
-        hipLaunchKernelGGL(k_trace_reduce, dim3(rblocks, 1), dim3(256), 0, s, tr, rows, nc, ntr, R, (const double*)nullptr, h->Nc, q0);
-        hipLaunchKernelGGL(k_gradacc, dim3(gblocks, 1), dim3(JQ_GRADACC_THREADS), 0, s, sp, (const double*)R, h->d_tb, n0, nc, -dt, gp, q0, ng, (long long)sp.nCoeff);
+        hipLaunchKernelGGL(k_trace_reduce, dim3(rblocks, P), dim3(256), 0, s, tr, rows, nc, ntr, R, mx ? mx->primal : (const double*)nullptr, h->Nc, q0);
+        hipLaunchKernelGGL(k_gradacc, dim3(gblocks, P), dim3(JQ_GRADACC_THREADS), 0, s, sp, (const double*)R, h->d_tb, n0, nc, -dt, gp, gq0, gng, (long long)sp.nCoeff);
     }
-    hipLaunchKernelGGL(k_trace_reduce, dim3(rblocks, dpl), dim3(256), 0, s, trd, rows, nc, ntr, Rd, (const double*)nullptr, h->Nc, q0);
-    hipLaunchKernelGGL(k_gradacc, dim3(gblocks, dpl), dim3(JQ_GRADACC_THREADS), 0, s, sp, (const double*)Rd, h->d_tb, n0, nc, -dt, gp + sp.nCoeff, q0, ng,
-                       (long long)sp.nCoeff);
+    hipLaunchKernelGGL(k_trace_reduce, dim3(rblocks, dpl * P), dim3(256), 0, s, trd, rows, nc, ntr, Rd, mx ? mx->dirs : (const double*)nullptr, h->Nc, q0);
+    hipLaunchKernelGGL(k_gradacc, dim3(gblocks, dpl * P), dim3(JQ_GRADACC_THREADS), 0, s, sp, (const double*)Rd, h->d_tb, n0, nc, -dt, gp + (size_t)P * sp.nCoeff, gq0,
+                       gng, (long long)sp.nCoeff);
+}
+// The per-member gradient blocks of a launch, blk = [pass][member 0 .. P - 1 | direction 0: member 0 .. P - 1 | ...][ncoeff] on the host, added
+// onto fold = [pass][primal | direction ...][ncoeff] (tl_copy_out's layout): the first `nm` members of the launch, in member order.
+static void tl_fold_members(const std::vector<double>& blk, std::vector<double>& fold, int npass, int P, int nm, int dpl, int ncoeff)
+{
+    const size_t pb = (size_t)P * (1 + dpl) * ncoeff, pf = (size_t)(1 + dpl) * ncoeff;
+    for (int pass = 0; pass < npass; ++pass)
+        for (int j = -1; j < dpl; ++j) {
+            double* f = fold.data() + pass * pf + (size_t)(1 + j) * ncoeff;
+            for (int g = 0; g < nm; ++g) {
+                const double* b = blk.data() + pass * pb + ((size_t)(j < 0 ? g : P + j * P + g)) * ncoeff;
+                for (int k = 0; k < ncoeff; ++k) f[k] += b[k];
+            }
+        }
 }
 // A round's gradient blocks gbuf = [pass][primal | direction ...][ncoeff] on the host -> the caller's arrays: g0 / g1 the gradient of the
 // forced / of the unforced pass (first: the first round only), v0 / v1 the products of the directions [j0, j0 + nd).  Without an

@@ -1052,6 +1052,11 @@ struct PropArgs {
     // waves per member (jq_group_stream; one member: every wave of the launch), and differentiates along direction blockIdx.y (jq_tl_dir_stream).
     // 1: the ensemble over eps-nodes (jq_eval_f_g_grad_hvp), P: a launch of P drift members (jq_eval_f_g_grad_drifts_hvp).
     int nprimal;
+    // 0: the directions' streams are shared by the members, [member 0 .. P - 1 | direction 0 .. D - 1] (D = gridDim.y) -- members that differ
+    // in their drift alone.  1: every member brings the streams of its own directions, [member 0 .. P - 1 | member 0: direction 0 .. D - 1 |
+    // member 1: ...] -- members with a control mix (jq_eval_f_g_grad_members_hvp): the tangent of member i along direction j is
+    // sum_l (C_i d_j)_l H_l.  No other value.
+    int tl_dirs_per_member;
 };
 // The tile stream of the control vector that unit `unit` of the launch (row-lane kernels: wave, cooperative-quad kernels: column quad)
 // works for, a.group_units units per vector.  Wave-uniform by construction (block index and kernel arguments); the readfirstlane says so to the
@@ -1061,10 +1066,13 @@ __device__ __forceinline__ const double* jq_group_stream(const PropArgs& a, int 
     const int g = __builtin_amdgcn_readfirstlane(unit / a.group_units);
     return a.stream + (size_t)g * (size_t)a.stream_gstride;
 }
-// The stream of direction blockIdx.y of a tangent-linear sweep, behind the a.nprimal primal streams (wave-uniform: block index and kernel arguments)
-__device__ __forceinline__ const double* jq_tl_dir_stream(const PropArgs& a)
+// The stream of direction blockIdx.y of a tangent-linear sweep, behind the a.nprimal primal streams: the one every member shares, or
+// (a.tl_dirs_per_member) that of the member unit `unit` works for -- jq_group_stream's unit.  Wave-uniform: block index and kernel arguments;
+// the readfirstlane says so to the compiler, as there.
+__device__ __forceinline__ const double* jq_tl_dir_stream(const PropArgs& a, int unit)
 {
-    return a.stream + (size_t)(a.nprimal + blockIdx.y) * (size_t)a.stream_gstride;
+    const int g = __builtin_amdgcn_readfirstlane(unit / a.group_units) * a.tl_dirs_per_member;
+    return a.stream + (size_t)(a.nprimal + g * (int)gridDim.y + (int)blockIdx.y) * (size_t)a.stream_gstride;
 }
 #ifndef JQ_MAX_WRANK
 #define JQ_MAX_WRANK 16       // largest rank of a full weight matrix the kernels take (include/juqbox_hip.h)

@@ -15,7 +15,8 @@
 // pcof (one per member of a drift ensemble, a.group_units quads each, a workgroup holds quads of one member; P = 1: one stream for
 // every quad), group P + j generated
 // by k_ctrl / k_stream with direction j as the coefficient vector and a zero drift image -- the controls are linear in the
-// coefficients, so that stream IS the derivative of the primal one.  Every product is mm_t4q on an image of one of the two, and
+// coefficients, so that stream IS the derivative of the primal one.  Members with a control mix (a.tl_dirs_per_member) bring the streams of
+// their own directions: P + P gridDim.y streams, member g's direction j at P + g gridDim.y + j.  Every product is mm_t4q on an image of one of the two, and
 //     y = c + M x   has the tangent   yd = cd + M xd + Md x      (two more mm_t4q).
 // The node shift does not depend on the coefficients and differs between the columns of a quad: it is applied per lane to the
 // results (cw = c eps ws[row], as QuadImr::cw), never folded into the MFMA operand; its tangent term is cw xd.  The Horner chain is
@@ -78,7 +79,7 @@ struct QtlRings {
         lo16 = 16u * lane;
         // (the workgroup's quads belong to ONE member: a.group_units is a multiple of the quads per workgroup)
         srcp = (const char*)jq_group_stream(a, (int)blockIdx.x * nwv_);
-        srcd = (const char*)jq_tl_dir_stream(a);
+        srcd = (const char*)jq_tl_dir_stream(a, (int)blockIdx.x * nwv_);
         wave = wave_, nwv = nwv_;
         issue(0, 0);
     }

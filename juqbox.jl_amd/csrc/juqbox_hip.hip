@@ -198,6 +198,11 @@ struct jq_handle {
     // ... and the last jq_eval_f_g_grad_drifts_hvp: its route (the same codes), members and directions per launch, chunk length, rounds
     // (direction rounds x member rounds; sequential: the members' sums) (jq_plan_info "drift_hvp")
     int drift_hvp_route = 0, drift_hvp_members = 0, drift_hvp_per_launch = 0, drift_hvp_chunk = 0, drift_hvp_rounds = 0;
+    // ... and the last jq_eval_f_g_grad_members_hvp: the same five, and what differed between its members (jq_plan_info "member_hvp")
+    struct MemberHvp {
+        int route = 0, members = 0, per_launch = 0, chunk = 0, rounds = 0;
+        bool drifts = false, mix = false;
+    } member_hvp;
     // Structure embedding (try_embed): a second handle of the SAME problem with its two fastest Kronecker factors zero-padded
     // to 4 levels each (row i1 + d1 i2 + d1 d2 i3 -> i1 + 4 i2 + 16 i3), under which the operators have the JQ_BW_T4 structure;
     // batches that would otherwise run on the dense / band MFMA kernels go there (quad-layout / JQ_BW_T4 slab kernels).

@@ -374,6 +374,66 @@ def eval_hessvec_drifts(pcof, d, params, wa, drifts, weights):
     return hv + tikhonov_hessvec(d, params.tik0)
 
 
+def eval_f_g_grad_members_hvp(pcof, dirs, params, wa, weights, Hconsts=None, ctrl_mix=None):
+    """eval_f_g_grad_drifts_hvp over the members of eval_f_g_grad_members, in one library call (jq_eval_f_g_grad_members_hvp): the weighted
+    sums sum_i w_i of infidelity and leak, of the two gradients and of their derivatives along the columns of dirs, over members that
+    differ in a real mixing matrix of the controls (ctrl_mix: Nc x Nc x nmember; amplitude_mix for miscalibrated amplitudes), in their
+    drift (Hconsts), or in both.  ctrl_mix=None is eval_f_g_grad_drifts_hvp, bit for bit.  With mixes the routes stay that call's, but the
+    tangent stream of a direction is the member's own (sum_l (C_i d)_l H_l): a member brings 1 + directions_per_launch streams into a
+    launch, the members that the stream budget (option stream_bytes) has no room for follow in further member rounds
+    (wa.plan_info()["member_hvp"] = {route, members_per_launch, directions_per_launch, chunk_steps, rounds, drifts, ctrl_mix}).  The
+    handle is never re-planned; params.Hconst, the handle's drift and params.last_* are left alone.
+
+    dirs: an ncoeff x ndir array (one direction per column) or a single vector; weights: one per member; Hconsts: None (the drift of
+    params) or as for eval_f_g_grad_drifts_hvp; ctrl_mix: None (identity), an Nc x Nc x nmember array or a sequence of Nc x Nc matrices.
+    Returns the dict of eval_f_g_grad_hvp.  Not served: members x eps-nodes, sharding over devices.  Shape errors raise ValueError
+    before any library call."""
+    who = "eval_f_g_grad_members_hvp"
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("%s: wa must be a Working_Arrays_HIP" % who)
+    if wa.params is not params:
+        raise ValueError("%s: wa was allocated for a different objparams" % who)
+    ncoeff = int(wa.nCoeff)
+    try:
+        p = np.asarray(pcof, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("%s: pcof must be a vector of numbers (%s)" % (who, e))
+    if p.ndim != 1 or p.size != ncoeff:
+        raise ValueError("%s: pcof has shape %r, expected (%d,) (wa.nCoeff)" % (who, p.shape, ncoeff))
+    H, C, nm = _members(params, Hconsts, ctrl_mix, who)
+    try:
+        w = np.asarray(weights, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("%s: weights must be a vector of numbers (%s)" % (who, e))
+    if w.ndim != 1 or w.size != nm:
+        raise ValueError("%s: need one weight per member (%d), not shape %r" % (who, nm, w.shape))
+    D = _directions(dirs, ncoeff, who)
+    p, w = _f64(p), _f64(w)
+    nd = D.shape[0]
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    out2 = np.zeros(2)
+    ig, lg = np.zeros(ncoeff), np.zeros(ncoeff)
+    hvi, hvl = np.zeros((nd, ncoeff)), np.zeros((nd, ncoeff))
+    _lib.check(L.jq_eval_f_g_grad_members_hvp(h, _ptr(p), ncoeff, _ptr(D), nd, _ptr(H), _ptr(C), _ptr(w), nm, _ptr(out2), _ptr(ig), _ptr(lg),
+                                              _ptr(hvi), _ptr(hvl)), h)
+    return dict(infidelity=float(out2[0]), leak=float(out2[1]), infid_grad=ig, leak_grad=lg, hv_infid=np.ascontiguousarray(hvi.T),
+                hv_leak=np.ascontiguousarray(hvl.T))
+
+
+def eval_hessvec_members(pcof, d, params, wa, weights, Hconsts=None, ctrl_mix=None):
+    """eval_hessvec_drifts for a member ensemble: the derivative along d of the ensemble's gradient (eval_grad_f_par with ctrl_mix=...),
+    hv_infid of eval_f_g_grad_members_hvp -- objFuncType == 1: the derivative of the total gradient -- plus the second derivative of the
+    Tikhonov term.  (setup_ipopt_problem(hessian="exact") does not take a member ensemble; this is the callback for a caller's own
+    trust-region loop.)"""
+    d = np.asarray(d, dtype=np.float64)
+    r = eval_f_g_grad_members_hvp(pcof, d, params, wa, weights, Hconsts=Hconsts, ctrl_mix=ctrl_mix)
+    hv = r["hv_infid"][:, 0]
+    if params.objFuncType == 1:
+        hv = hv + r["hv_leak"][:, 0]
+    return hv + tikhonov_hessvec(d, params.tik0)
+
+
 def eval_f_g_grad_members(pcof, params, wa, weights, Hconsts=None, ctrl_mix=None, compute_adjoint=True, per_member=False):
     """eval_f_g_grad_drifts over the members of traceobjgrad_members (jq_eval_f_g_grad_members): the weighted sums over members that differ
     in a real mixing matrix of the controls (ctrl_mix: Nc x Nc x nmember; amplitude_mix for miscalibrated amplitudes), in their drift
