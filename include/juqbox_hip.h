@@ -52,7 +52,8 @@ extern "C" {
  *     the two gradients of a risk-neutral ensemble: the nodes in the lanes, the directions in the grid), jq_eval_f_g_grad_drifts_hvp (the
  *     same for an ensemble of arbitrary drift Hamiltonians: every wave reads the operator stream of its own member),
  *     jq_eval_f_g_grad_members_hvp (the same for members with a control mix as well: every wave reads the tangent stream of its own
- *     member too). */
+ *     member too), jq_sample_times / jq_control_samples / jq_traceobjgrad_samples / jq_eval_f_g_grad_samples (the objective of a table
+ *     of control values on the time grid and its gradient per entry: any parameterisation by a host-side chain rule). */
 #define JQ_ABI_VERSION 6
 
 #define JQ_MAX_CONTROLS 16 /* control Hamiltonians the fast kernels hold in registers; more: cooperative kernels (no limit)    */
@@ -646,6 +647,49 @@ int jq_eval_f_g_grad_dev(jq_handle *h, const double *pcof, int32_t ncoeff, const
  */
 int jq_traceobj_sweep(jq_handle *h, const double *pcof, int32_t ncoeff, const double *nodes, int32_t nquad,
                       const double *shift, double *out);
+
+/* ---- controls given as samples on the time grid ----------------------------------------------*/
+/*
+ * Every call above takes its controls in ONE parameterisation, quadratic B-splines with carrier waves (bcarrier2, the reference's only
+ * one).  The time loops know nothing of it: they read the table pq[time point][2 Nc] = (p_1, q_1, p_2, q_2, ...) and write per-step trace
+ * records; two small kernels turn coefficients into the table and records into a coefficient gradient.  The calls below put the table
+ * itself in the caller's hands: the objective for ANY table of control values on the 2 nsteps + 1 time points the integrator reads, and
+ * its exact gradient with respect to every entry.  Any parameterisation theta -> pq (piecewise-constant pulses, DRAG or Gaussian
+ * envelopes, Fourier or Slepian bases, a pulse filtered by a transfer function, the output of a neural network) is then a host-side
+ * chain rule, dJ/dtheta = (d pq / d theta)' dJ/dpq.  Sweeps, plan, chunking, kernel families, control groups, two-pass gradients,
+ * sv_type, full weights, the Jacobi solver, the implicit-midpoint integrator, the eps ensemble with its rounds and the embedded twin
+ * are those of jq_traceobjgrad / jq_eval_f_g_grad: no time-loop kernel differs, and the plan does not depend on whether samples or
+ * coefficients are given.
+ *
+ * The grid: nt = 2 nsteps + 1 points, J = 0 .. 2 nsteps counting half steps; jq_sample_times returns t[2 n] = the time of step n as the
+ * forward sweep accumulates it (t = t + h) and t[2 n + 1] = t[2 n] + h / 2.  A Stormer-Verlet step n reads the points 2 n, 2 n + 1,
+ * 2 n + 2; an implicit-midpoint step reads 2 n + 1 only, so its gradient entries at the even points are exact zeros.
+ * A sample is ONE number used by the forward and by the backward sweep.  The spline calls evaluate the backward sweep at the times of
+ * its own table (T - n h accumulated downwards), which differ from the forward ones in the last place: the objective of
+ * jq_traceobjgrad_samples with the table of jq_control_samples is bit-identical to jq_traceobjgrad's, the gradients agree to rounding.
+ *   pq : [2 Nc x nt] column-major: element (2 k, J) = p_k, (2 k + 1, J) = q_k at time point J (k = 0 .. Nc - 1)
+ * jq_sample_times: JQ_EINVAL for NULL or nt != 2 nsteps + 1.
+ * jq_control_samples: the handle's own spline-with-carrier controls of pcof on the grid -- the launch of the control kernel a forward
+ * sweep makes, over all steps at once, so the bits are the ones an evaluation of pcof streams.  Errors: the codes of jq_traceobjgrad
+ * for the coefficient count.
+ * jq_traceobjgrad_samples: out4 as jq_traceobjgrad; totalgrad / infidelgrad / leakgrad: [2 Nc x nt], the layout of pq, written when
+ * evaladjoint != 0 with the conventions of jq_traceobjgrad per entry (leakgrad zero-filled and infidelgrad == totalgrad for
+ * objFuncType 1); may be NULL when evaladjoint == 0.  No Tikhonov term.  A point shared by two chunks of the time loop receives its two
+ * halves from two launches in stream order: results are deterministic, equal across chunk lengths to rounding.
+ * jq_eval_f_g_grad_samples: jq_eval_f_g_grad with the table in place of the coefficients; infid_grad / leak_grad: [2 Nc x nt].
+ * jq_plan_info reports "sampled_controls": {time_points, nodes, chunk_steps} after such a call (additive key).
+ * Errors: JQ_EINVAL for NULL required pointers, nt != 2 nsteps + 1, a sample that is not finite, nquad < 1.  JQ_EUNSUPPORTED for
+ * uncoupled controls (their operators are driven by ft = 2 (p cos(2 pi Rfreq t) - q sin(2 pi Rfreq t)), a function of both slots: a
+ * lab-frame sample interface is a later step), and whatever jq_traceobjgrad refuses for the handle's settings.  A refused call writes
+ * nothing and leaves the handle as it was.  Multi-device handles run these calls on their first device.  Not served: Hessian-vector
+ * products in sample space, batches of sample tables, drift or mix members with samples, device pointers, sharding over devices.
+ */
+int jq_sample_times(const jq_handle *h, double *t, int32_t nt);
+int jq_control_samples(jq_handle *h, const double *pcof, int32_t ncoeff, double *pq);
+int jq_traceobjgrad_samples(jq_handle *h, const double *pq, int32_t nt, int32_t evaladjoint, double *out4, double *totalgrad,
+                            double *infidelgrad, double *leakgrad);
+int jq_eval_f_g_grad_samples(jq_handle *h, const double *pq, int32_t nt, const double *nodes, const double *weights, int32_t nquad,
+                             const double *shift, int32_t compute_adjoint, double *out2, double *infid_grad, double *leak_grad);
 
 /* ---- introspection ---------------------------------------------------------------------------*/
 /*

@@ -426,6 +426,50 @@ function hessian(pcof::Vector{Float64}, params::objparams, wa::AbstractWorkingAr
     return symmetrize ? (J + J') / 2 : J
 end
 
+# ---- controls given as samples on the time grid (include/juqbox_hip.h): the objective of ANY table pq[2 Nc, nt] of control values on the
+# nt = 2 nsteps + 1 time points the integrator reads, and its gradient with respect to every entry -- a parameterisation theta -> pq
+# (piecewise-constant pulses, envelopes, Fourier bases, a filtered pulse) is then the chain rule (d pq / d theta)' * gradient on the host.
+# Row 2k - 1 of pq is p_k, row 2k is q_k.  Coupled controls only; the library refuses uncoupled ones.
+function control_sample_times(params::objparams, wa::AbstractWorkingArraysHIP)
+    t = zeros(2 * params.nsteps + 1)
+    rc = ccall((:jq_sample_times, libjq), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32), wa.handle, t, length(t))
+    rc == 0 || error("jq_sample_times: error $rc (the handle has another number of time steps than params)")
+    return t
+end
+# the handle's own spline-with-carrier controls of pcof on that grid, bit for bit what an evaluation of pcof streams
+function control_samples(pcof::Vector{Float64}, params::objparams, wa::AbstractWorkingArraysHIP)
+    sync!(wa, params)
+    pq = zeros(2 * params.Ncoupled, 2 * params.nsteps + 1)
+    jqcheck(wa, ccall((:jq_control_samples, libjq), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}), wa.handle, pcof, length(pcof), pq))
+    return pq
+end
+# the return tuples of traceobjgrad (not verbose) with [2 Nc, nt] gradients
+function traceobjgrad_samples(pq::Matrix{Float64}, params::objparams, wa::AbstractWorkingArraysHIP, evaladjoint::Bool = true)
+    size(pq) == (2 * params.Ncoupled, 2 * params.nsteps + 1) || throw(DimensionMismatch("traceobjgrad_samples: pq must be 2 Ncoupled x (2 nsteps + 1)"))
+    sync!(wa, params)
+    out4 = zeros(4)
+    tg = zeros(size(pq)); ig = zeros(size(pq)); lg = zeros(size(pq))
+    jqcheck(wa, ccall((:jq_traceobjgrad_samples, libjq), Cint,
+                      (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                      wa.handle, pq, size(pq, 2), evaladjoint ? 1 : 0, out4, tg, ig, lg))
+    evaladjoint || return out4[1], out4[2], out4[3]
+    return out4[1], tg, out4[2], out4[3], out4[4], ig, (params.objFuncType == 1 ? zeros(0, 0) : lg)
+end
+# eval_f_g_grad over the quadrature nodes with the table in place of the coefficients: (infidelity, leak, infid_grad, leak_grad), the
+# gradients [2 Nc, nt]; params.last_* are left alone
+function eval_f_g_grad_samples(pq::Matrix{Float64}, params::objparams, wa::AbstractWorkingArraysHIP, nodes::Vector{Float64} = [0.0],
+                               weights::Vector{Float64} = [1.0], shift::Union{Nothing, Vector{Float64}} = nothing, compute_adjoint::Bool = true)
+    size(pq) == (2 * params.Ncoupled, 2 * params.nsteps + 1) || throw(DimensionMismatch("eval_f_g_grad_samples: pq must be 2 Ncoupled x (2 nsteps + 1)"))
+    nq = length(nodes)
+    (nq >= 1 && length(weights) == nq) || throw(ArgumentError("eval_f_g_grad_samples: nodes and weights must have the same length >= 1"))
+    sync!(wa, params)
+    out2 = zeros(2); ig = zeros(size(pq)); lg = zeros(size(pq))
+    jqcheck(wa, ccall((:jq_eval_f_g_grad_samples, libjq), Cint,
+                      (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                      wa.handle, pq, size(pq, 2), nodes, weights, nq, shift === nothing ? C_NULL : pointer(shift), compute_adjoint ? 1 : 0, out2, ig, lg))
+    return (infidelity = out2[1], leak = out2[2], infid_grad = ig, leak_grad = lg)
+end
+
 # Many control vectors of ONE problem in one call (jq_traceobjgrad_batch): column i of every result is what
 # traceobjgrad(pcofs[:, i], params, wa, false, evaladjoint) returns.  On the latency kernels (row-lane, cooperative quad; Stormer-Verlet)
 # the vectors share launches, elsewhere they run one after the other inside the call.

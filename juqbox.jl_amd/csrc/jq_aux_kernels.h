@@ -1,6 +1,7 @@
 // jq_aux_kernels.h -- the small kernels around the propagators: on-device control evaluation
 // (bcarrier2), K(t)/S(t) tile-stream generation, state initialisation, fidelity + adjoint terminal
-// condition, trace reduction and gradient assembly (gradbcarrier2! as an 18-entry scatter).
+// condition, trace reduction and gradient assembly (gradbcarrier2! as an 18-entry scatter); the siblings of the control evaluation and
+// of the assembly for controls given as samples on the time grid (k_ctrl_samples, k_gradsamples).
 #pragma once
 #include "jq_kernels.h"
 #include "jq_rowlane_kernels.h"
@@ -511,6 +512,65 @@ __global__ __launch_bounds__(JQ_GRADACC_THREADS) void k_gradacc(SplineArgs s, co
         __syncthreads();
     }
     if (threadIdx.x == 0) grad[idx] += red[0];
+}
+
+// ---------------------------------------------------------------------------------------------
+// Controls given as samples on the time grid (jq_traceobjgrad_samples): the siblings of k_ctrl and k_gradacc without a basis.
+// S[J][2 Nc] = (p_1, q_1, p_2, q_2, ...) at the half-step index J = 0 .. 2 nsteps of the FORWARD grid (jq_sample_times), nt = 2 nsteps + 1
+// rows; G has the same layout.  A chunk of a sweep maps its stream point j to J = J0 + dir j:
+//   forward chunk at step n0:            J0 = 2 n0,             dir = +1
+//   backward chunk at backward step n0:  J0 = 2 (nsteps - n0),  dir = -1
+// One number per time point serves both sweeps (the spline path evaluates the backward sweep at the times of its own table, which
+// differ from the forward ones in the last place).
+
+// pq[j][2 Nc] = S[J0 + dir j][2 Nc]; the layout and the launch geometry over ntp of k_ctrl, no mix, no uncoupled branch
+__global__ void k_ctrl_samples(const double* __restrict__ S, int nt, int J0, int dir, int ntp, int Nc, double* __restrict__ pq)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= ntp) return;
+    const int J = J0 + dir * j;
+    if (J < 0 || J >= nt) return;
+    for (int f = 0; f < 2 * Nc; ++f) pq[(size_t)j * 2 * Nc + f] = S[(size_t)J * 2 * Nc + f];
+}
+
+// Gradient with respect to the samples from the trace records of one chunk of backward steps: the assembly of k_gradacc before the
+// basis.  R[m][ng][JQ_NTR] are the rows of the sweep's control group [q0, q0 + ng); with r the row of step m and h = -dt, the step gives
+//   its point 2 m:      dJ/dp = h (-r[1]),  dJ/dq = h (-r[0])
+//   its point 2 m + 2:  dJ/dp = h (-r[1]),  dJ/dq = h (-r[2])
+//   its point 2 m + 1:  dJ/dp = h   r[3],   dJ/dq = h (-r[4])
+// -- the (w = 0, 1, 2) cases of k_gradacc.  One thread per (chunk point j, control, p or q): an even point adds the contribution of
+// step j / 2 and then that of step j / 2 - 1, where the chunk has them, and does ONE += into G[J0 - j][2 q + {0: p, 1: q}].  A point on
+// the boundary of two chunks gets its halves from two launches in stream order, so the result is deterministic.  The implicit-midpoint
+// kernels fill r[3], r[4] only: their integer-point entries stay exact zeros.
+__global__ void k_gradsamples(const double* __restrict__ R, int nsteps_chunk, double h, double* G, int nt, int J0, int Nc, int q0, int ng)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int ntp = 2 * nsteps_chunk + 1;
+    if (i >= (long long)ntp * ng * 2) return;
+    const int j = (int)(i / (2 * ng)), rem = (int)(i - (long long)j * 2 * ng);
+    const int c = rem >> 1, isq = rem & 1;
+    const int J = J0 - j;
+    if (J < 0 || J >= nt) return;
+    const int ntr = ng * JQ_NTR;
+    double acc = 0.0;
+    if (j & 1) {
+        const double* r = R + (size_t)(j >> 1) * ntr + c * JQ_NTR;
+        acc = h * (isq ? -r[4] : r[3]);
+    } else {
+        const int m = j >> 1;
+        bool first = true;
+        if (m < nsteps_chunk) {      // point 2 m of step m
+            const double* r = R + (size_t)m * ntr + c * JQ_NTR;
+            acc = h * (isq ? -r[0] : -r[1]);
+            first = false;
+        }
+        if (m >= 1) {                // point 2 (m - 1) + 2 of step m - 1
+            const double* r = R + (size_t)(m - 1) * ntr + c * JQ_NTR;
+            const double v = h * (isq ? -r[2] : -r[1]);
+            acc = first ? v : acc + v;
+        }
+    }
+    G[(size_t)J * 2 * Nc + 2 * (q0 + c) + isq] += acc;
 }
 
 // Packed result of an ensemble evaluation, left on the device for the collective that sums it over GPUs (one all-reduce):

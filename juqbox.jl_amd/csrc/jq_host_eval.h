@@ -21,6 +21,10 @@ struct EvalRequest {
     // group g is sum_k C_g[l, k] (p_k, q_k).  In a grouped batch the groups share ONE control vector, as with drifts; without groups it is
     // the mix of the single evaluation.  Only k_ctrl and k_trace_reduce see it.
     const double* mix = nullptr;
+    // controls as samples on the time grid (jq_traceobjgrad_samples): HOST array [2 Nc x nt], nt = 2 nsteps + 1 (NULL: none), the values
+    // (p_1, q_1, p_2, q_2, ...) at every time point of jq_sample_times.  It takes the place of the coefficients: pcof is not read, ncoeff
+    // = 2 Nc nt is the length of the gradients, which are those with respect to the samples.  Only k_ctrl_samples and k_gradsamples see it.
+    const double* samples = nullptr;
     bool split_part = false;        // one part of a split batch: not split again
 };
 struct EvalOut {
@@ -94,6 +98,15 @@ static jq_handle* eval_target(jq_handle* h, int nsamples, bool hist)
 }
 // The batched evaluation behind every hot-path entry point.  It writes the handle's buffers and their capacities, the bookkeeping of the
 // three-workgroup kernels, `timing` and `err`.
+// what every sampled-controls call refuses before anything is written: uncoupled controls -- ft is a function of BOTH slots of a pair
+// and of the rotation frequency, so a table of (p, q) values is not what their operators are driven with
+static int samples_refuse(jq_handle* h, const char* who)
+{
+    if (!h->rfreq.empty())
+        return fail(h, JQ_EUNSUPPORTED, (std::string(who) + ": uncoupled controls are not served with sampled controls (their operators are driven by "
+                                                            "ft = 2 (p cos(2 pi Rfreq t) - q sin(2 pi Rfreq t)), not by p and q)").c_str());
+    return JQ_OK;
+}
 #define JQ_ERETRY_INTERNAL (-1000)      // run_eval_impl: k_backward_cq3 gave up (the handle leaves it alone for a while): evaluate again
 #define JQ_CQ3_MAX_FAULTS 6
 static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out);
@@ -153,8 +166,15 @@ static void terminal_cols(hipStream_t s, Map m, int files, double* state, size_t
 
 static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
 {
-    const double *const pcof = rq.pcof, *const shift = rq.shift, *eps = rq.eps, *wgt = rq.wgt;      // (eps, wgt: a grouped batch expands them below)
+    const bool sampled = rq.samples != nullptr;      // (the sample table travels where the coefficients do: d_pcof)
+    const double *const pcof = sampled ? rq.samples : rq.pcof, *const shift = rq.shift, *eps = rq.eps, *wgt = rq.wgt;      // (eps, wgt: a grouped batch expands them below)
     const int ncoeff = rq.ncoeff, nsamples = rq.nsamples;
+    const int nt = 2 * h->nsteps + 1;
+    if (sampled) {
+        if (int rc = samples_refuse(h, "run_eval")) return rc;
+        if (rq.groups > 0 || rq.drifts || rq.mix) return fail(h, JQ_EUNSUPPORTED, "sampled controls together with a batch of control vectors, member drifts or control mixes are not served");
+        if (ncoeff != 2 * h->Nc * nt) return fail(h, JQ_EHIP, "internal error: sampled controls with a gradient length other than 2 Nc nt");
+    }
     const bool adjoint = rq.adjoint;
     double *const hist_r = rq.hist_r, *const hist_i = rq.hist_i, *const d_packed = rq.d_packed;
     HIPCHK(h, hipSetDevice(h->device));
@@ -209,12 +229,13 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
             h->timing.kernel_family = t1.kernel_family, h->timing.kernel_size = t1.kernel_size, h->timing.kernel_band = t1.kernel_band;
             h->last_kernels = k1;
             h->timing.ms_shard_min = h->timing.ms_shard_max = h->timing.ms_total;
+            if (sampled) h->sc_nodes = nsamples;
             return JQ_OK;
         }
     }
-    int rc = check_ncoeff(h, ncoeff);
+    int rc = sampled ? JQ_OK : check_ncoeff(h, ncoeff);
     if (rc) return rc;
-    const int D1 = ncoeff / (2 * h->Nc * h->Nfreq);  // src/evalobjgrad.jl:608
+    const int D1 = sampled ? 3 : ncoeff / (2 * h->Nc * h->Nfreq);  // src/evalobjgrad.jl:608 (sampled controls: no spline is evaluated)
     if (nsamples < 1) return fail(h, JQ_EINVAL, "need at least one sample");
     // grouped batch (pcof_batch): G control vectors, pcof = their G coefficient blocks, nsamples = G x spg samples: per vector the Q samples
     // of the caller (eps, wgt: [Q], the same nodes for every vector; without them one sample of weight 1) and the padding that ends its
@@ -245,6 +266,7 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
         if (rc != JQ_OK) h->err = e->err;
         h->timing = e->timing;
         if (rc == JQ_OK) h->last_kernels = e->last_kernels;
+        if (rc == JQ_OK && sampled) h->sc_nt = e->sc_nt, h->sc_nodes = e->sc_nodes, h->sc_chunk = e->sc_chunk;
         return rc;
     }
     GateHold gate_hold;      // (held until the evaluation ends when the plan takes the split latency kernels)
@@ -416,7 +438,10 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     for (int n0 = 0; n0 < h->nsteps; n0 += p.cs) {
         const int nc = std::min(p.cs, h->nsteps - n0);
         const int ntp = 2 * nc + 1;
-        hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, sp, h->d_tf, n0, ntp, dt, h->d_pq, d_mix, d_pqraw);
+        if (sampled)
+            hipLaunchKernelGGL(k_ctrl_samples, dim3((ntp + 127) / 128), dim3(128), 0, s, h->d_pcof, nt, 2 * n0, 1, ntp, h->Nc, h->d_pq);
+        else
+            hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, sp, h->d_tf, n0, ntp, dt, h->d_pq, d_mix, d_pqraw);
         hipLaunchKernelGGL(k_stream, dim3((unsigned)((p.stride + 255) / 256), ntp, nvec), dim3(256), 0, s, p.himg, h0img, h0_gstride,
                            h->d_pq, h->Nc, p.stride, 0.5 * dt, h->d_stream, (long long)gstride);
         a.nsteps_chunk = nc; a.step0 = n0; a.first_chunk = (n0 == 0); a.h = dt; a.forced = 1;
@@ -483,7 +508,10 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
             for (int n0 = 0; n0 < h->nsteps; n0 += p.cs) {
                 const int nc = std::min(p.cs, h->nsteps - n0);
                 const int ntp = 2 * nc + 1;
-                hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, sp, h->d_tb, n0, ntp, -dt, h->d_pq, d_mix, d_pqraw);
+                if (sampled)
+                    hipLaunchKernelGGL(k_ctrl_samples, dim3((ntp + 127) / 128), dim3(128), 0, s, h->d_pcof, nt, 2 * (h->nsteps - n0), -1, ntp, h->Nc, h->d_pq);
+                else
+                    hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, sp, h->d_tb, n0, ntp, -dt, h->d_pq, d_mix, d_pqraw);
                 hipLaunchKernelGGL(k_stream, dim3((unsigned)((p.stride + 255) / 256), ntp, nvec), dim3(256), 0, s, p.himg, h0img,
                                    h0_gstride, h->d_pq, h->Nc, p.stride, -0.5 * dt, h->d_stream, (long long)gstride);
                 a.nsteps_chunk = nc; a.step0 = n0; a.first_chunk = (n0 == 0); a.h = -dt; a.forced = (pass == 0);
@@ -532,9 +560,12 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
                 const int ntr_R = d_mix ? h->Nc * JQ_NTR : ntr_g;
                 hipLaunchKernelGGL(k_trace_reduce, dim3((unsigned)(((long long)nc * ntr_R + 255) / 256), nvec), dim3(256), 0, s,
                                    h->d_traces, G > 0 ? p.upg : p.trace_rows, nc, ntr_g, h->d_R, d_mix, h->Nc, q0);
-                // gradbcarrier2! as a scatter: one workgroup per coefficient of the group's controls
-                hipLaunchKernelGGL(k_gradacc, dim3((d_mix ? h->Nc : ng) * 2 * h->Nfreq * D1, nvec), dim3(JQ_GRADACC_THREADS), 0, s, sp, h->d_R, h->d_tb, n0, nc, -dt,
-                                   h->d_grad + (size_t)pass * ncoeff, d_mix ? 0 : q0, d_mix ? h->Nc : ng, (long long)2 * ncoeff);
+                if (sampled)      // the same records without the basis: one thread per (time point of the chunk, control of the group, p | q)
+                    hipLaunchKernelGGL(k_gradsamples, dim3((unsigned)(((long long)ntp * ng * 2 + 255) / 256)), dim3(256), 0, s, h->d_R, nc, -dt,
+                                       h->d_grad + (size_t)pass * ncoeff, nt, 2 * (h->nsteps - n0), h->Nc, q0, ng);
+                else      // gradbcarrier2! as a scatter: one workgroup per coefficient of the group's controls
+                    hipLaunchKernelGGL(k_gradacc, dim3((d_mix ? h->Nc : ng) * 2 * h->Nfreq * D1, nvec), dim3(JQ_GRADACC_THREADS), 0, s, sp, h->d_R, h->d_tb, n0, nc, -dt,
+                                       h->d_grad + (size_t)pass * ncoeff, d_mix ? 0 : q0, d_mix ? h->Nc : ng, (long long)2 * ncoeff);
                 mfma += (long long)p.nslabs * nc * (2 * (8 + 2 * h->m) * p.tiles + 4 * trace_tiles);
                 if (n0 == 0) mfma += (long long)p.nslabs * trace_tiles;
             }
@@ -631,6 +662,7 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     h->last_kernels = p.sel;
     h->timing.ms_allreduce = 0.0;
     h->timing.ms_shard_min = h->timing.ms_shard_max = h->timing.ms_total;
+    if (sampled) h->sc_nt = nt, h->sc_nodes = nsamples, h->sc_chunk = p.cs;
     return JQ_OK;
 }
 

@@ -213,6 +213,9 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
                            ", \"directions_per_launch\": " + num(m.per_launch) + ", \"chunk_steps\": " + num(m.chunk) + ", \"rounds\": " + num(m.rounds) + ", \"drifts\": " +
                            (m.drifts ? "true" : "false") + ", \"ctrl_mix\": " + (m.mix ? "true" : "false") + "}");
     }
+    // jq_traceobjgrad_samples / jq_eval_f_g_grad_samples (after a call): time points of the sample table, nodes, steps per chunk
+    if (h->sc_nt > 0)
+        kv("sampled_controls", std::string("{\"time_points\": ") + num(h->sc_nt) + ", \"nodes\": " + num(h->sc_nodes) + ", \"chunk_steps\": " + num(h->sc_chunk) + "}");
     o += "}";
     if (buflen > 0) {
         const size_t n = std::min(o.size(), (size_t)buflen - 1);

@@ -28,6 +28,12 @@
                                         all unit directions through one traceobjgrad_hvp call.
   gradient_check(pcof0, params, wa, kpars, h=1e-6)
                                         adjoint gradient entries against central differences, from one batch.
+  traceobjgrad_samples(pq, params, wa, evaladjoint=True)
+                                        traceobjgrad for controls given as values on the time grid (jq_traceobjgrad_samples): the
+                                        objective of a 2 Ncoupled x (2 nsteps + 1) table and its gradient per entry -- any
+                                        parameterisation is then a chain rule on the host.
+  control_sample_times(params, wa), control_samples(pcof, params, wa), spline_sample_matrix(params, ncoeff, times)
+                                        the grid, the library's own controls on it, and their dense derivative d pq / d pcof.
 """
 import contextlib
 import ctypes
@@ -697,6 +703,118 @@ def traceobjgrad_members(pcof, params: objparams, wa: Working_Arrays_HIP, Hconst
     leak = np.zeros((0, n)) if params.objFuncType == 1 else np.ascontiguousarray(lg.T)
     return (out4[:, 0].copy(), np.ascontiguousarray(tg.T), out4[:, 1].copy(), out4[:, 2].copy(), out4[:, 3].copy(),
             np.ascontiguousarray(ig.T), leak)
+
+
+# ---- controls given as samples on the time grid (include/juqbox_hip.h, "controls given as samples") ----
+def _sample_table(pq, params, who):
+    """pq -> the flat [2 Nc x nt] column-major table of the C ABI; ValueError for another shape or entries that are not finite"""
+    shape = (2 * int(params.Ncoupled), 2 * int(params.nsteps) + 1)
+    try:
+        a = np.asarray(pq, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("%s: pq must be a 2 Ncoupled x (2 nsteps + 1) array of numbers (%s)" % (who, e))
+    if a.shape != shape:
+        raise ValueError("%s: pq has shape %r, expected %r (2 Ncoupled x (2 nsteps + 1): row 2k is p_k, row 2k + 1 is q_k)" % (who, a.shape, shape))
+    if not np.all(np.isfinite(a)):
+        raise ValueError("%s: pq has an entry that is not finite" % who)
+    return _f64(a), shape
+
+
+def control_sample_times(params: objparams, wa: Working_Arrays_HIP):
+    """The 2 nsteps + 1 time points the integrator reads controls at (jq_sample_times): t[2n] is the time of step n as the forward sweep
+    accumulates it, t[2n + 1] = t[2n] + dt / 2.  Column J of a sample table belongs to t[J]."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("control_sample_times: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("control_sample_times: wa was allocated for a different objparams")
+    t = np.zeros(2 * int(params.nsteps) + 1)
+    rc = _lib.load().jq_sample_times(wa.handle, _ptr(t), t.size)
+    if rc != _lib.JQ_OK:
+        raise _lib.JuqboxHipError(rc, "jq_sample_times: the handle has another number of time steps than params")
+    return t
+
+
+def control_samples(pcof, params: objparams, wa: Working_Arrays_HIP):
+    """The handle's own spline-with-carrier controls of pcof on the grid of control_sample_times (jq_control_samples): a 2 Ncoupled x
+    (2 nsteps + 1) array, row 2k = p_k, row 2k + 1 = q_k -- bit for bit what an evaluation of pcof streams, so traceobjgrad_samples of it
+    returns the objective of traceobjgrad(pcof) bit for bit.  Coupled controls only."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("control_samples: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("control_samples: wa was allocated for a different objparams")
+    p = _f64(pcof)
+    shape = (2 * int(params.Ncoupled), 2 * int(params.nsteps) + 1)
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    pq = np.zeros(shape[0] * shape[1])
+    _lib.check(L.jq_control_samples(h, _ptr(p), p.size, _ptr(pq)), h)
+    return pq.reshape(shape, order="F")
+
+
+def traceobjgrad_samples(pq, params: objparams, wa: Working_Arrays_HIP, evaladjoint: bool = True):
+    """traceobjgrad for controls given as VALUES on the time grid instead of spline coefficients (jq_traceobjgrad_samples): pq is a
+    2 Ncoupled x (2 nsteps + 1) array, column J the controls (p_1, q_1, p_2, q_2, ...) at control_sample_times()[J].  The gradients are
+    those of the discrete objective with respect to every entry of pq, in the shape of pq; any parameterisation theta -> pq is then a chain
+    rule on the host (spline_sample_matrix is the one of the library's own splines; torch_controls.SampledObjective the autograd form).
+    Sweeps, plan and kernel families are those of traceobjgrad.  The implicit-midpoint integrator reads the odd columns only: its
+    gradient columns at even J are exact zeros.
+
+    evaladjoint: (objfv, totalgrad, primaryobjf, secondaryobjf, traceInfidelity, infidelgrad, leakgrad) -- leakgrad empty for
+                 objFuncType == 1, like traceobjgrad's
+    else:        (objfv, primaryobjf, secondaryobjf)
+    No Tikhonov term.  Shape errors and entries that are not finite raise ValueError before any library call; the library refuses
+    uncoupled controls."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("traceobjgrad_samples: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("traceobjgrad_samples: wa was allocated for a different objparams")
+    tab, shape = _sample_table(pq, params, "traceobjgrad_samples")
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    out4 = np.zeros(4)
+    if not evaladjoint:
+        _lib.check(L.jq_traceobjgrad_samples(h, _ptr(tab), shape[1], 0, _ptr(out4), None, None, None), h)
+        return out4[0], out4[1], out4[2]
+    tg, ig, lg = np.zeros(tab.size), np.zeros(tab.size), np.zeros(tab.size)
+    _lib.check(L.jq_traceobjgrad_samples(h, _ptr(tab), shape[1], 1, _ptr(out4), _ptr(tg), _ptr(ig), _ptr(lg)), h)
+    leak = np.zeros((0, 0)) if params.objFuncType == 1 else lg.reshape(shape, order="F")
+    return out4[0], tg.reshape(shape, order="F"), out4[1], out4[2], out4[3], ig.reshape(shape, order="F"), leak
+
+
+def spline_sample_matrix(params: objparams, ncoeff: int, times):
+    """The dense B = d pq / d pcof of the library's own parameterisation (bcarrier2, src/bsplines.jl:211-304) on the given times, in
+    numpy: (2 Ncoupled len(times)) x ncoeff, row 2 Ncoupled J + f = control function f (2k: p_k, 2k + 1: q_k) at times[J], so that
+        pq = (B @ pcof).reshape((2 Ncoupled, len(times)), order="F")        and        dJ/dpcof = B.T @ G.ravel(order="F")
+    for a sample gradient G of traceobjgrad_samples.  With times = control_sample_times() the first agrees with control_samples(pcof)
+    to rounding (the device evaluates sin / cos and the sums in its own order).  The controls are linear in pcof, so B does not depend
+    on it.  Host only: no handle, no device."""
+    Nc, Nfreq = int(params.Ncoupled), int(params.Nfreq)
+    ncoeff = int(ncoeff)
+    if Nc < 1 or ncoeff % (2 * Nc * Nfreq) != 0 or ncoeff // (2 * Nc * Nfreq) < 3:
+        raise ValueError("spline_sample_matrix: ncoeff = %d is not 2 Ncoupled Nfreq D1 with D1 >= 3" % ncoeff)
+    D1 = ncoeff // (2 * Nc * Nfreq)
+    t = np.asarray(times, dtype=np.float64).ravel()
+    dtknot = float(params.T) / (D1 - 2)      # bcparams (src/bsplines.jl:174)
+    width = 3.0 * dtknot
+    k = np.clip(np.ceil(t / dtknot + 2.0).astype(np.int64), 3, D1)      # 1-based knot index (:224-225)
+    tau = [(t - dtknot * ((k - i) - 1.5)) / width for i in range(3)]      # centres k, k - 1, k - 2 (:238-250)
+    b = [9.0 / 8.0 + 4.5 * tau[0] + 4.5 * tau[0] * tau[0], 0.75 - 9.0 * tau[1] * tau[1], 9.0 / 8.0 - 4.5 * tau[2] + 4.5 * tau[2] * tau[2]]
+    Cfreq = np.asarray(params.Cfreq, dtype=np.float64).reshape(-1, Nfreq)
+    B = np.zeros((2 * Nc * t.size, ncoeff))
+    J = np.arange(t.size)
+    for osc in range(Nc):
+        for freq in range(Nfreq):
+            off1 = 2 * osc * Nfreq * D1 + freq * 2 * D1
+            off2 = off1 + D1
+            cs, sn = np.cos(Cfreq[osc, freq] * t), np.sin(Cfreq[osc, freq] * t)
+            for i in range(3):
+                col = k - 1 - i
+                rp, rq = 2 * Nc * J + 2 * osc, 2 * Nc * J + 2 * osc + 1
+                B[rp, off1 + col] += b[i] * cs      # p = fbs1 cos - fbs2 sin (:260)
+                B[rp, off2 + col] += -b[i] * sn
+                B[rq, off1 + col] += b[i] * sn      # q = fbs1 sin + fbs2 cos (:258)
+                B[rq, off2 + col] += b[i] * cs
+    return B
 
 
 def gradient_check(pcof0, params: objparams, wa: Working_Arrays_HIP, kpars, h: float = 1e-6):

@@ -5,7 +5,7 @@ signatures, so any L-BFGS driver can call them)."""
 import numpy as np
 
 from . import _lib
-from .evalobjgrad import Working_Arrays_HIP, _directions, _drift_members, _f64, _members, _pcof_columns, _ptr
+from .evalobjgrad import Working_Arrays_HIP, _directions, _drift_members, _f64, _members, _pcof_columns, _ptr, _sample_table
 from .setup_utils import tikhonov_grad, tikhonov_pen
 
 
@@ -247,6 +247,46 @@ def eval_f_g_grad_hvp(pcof, dirs, params, wa, nodes=(0.0,), weights=(1.0,), shif
                                       _ptr(lg), _ptr(hvi), _ptr(hvl)), h)
     return dict(infidelity=float(out2[0]), leak=float(out2[1]), infid_grad=ig, leak_grad=lg, hv_infid=np.ascontiguousarray(hvi.T),
                 hv_leak=np.ascontiguousarray(hvl.T))
+
+
+def eval_f_g_grad_samples(pq, params, wa, nodes=(0.0,), weights=(1.0,), shift=None, compute_adjoint=True):
+    """eval_f_g_grad over the quadrature nodes for controls given as VALUES on the time grid (jq_eval_f_g_grad_samples): pq is the
+    2 Ncoupled x (2 nsteps + 1) table of traceobjgrad_samples, node i the evaluation with Hconst + nodes[i] diag(shift), all nodes in one
+    batch like eval_f_g_grad's (its kernel families, rounds and embedded twin).
+
+    Returns a dict: infidelity, leak, and with compute_adjoint infid_grad, leak_grad in the shape of pq -- the weighted sums of the nodes'
+    gradients with respect to every sample (objFuncType == 1: infid_grad is the total gradient, leak_grad zeros).  No Tikhonov term;
+    params.last_* are left alone.  Shape errors raise ValueError before any library call."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("eval_f_g_grad_samples: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("eval_f_g_grad_samples: wa was allocated for a different objparams")
+    tab, shape = _sample_table(pq, params, "eval_f_g_grad_samples")
+    try:
+        nodes, weights = np.asarray(nodes, dtype=np.float64), np.asarray(weights, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("eval_f_g_grad_samples: nodes and weights must be vectors of numbers (%s)" % e)
+    if nodes.ndim != 1 or weights.ndim != 1 or nodes.size != weights.size:
+        raise ValueError("eval_f_g_grad_samples: nodes and weights must be vectors of the same length, not %r and %r" % (nodes.shape, weights.shape))
+    if nodes.size < 1:
+        raise ValueError("eval_f_g_grad_samples: need at least one node")
+    sh = None
+    if shift is not None:
+        if np.shape(shift) != (int(params.Ntot),):
+            raise ValueError("eval_f_g_grad_samples: shift must have one entry per level, not shape %r" % (np.shape(shift),))
+        sh = _f64(shift)
+    nodes, weights = _f64(nodes), _f64(weights)
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    out2 = np.zeros(2)
+    ig = np.zeros(tab.size) if compute_adjoint else None
+    lg = np.zeros(tab.size) if compute_adjoint else None
+    _lib.check(L.jq_eval_f_g_grad_samples(h, _ptr(tab), shape[1], _ptr(nodes), _ptr(weights), nodes.size, _ptr(sh), 1 if compute_adjoint else 0,
+                                          _ptr(out2), _ptr(ig), _ptr(lg)), h)
+    r = dict(infidelity=float(out2[0]), leak=float(out2[1]))
+    if compute_adjoint:
+        r["infid_grad"], r["leak_grad"] = ig.reshape(shape, order="F"), lg.reshape(shape, order="F")
+    return r
 
 
 def tikhonov_hessvec(d, tik0):
