@@ -681,8 +681,27 @@ int jq_traceobj_sweep(jq_handle *h, const double *pcof, int32_t ncoeff, const do
  * Errors: JQ_EINVAL for NULL required pointers, nt != 2 nsteps + 1, a sample that is not finite, nquad < 1.  JQ_EUNSUPPORTED for
  * uncoupled controls (their operators are driven by ft = 2 (p cos(2 pi Rfreq t) - q sin(2 pi Rfreq t)), a function of both slots: a
  * lab-frame sample interface is a later step), and whatever jq_traceobjgrad refuses for the handle's settings.  A refused call writes
- * nothing and leaves the handle as it was.  Multi-device handles run these calls on their first device.  Not served: Hessian-vector
- * products in sample space, batches of sample tables, drift or mix members with samples, device pointers, sharding over devices.
+ * nothing and leaves the handle as it was.  Multi-device handles run these calls on their first device.  Not served: batches of
+ * sample tables, drift or mix members with samples, device pointers, sharding over devices.
+ *
+ * jq_eval_f_g_grad_samples_hvp: jq_eval_f_g_grad_samples with its gradients, and Hessian-vector products in sample space -- the semantics
+ * of jq_eval_f_g_grad_hvp with "coefficient" read as "sample":
+ *   hv_infid[:, :, j] = d/d eps infid_grad(pq + eps dirs[:, :, j]),  hv_leak[:, :, j] = d/d eps leak_grad(pq + eps dirs[:, :, j])  at eps = 0,
+ * the exact derivatives of the two gradients jq_eval_f_g_grad_samples returns, Neumann truncation included and not symmetrised
+ * (objFuncType 1: hv_infid is the total gradient's derivative, hv_leak zero-filled).  A table is linear in itself, so the tangent
+ * stream of a direction is the stream of its table with a zero drift: the tangent-linear time-loop kernels, the routes (lane, row-lane,
+ * quad, sequential -- a table never changes the route), the budget and the rounds are those of jq_eval_f_g_grad_hvp; only the two small
+ * kernels that turn tables into operator streams and trace records into gradients differ.  A single evaluation is nquad = 1 with node
+ * 0 and weight 1.
+ *   dirs : ndir tables, each [2 Nc x nt] column-major (the layout of pq), one after the other
+ *   infid_grad / leak_grad : [2 Nc x nt];  hv_infid / hv_leak : [2 Nc x nt x ndir]
+ * jq_plan_info reports "sampled_hvp": {route, directions_per_launch, chunk_steps, rounds, time_points, nodes} after such a call
+ * (additive key; "ens_hvp" and "hvp" keep the values of the coefficient calls); jq_last_timing and "last_kernels" as for
+ * jq_eval_f_g_grad_hvp.  Errors: JQ_EINVAL for NULL required pointers (every output is required), nt != 2 nsteps + 1, ndir < 1, nquad < 1,
+ * an entry of pq or dirs that is not finite.  JQ_EUNSUPPORTED for what jq_eval_f_g_grad_hvp refuses (the implicit-midpoint integrator,
+ * the Jacobi solver, full leakage weights, sv_type != 1, uncoupled controls).  A refused call writes nothing and leaves the handle as it
+ * was.  Multi-device handles run the call on their first device.  Not served: products over drift or member ensembles, batches of
+ * tables, device pointers, sharding over devices.
  */
 int jq_sample_times(const jq_handle *h, double *t, int32_t nt);
 int jq_control_samples(jq_handle *h, const double *pcof, int32_t ncoeff, double *pq);
@@ -690,6 +709,9 @@ int jq_traceobjgrad_samples(jq_handle *h, const double *pq, int32_t nt, int32_t 
                             double *infidelgrad, double *leakgrad);
 int jq_eval_f_g_grad_samples(jq_handle *h, const double *pq, int32_t nt, const double *nodes, const double *weights, int32_t nquad,
                              const double *shift, int32_t compute_adjoint, double *out2, double *infid_grad, double *leak_grad);
+int jq_eval_f_g_grad_samples_hvp(jq_handle *h, const double *pq, int32_t nt, const double *dirs, int32_t ndir, const double *nodes,
+                                 const double *weights, int32_t nquad, const double *shift, double *out2, double *infid_grad,
+                                 double *leak_grad, double *hv_infid, double *hv_leak);
 
 /* ---- introspection ---------------------------------------------------------------------------*/
 /*

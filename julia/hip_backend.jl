@@ -469,6 +469,27 @@ function eval_f_g_grad_samples(pq::Matrix{Float64}, params::objparams, wa::Abstr
                       wa.handle, pq, size(pq, 2), nodes, weights, nq, shift === nothing ? C_NULL : pointer(shift), compute_adjoint ? 1 : 0, out2, ig, lg))
     return (infidelity = out2[1], leak = out2[2], infid_grad = ig, leak_grad = lg)
 end
+# eval_f_g_grad_samples and the derivative of its two gradients along direction tables (jq_eval_f_g_grad_samples_hvp): Hessian-vector
+# products in sample space, eval_f_g_grad_hvp with "coefficient" read as "sample" -- exact derivatives of the gradients the library
+# returns, truncated Neumann series included, never symmetrised.  dirs: one table like pq or [2 Nc, nt, ndir].  A table never changes the
+# route (jq_plan_info "sampled_hvp").  Returns (infidelity, leak, infid_grad[2 Nc, nt], leak_grad[2 Nc, nt], hv_infid[2 Nc, nt, ndir],
+# hv_leak[2 Nc, nt, ndir]); objFuncType == 1: infid_grad / hv_infid carry the total gradient's, leak_grad / hv_leak are zero.
+function eval_f_g_grad_samples_hvp(pq::Matrix{Float64}, dirs::Union{Matrix{Float64}, Array{Float64, 3}}, params::objparams, wa::AbstractWorkingArraysHIP,
+                                   nodes::Vector{Float64} = [0.0], weights::Vector{Float64} = [1.0], shift::Union{Nothing, Vector{Float64}} = nothing)
+    size(pq) == (2 * params.Ncoupled, 2 * params.nsteps + 1) || throw(DimensionMismatch("eval_f_g_grad_samples_hvp: pq must be 2 Ncoupled x (2 nsteps + 1)"))
+    D = dirs isa Matrix ? reshape(dirs, size(dirs, 1), size(dirs, 2), 1) : dirs
+    nd = size(D, 3)
+    (size(D, 1) == size(pq, 1) && size(D, 2) == size(pq, 2) && nd >= 1) || throw(DimensionMismatch("eval_f_g_grad_samples_hvp: dirs must be one table like pq or 2 Ncoupled x (2 nsteps + 1) x ndir, ndir >= 1"))
+    nq = length(nodes)
+    (nq >= 1 && length(weights) == nq) || throw(ArgumentError("eval_f_g_grad_samples_hvp: nodes and weights must have the same length >= 1"))
+    sync!(wa, params)
+    out2 = zeros(2); ig = zeros(size(pq)); lg = zeros(size(pq)); hvi = zeros(size(D)); hvl = zeros(size(D))
+    jqcheck(wa, ccall((:jq_eval_f_g_grad_samples_hvp, libjq), Cint,
+                      (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64},
+                       Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                      wa.handle, pq, size(pq, 2), D, nd, nodes, weights, nq, shift === nothing ? C_NULL : pointer(shift), out2, ig, lg, hvi, hvl))
+    return (infidelity = out2[1], leak = out2[2], infid_grad = ig, leak_grad = lg, hv_infid = hvi, hv_leak = hvl)
+end
 
 # Many control vectors of ONE problem in one call (jq_traceobjgrad_batch): column i of every result is what
 # traceobjgrad(pcofs[:, i], params, wa, false, evaladjoint) returns.  On the latency kernels (row-lane, cooperative quad; Stormer-Verlet)

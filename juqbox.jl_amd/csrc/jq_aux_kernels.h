@@ -1,7 +1,8 @@
 // jq_aux_kernels.h -- the small kernels around the propagators: on-device control evaluation
 // (bcarrier2), K(t)/S(t) tile-stream generation, state initialisation, fidelity + adjoint terminal
 // condition, trace reduction and gradient assembly (gradbcarrier2! as an 18-entry scatter); the siblings of the control evaluation and
-// of the assembly for controls given as samples on the time grid (k_ctrl_samples, k_gradsamples).
+// of the assembly for controls given as samples on the time grid (k_ctrl_samples, k_gradsamples) and their batched forms for the
+// tangent-linear sweeps (k_ctrl_samples_grouped, k_gradsamples_grouped).
 #pragma once
 #include "jq_kernels.h"
 #include "jq_rowlane_kernels.h"
@@ -552,6 +553,58 @@ __global__ void k_gradsamples(const double* __restrict__ R, int nsteps_chunk, do
     const int J = J0 - j;
     if (J < 0 || J >= nt) return;
     const int ntr = ng * JQ_NTR;
+    double acc = 0.0;
+    if (j & 1) {
+        const double* r = R + (size_t)(j >> 1) * ntr + c * JQ_NTR;
+        acc = h * (isq ? -r[4] : r[3]);
+    } else {
+        const int m = j >> 1;
+        bool first = true;
+        if (m < nsteps_chunk) {      // point 2 m of step m
+            const double* r = R + (size_t)m * ntr + c * JQ_NTR;
+            acc = h * (isq ? -r[0] : -r[1]);
+            first = false;
+        }
+        if (m >= 1) {                // point 2 (m - 1) + 2 of step m - 1
+            const double* r = R + (size_t)(m - 1) * ntr + c * JQ_NTR;
+            const double v = h * (isq ? -r[2] : -r[1]);
+            acc = first ? v : acc + v;
+        }
+    }
+    G[(size_t)J * 2 * Nc + 2 * (q0 + c) + isq] += acc;
+}
+
+// The batched forms for the tangent-linear sweeps (jq_eval_f_g_grad_samples_hvp, jq_host_tl.h): siblings, so that the two launches of
+// run_eval above stay the code they were.  A table is linear in itself: the tangent stream of a direction table V is the stream of V
+// with a zero drift image, and the assembly of the tangent records is the assembly of the primal ones.
+
+// grid.y = the streams [primal table | direction table ...]: table g is read tstride doubles behind the one before and written to the pq
+// block g ([g][ntp][2 Nc], what k_stream reads for a grouped chunk); index map and bounds of k_ctrl_samples
+__global__ void k_ctrl_samples_grouped(const double* __restrict__ S, long long tstride, int nt, int J0, int dir, int ntp, int Nc, double* __restrict__ pq)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= ntp) return;
+    const int J = J0 + dir * j;
+    if (J < 0 || J >= nt) return;
+    S += (size_t)blockIdx.y * (size_t)tstride;
+    pq += (size_t)blockIdx.y * ntp * 2 * Nc;
+    for (int f = 0; f < 2 * Nc; ++f) pq[(size_t)j * 2 * Nc + f] = S[(size_t)J * 2 * Nc + f];
+}
+
+// grid.y = the gradient blocks [primal | direction ...]: block g assembles record g of R ([g][nsteps_chunk][ng][JQ_NTR], k_trace_reduce's
+// grouped output) with ONE += into its own table, gstride doubles behind the one before; arithmetic, order and bounds of k_gradsamples
+__global__ void k_gradsamples_grouped(const double* __restrict__ R, int nsteps_chunk, double h, double* G, long long gstride, int nt, int J0, int Nc, int q0, int ng)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int ntp = 2 * nsteps_chunk + 1;
+    if (i >= (long long)ntp * ng * 2) return;
+    const int j = (int)(i / (2 * ng)), rem = (int)(i - (long long)j * 2 * ng);
+    const int c = rem >> 1, isq = rem & 1;
+    const int J = J0 - j;
+    if (J < 0 || J >= nt) return;
+    const int ntr = ng * JQ_NTR;
+    R += (size_t)blockIdx.y * nsteps_chunk * ntr;
+    G += (size_t)blockIdx.y * (size_t)gstride;
     double acc = 0.0;
     if (j & 1) {
         const double* r = R + (size_t)(j >> 1) * ntr + c * JQ_NTR;

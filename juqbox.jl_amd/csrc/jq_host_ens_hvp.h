@@ -36,6 +36,10 @@
 // ([member 0 .. P - 1 | member 0: direction ... | member 1: ...], PropArgs::tl_dirs_per_member), k_ctrl mixes every stream with the mix of
 // its member, and the traces of a member are reduced apart with its mix (k_trace_reduce) into gradient blocks of their own, which the
 // host adds in member order.  A mix never changes the route: operators and structure are the handle's.
+//
+// jq_eval_f_g_grad_samples_hvp (jq_host_samples.h) -- the eps ensemble with the controls and the directions given as sample tables on the
+// time grid (EnsHvpArgs::sampled): the same driver, routes, budget and rounds with blocks of 2 Nc nt doubles where the coefficient blocks
+// are; tl_generate and tl_reduce_chunk launch the sample kernels instead of k_ctrl and k_gradacc.  A table never changes the route.
 static double ens_hvp_shift(const double* shift, int i) { return shift ? shift[i] : (i >= 1 ? 0.01 * pow(10.0, (double)(i - 1)) : 0.0); }
 
 struct EnsHvpArgs {
@@ -46,6 +50,9 @@ struct EnsHvpArgs {
     double *out2, *infid_grad, *leak_grad, *hv_infid, *hv_leak;
     const double* mix = nullptr;      // HOST [Nc x Nc x nquad] control mixes of the members (NULL: none); with drifts == NULL the members have the handle's drift
     bool member_call = false;         // jq_eval_f_g_grad_members_hvp runs: the call is recorded as "member_hvp" of jq_plan_info, not as "drift_hvp"
+    // jq_eval_f_g_grad_samples_hvp runs (jq_host_samples.h): pcof and dirs are sample tables [2 Nc x nt], ncoeff = 2 Nc nt, the gradients and products
+    // are those with respect to the samples; nodes only (no drifts, no mix).  The call is recorded as "sampled_hvp" of jq_plan_info.
+    bool sampled = false;
 };
 // the four outputs from the forced (g0, v0) and unforced (g1, v1; objFuncType != 1 only) gradients and products (out_grads' rule)
 static void ens_hvp_outputs(const jq_handle* h, const EnsHvpArgs& x, const double* g0, const double* g1, const double* v0, const double* v1)
@@ -178,7 +185,7 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
     };
     if (mrounds == 1 && (rc = upload_samples(0))) return rc;
 
-    const TlGen gen = {tl_spline(h, d_pc.p, ncoeff, nullptr), lay.himg, d_h0.p, d_pq.p, d_stream.p, stride, b.gstride, nvec, d_mix.p, d_raw.p};
+    const TlGen gen = {x.sampled ? tl_samples(h, d_pc.p, ncoeff) : tl_spline(h, d_pc.p, ncoeff, nullptr), lay.himg, d_h0.p, d_pq.p, d_stream.p, stride, b.gstride, nvec, d_mix.p, d_raw.p, x.sampled};
     const TlMix mx = {d_mix.p, d_mix.p + (size_t)nvec * ncnc, P};
     PropArgs a;
     memset(&a, 0, sizeof a);
@@ -263,7 +270,7 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
                 hipLaunchKernelGGL(kbwd, sgrid, sblock, lay.lds_bwd, s, a);
                 if ((rc = tm.end())) return rc;
                 tl_reduce_chunk(h, gen.sp, r == 0, d_tr.p, mixed ? wps : nwaves, dpl, n0, nc, 0, Nc, d_R.p, d_R.p + (size_t)PR * cs * ntr, d_g.p + (size_t)pass * ndb * ncoeff,
-                                mixed ? &mx : nullptr);
+                                mixed ? &mx : nullptr, x.sampled);
             }
         }
         HIPCHK(h, hipGetLastError());
@@ -282,7 +289,8 @@ static int ens_hvp_lane(jq_handle* h, const EnsHvpArgs& x, const EnsHvpLayout& l
     }
     x.out2[0] = inf, x.out2[1] = leak;
     ens_hvp_outputs(h, x, g0.data(), g1.data(), v0.data(), v1.data());
-    if (x.member_call)
+    if (x.sampled) h->sampled_hvp = {lay.route, dpl, cs, rounds, 2 * h->nsteps + 1, nquad};
+    else if (x.member_call)
         h->member_hvp = {lay.route, P, dpl, cs, rounds * mrounds, x.drifts != nullptr, mixed};
     else if (members) h->drift_hvp_route = lay.route, h->drift_hvp_members = P, h->drift_hvp_per_launch = dpl, h->drift_hvp_chunk = cs, h->drift_hvp_rounds = rounds * mrounds;
     else h->ens_hvp_route = lay.route, h->ens_hvp_per_launch = dpl, h->ens_hvp_chunk = cs, h->ens_hvp_rounds = rounds;
@@ -306,6 +314,7 @@ static int ens_hvp_sequential(jq_handle* h, const EnsHvpArgs& x)
     double inf = 0.0, leak = 0.0, out4[4];
     jq_timing sum = jq_timing{};
     const int keep[3] = {h->hvp_per_launch, h->hvp_chunk, h->hvp_rounds};      // ("hvp" of jq_plan_info stays jq_traceobjgrad_hvp's)
+    // (sampled: pcof and dirs are sample tables, hvp_run generates and assembles without a basis; a node still only shifts the drift)
     int rc = JQ_OK, dpl = 0, cs = 0, rounds = 0;
     for (int i = 0; i < x.nquad && rc == JQ_OK; ++i) {
         if (x.drifts) drift.assign(x.drifts + (size_t)i * Ntot * Ntot, x.drifts + (size_t)(i + 1) * Ntot * Ntot);      // member i
@@ -314,7 +323,7 @@ static int ens_hvp_sequential(jq_handle* h, const EnsHvpArgs& x)
             for (int j = 0; j < Ntot && !x.mix; ++j) drift[(size_t)j * Ntot + j] += x.nodes[i] * ens_hvp_shift(x.shift, j);      // src/ipopt_interface.jl:41-44
         }
         rc = hvp_run(h, drift.data(), x.pcof, ncoeff, x.dirs, ndir, out4, gi.data(), vi.data(), vin.data(), gin.data(), x.who,
-                     x.mix ? x.mix + (size_t)i * h->Nc * h->Nc : nullptr);
+                     x.mix ? x.mix + (size_t)i * h->Nc * h->Nc : nullptr, x.sampled);
         if (rc != JQ_OK) break;
         const double w = x.weights[i];
         inf += out4[1] * w, leak += out4[2] * w;
@@ -337,7 +346,8 @@ static int ens_hvp_sequential(jq_handle* h, const EnsHvpArgs& x)
     ens_hvp_outputs(h, x, g0.data(), g1.data(), v0.data(), v1.data());
     h->timing = sum;
     h->timing.ms_shard_min = h->timing.ms_shard_max = h->timing.ms_total;
-    if (x.member_call) h->member_hvp = {2, 1, dpl, cs, rounds, x.drifts != nullptr, x.mix != nullptr};
+    if (x.sampled) h->sampled_hvp = {2, dpl, cs, rounds, 2 * h->nsteps + 1, x.nquad};
+    else if (x.member_call) h->member_hvp = {2, 1, dpl, cs, rounds, x.drifts != nullptr, x.mix != nullptr};
     else if (x.drifts) h->drift_hvp_route = 2, h->drift_hvp_members = 1, h->drift_hvp_per_launch = dpl, h->drift_hvp_chunk = cs, h->drift_hvp_rounds = rounds;
     else h->ens_hvp_route = 2, h->ens_hvp_per_launch = dpl, h->ens_hvp_chunk = cs, h->ens_hvp_rounds = rounds;
     return JQ_OK;

@@ -15,8 +15,10 @@
 // point that runs.  mix (may be NULL; jq_eval_f_g_grad_members_hvp's sequential route: a member's): the HOST Nc x Nc control mix, column-major --
 // operator l is driven by sum_k C[l, k] (p_k, q_k), in the primal stream and in every direction's; k_ctrl and the reducer see it, the
 // operators stay the handle's.  A control group's sweep then contributes to the coefficients of ALL controls (k_trace_reduce's q0).
+// sampled (jq_eval_f_g_grad_samples_hvp's sequential route; never with a mix): pcof and the directions are sample tables [2 Nc x nt] on the
+// time grid, ncoeff = 2 Nc nt, and grad, hv are with respect to the samples (TlGen::sampled); a control group adds its own columns.
 static int hvp_run(jq_handle* h, const double* drift, const double* pcof, int ncoeff, const double* dirs, int ndir, double* out4, double* grad, double* hv,
-                   double* hv_infid, double* grad_infid = nullptr, const char* who = "jq_traceobjgrad_hvp", const double* mix = nullptr)
+                   double* hv_infid, double* grad_infid = nullptr, const char* who = "jq_traceobjgrad_hvp", const double* mix = nullptr, bool sampled = false)
 {
     HIPCHK(h, hipSetDevice(h->device));
     const int NT = (h->Ntot + 15) / 16, KT = 4 * NT, Nc = h->Nc, parts = h->parts;
@@ -63,7 +65,7 @@ static int hvp_run(jq_handle* h, const double* drift, const double* pcof, int nc
         HIPCHK(h, hipMemcpyAsync(d_mix.p, mixes.data(), mixes.size() * sizeof(double), hipMemcpyHostToDevice, s));
     }
     const TlMix mx = {d_mix.p, d_mix.p, 1};
-    const TlGen gen = {tl_spline(h, d_pc.p, ncoeff, nullptr), d_img.p, d_h0.p, d_pq.p, d_stream.p, stride, b.gstride, nvec, d_mix.p, d_raw.p};
+    const TlGen gen = {sampled ? tl_samples(h, d_pc.p, ncoeff) : tl_spline(h, d_pc.p, ncoeff, nullptr), d_img.p, d_h0.p, d_pq.p, d_stream.p, stride, b.gstride, nvec, d_mix.p, d_raw.p, sampled};
     PropArgs a = tl_prop_args(h, gen, dpl, d_state.p, sstride, d_work.p, d_wd.p);
     a.traces = d_tr.p;
 
@@ -98,7 +100,7 @@ static int hvp_run(jq_handle* h, const double* drift, const double* pcof, int nc
                 hipLaunchKernelGGL(k_backward_tl<>, dim3(nblocks), dim3(64 * JQ_HUGE_WAVES), 0, s, a);
                 if ((rc = tm.end())) return rc;
                 tl_reduce_chunk(h, gen.sp, r == 0, d_tr.p, rows, dpl, n0, nc, q0, ng, d_R.p, d_R.p + (size_t)cs * ntr_R, d_g.p + (size_t)pass * nvec * ncoeff,
-                                mix ? &mx : nullptr);
+                                mix ? &mx : nullptr, sampled);
                 mfma_bwd += (long long)nblocks * nc * (6 * (8 + 2 * h->m) + 8 * ng) * NT * KT;      // (two MFMAs per tile of a trace product)
                 if (n0 == 0) mfma_bwd += (long long)nblocks * 2 * ng * NT * KT;
             }

@@ -216,6 +216,12 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
     // jq_traceobjgrad_samples / jq_eval_f_g_grad_samples (after a call): time points of the sample table, nodes, steps per chunk
     if (h->sc_nt > 0)
         kv("sampled_controls", std::string("{\"time_points\": ") + num(h->sc_nt) + ", \"nodes\": " + num(h->sc_nodes) + ", \"chunk_steps\": " + num(h->sc_chunk) + "}");
+    // jq_eval_f_g_grad_samples_hvp (after a call): the route its nodes took, the three of "ens_hvp", time points of the tables, nodes
+    if (h->sampled_hvp.route > 0) {
+        const jq_handle::SampledHvp& m = h->sampled_hvp;
+        kv("sampled_hvp", std::string("{\"route\": \"") + (m.route == 1 ? "lane" : m.route == 3 ? "rowlane" : m.route == 4 ? "quad" : "sequential") + "\", \"directions_per_launch\": " + num(m.per_launch) +
+                            ", \"chunk_steps\": " + num(m.chunk) + ", \"rounds\": " + num(m.rounds) + ", \"time_points\": " + num(m.nt) + ", \"nodes\": " + num(m.nodes) + "}");
+    }
     o += "}";
     if (buflen > 0) {
         const size_t n = std::min(o.size(), (size_t)buflen - 1);

@@ -1,5 +1,6 @@
 // jq_host_samples.h -- part of the host side of libjuqbox_hip.so (included by juqbox_hip.hip, ONE translation unit; not a stand-alone header):
-// controls given as samples on the time grid -- jq_sample_times, jq_control_samples, jq_traceobjgrad_samples, jq_eval_f_g_grad_samples.
+// controls given as samples on the time grid -- jq_sample_times, jq_control_samples, jq_traceobjgrad_samples, jq_eval_f_g_grad_samples,
+// and jq_eval_f_g_grad_samples_hvp (at the end: Hessian-vector products along direction tables, through the drivers of jq_host_ens_hvp.h).
 // The time loops see the table pq[time point][2 Nc] and the trace records R only; the parameterisation lives in k_ctrl and k_gradacc.  These
 // entry points put k_ctrl_samples / k_gradsamples (jq_aux_kernels.h) in their place through EvalRequest::samples: the objective of a
 // caller-given table and its gradient with respect to every entry, from the sweeps, the plan and the kernels of jq_traceobjgrad.
@@ -108,5 +109,34 @@ extern "C" int jq_eval_f_g_grad_samples(jq_handle* h, const double* pq, int32_t 
         out2[1] = leak;
         if (compute_adjoint) out_grads(h, rq.ncoeff, o.grad0.data(), o.grad1.data(), nullptr, infid_grad, leak_grad);
         return JQ_OK;
+    });
+}
+
+// jq_eval_f_g_grad_samples and the derivative of its two gradients along direction tables: jq_eval_f_g_grad_hvp (jq_host_ens_hvp.h) with
+// "coefficient" read as "sample".  The tangent-linear time loops read a primal operator stream and one stream per direction and write
+// trace records and their tangents; the parameterisation lives in tl_generate and tl_reduce_chunk (jq_host_tl.h), which EnsHvpArgs::sampled
+// switches to k_ctrl_samples_grouped / k_gradsamples_grouped.  A table never changes the route: lane, row-lane, quad or sequential exactly
+// as for coefficients, on the same propagator kernels.
+extern "C" int jq_eval_f_g_grad_samples_hvp(jq_handle* h, const double* pq, int32_t nt, const double* dirs, int32_t ndir, const double* nodes,
+                                            const double* weights, int32_t nquad, const double* shift, double* out2, double* infid_grad,
+                                            double* leak_grad, double* hv_infid, double* hv_leak)
+{
+    if (!h) return JQ_EINVAL;
+    return abi_guard(h, "jq_eval_f_g_grad_samples_hvp", [&]() -> int {
+        if (!pq || !dirs || !nodes || !weights || !out2 || !infid_grad || !leak_grad || !hv_infid || !hv_leak)
+            return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_samples_hvp: NULL pointer");
+        if (ndir < 1) return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_samples_hvp: ndir must be >= 1");
+        if (nquad < 1) return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_samples_hvp: nquad must be >= 1");
+        JQ_ON_FIRST(h, jq_eval_f_g_grad_samples_hvp(s0_, pq, nt, dirs, ndir, nodes, weights, nquad, shift, out2, infid_grad, leak_grad, hv_infid, hv_leak))
+        if (int rc = tl_refuse(h, "jq_eval_f_g_grad_samples_hvp", true)) return rc;
+        if (int rc = samples_refuse(h, "jq_eval_f_g_grad_samples_hvp")) return rc;
+        if (int rc = samples_args(h, "jq_eval_f_g_grad_samples_hvp", pq, nt)) return rc;
+        const size_t len = (size_t)2 * h->Nc * nt;
+        for (size_t e = 0; e < len * (size_t)ndir; ++e)
+            if (!std::isfinite(dirs[e])) return fail(h, JQ_EINVAL, "jq_eval_f_g_grad_samples_hvp: an entry of a direction table is not finite");
+        EvalGate gate(h);
+        EnsHvpArgs x = {"jq_eval_f_g_grad_samples_hvp", pq, dirs, nodes, weights, shift, nullptr, (int)len, ndir, nquad, out2, infid_grad, leak_grad, hv_infid, hv_leak};
+        x.sampled = true;
+        return ens_hvp_dispatch(h, x);
     });
 }

@@ -80,6 +80,9 @@ static TlBudget tl_budget(const jq_handle* h, size_t stride, int ndir, int dir_c
 // The generators of a chunk's 1 + dpl streams: k_ctrl over the coefficient blocks in sp.pcof, k_stream over the operator images
 // himg = [H0 | Hsym_q | Hanti_q] with the groups' drift images h0 = [H0 | 0 ...].  dt > 0: the forward time table, dt < 0: the backward one.
 // mix (NULL: none, the launches they always were): one Nc x Nc control mix per group for k_ctrl, raw: its unmixed values in pq's layout.
+// sampled (jq_eval_f_g_grad_samples_hvp): the blocks in sp.pcof are sample tables [2 Nc x nt] on the time grid (tl_samples), sp.nCoeff
+// = 2 Nc nt doubles apart, and k_ctrl_samples_grouped takes the place of k_ctrl -- a table is linear in itself, so the stream of a
+// direction table with a zero drift image is its tangent stream; no mix.
 struct TlGen {
     SplineArgs sp;
     const double *himg, *h0;
@@ -88,6 +91,7 @@ struct TlGen {
     int nvec;
     const double* mix = nullptr;
     double* raw = nullptr;
+    bool sampled = false;
 };
 static SplineArgs tl_spline(const jq_handle* h, const double* d_pcof, int ncoeff, const double* d_rfreq)
 {
@@ -97,10 +101,23 @@ static SplineArgs tl_spline(const jq_handle* h, const double* d_pcof, int ncoeff
     sp.rfreq = d_rfreq;
     return sp;
 }
+// the blocks of sample tables in the place of the coefficient blocks: only pcof and nCoeff (the table stride) are read
+static SplineArgs tl_samples(const jq_handle* h, const double* d_tables, int ncoeff)
+{
+    SplineArgs sp;
+    sp.pcof = d_tables; sp.cfreq = h->d_cfreq; sp.D1 = 0; sp.Nfreq = h->Nfreq; sp.Ncoupled = h->Nc; sp.nCoeff = ncoeff;
+    sp.dtknot = 0.0;
+    sp.rfreq = nullptr;
+    return sp;
+}
 static void tl_generate(const jq_handle* h, const TlGen& g, int n0, int nc, double dt)
 {
     const int ntp = 2 * nc + 1;
-    hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, g.nvec), dim3(128), 0, h->stream, g.sp, dt > 0 ? h->d_tf : h->d_tb, n0, ntp, dt, g.pq, g.mix, g.raw);
+    if (g.sampled)      // (run_eval's index map: a forward chunk reads the table upwards from 2 n0, a backward one downwards from 2 (nsteps - n0))
+        hipLaunchKernelGGL(k_ctrl_samples_grouped, dim3((ntp + 127) / 128, g.nvec), dim3(128), 0, h->stream, g.sp.pcof, (long long)g.sp.nCoeff, 2 * h->nsteps + 1,
+                           dt > 0 ? 2 * n0 : 2 * (h->nsteps - n0), dt > 0 ? 1 : -1, ntp, h->Nc, g.pq);
+    else
+        hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, g.nvec), dim3(128), 0, h->stream, g.sp, dt > 0 ? h->d_tf : h->d_tb, n0, ntp, dt, g.pq, g.mix, g.raw);
     hipLaunchKernelGGL(k_stream, dim3((unsigned)((g.stride + 255) / 256), ntp, g.nvec), dim3(256), 0, h->stream, g.himg, g.h0, (long long)g.stride, g.pq, h->Nc,
                        (long long)g.stride, 0.5 * dt, g.stream, (long long)g.gstride);
 }
@@ -237,12 +254,14 @@ static long long tl_forward_mfma(const jq_handle* h, int rounds, int nblocks)
 // then hold rows for ALL Nc controls and the assembly covers all of them, the other control groups add theirs in their sweeps (run_eval's
 // rule) -- into gradient blocks of their own, gp = [member 0 .. P - 1 | direction 0: member 0 .. P - 1 | direction 1: ...][ncoeff], for
 // the caller to add in member order (tl_fold_members).  primal: [C_0 .. C_{P - 1}], dirs: that dpl times.
+// sampled (TlGen::sampled; never with mx): gp = [primal | direction ...][2 Nc nt] are gradients with respect to the samples, assembled by
+// k_gradsamples_grouped from the same records.
 struct TlMix {
     const double *primal, *dirs;
     int P;
 };
 static void tl_reduce_chunk(const jq_handle* h, const SplineArgs& sp, bool primal, const double* tr, int rows, int dpl, int n0, int nc, int q0, int ng, double* R,
-                            double* Rd, double* gp, const TlMix* mx = nullptr)
+                            double* Rd, double* gp, const TlMix* mx = nullptr, bool sampled = false)
 {
     const int ntr = ng * JQ_NTR, P = mx ? mx->P : 1;
     const int ntr_R = mx ? h->Nc * JQ_NTR : ntr, gq0 = mx ? 0 : q0, gng = mx ? h->Nc : ng;
@@ -250,6 +269,17 @@ static void tl_reduce_chunk(const jq_handle* h, const SplineArgs& sp, bool prima
     const unsigned rblocks = (unsigned)(((long long)nc * ntr_R + 255) / 256), gblocks = (unsigned)(gng * 2 * h->Nfreq * sp.D1);
     const double* trd = tr + (size_t)dpl * P * rows * nc * ntr;      // the tangents' record (k_backward_tl, k_backward_lane_tl)
     hipStream_t s = h->stream;
+    if (sampled) {
+        const int nt = 2 * h->nsteps + 1, J0 = 2 * (h->nsteps - n0);
+        const unsigned sblocks = (unsigned)(((long long)(2 * nc + 1) * ng * 2 + 255) / 256);
+        if (primal) {
+            hipLaunchKernelGGL(k_trace_reduce, dim3(rblocks, 1), dim3(256), 0, s, tr, rows, nc, ntr, R, (const double*)nullptr, h->Nc, q0);
+            hipLaunchKernelGGL(k_gradsamples_grouped, dim3(sblocks, 1), dim3(256), 0, s, (const double*)R, nc, -dt, gp, (long long)sp.nCoeff, nt, J0, h->Nc, q0, ng);
+        }
+        hipLaunchKernelGGL(k_trace_reduce, dim3(rblocks, dpl), dim3(256), 0, s, trd, rows, nc, ntr, Rd, (const double*)nullptr, h->Nc, q0);
+        hipLaunchKernelGGL(k_gradsamples_grouped, dim3(sblocks, dpl), dim3(256), 0, s, (const double*)Rd, nc, -dt, gp + sp.nCoeff, (long long)sp.nCoeff, nt, J0, h->Nc, q0, ng);
+        return;
+    }
     if (primal) {
         hipLaunchKernelGGL(k_trace_reduce, dim3(rblocks, P), dim3(256), 0, s, tr, rows, nc, ntr, R, mx ? mx->primal : (const double*)nullptr, h->Nc, q0);
         hipLaunchKernelGGL(k_gradacc, dim3(gblocks, P), dim3(JQ_GRADACC_THREADS), 0, s, sp, (const double*)R, h->d_tb, n0, nc, -dt, gp, gq0, gng, (long long)sp.nCoeff);

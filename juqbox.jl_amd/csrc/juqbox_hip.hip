@@ -206,6 +206,11 @@ struct jq_handle {
     // ... and the last evaluation with sampled controls (jq_traceobjgrad_samples / jq_eval_f_g_grad_samples): time points of the table,
     // nodes, chunk length (jq_plan_info "sampled_controls"; sc_nt 0: no call yet)
     int sc_nt = 0, sc_nodes = 0, sc_chunk = 0;
+    // ... and the last jq_eval_f_g_grad_samples_hvp: its route (the codes of ens_hvp_route), directions per launch, chunk length, rounds,
+    // time points of the tables, nodes (jq_plan_info "sampled_hvp"; route 0: no call yet)
+    struct SampledHvp {
+        int route = 0, per_launch = 0, chunk = 0, rounds = 0, nt = 0, nodes = 0;
+    } sampled_hvp;
     // Structure embedding (try_embed): a second handle of the SAME problem with its two fastest Kronecker factors zero-padded
     // to 4 levels each (row i1 + d1 i2 + d1 d2 i3 -> i1 + 4 i2 + 16 i3), under which the operators have the JQ_BW_T4 structure;
     // batches that would otherwise run on the dense / band MFMA kernels go there (quad-layout / JQ_BW_T4 slab kernels).
@@ -720,11 +725,11 @@ extern "C" int jq_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int32_t
     });
 }
 
-#include "jq_host_samples.h"      // controls given as samples on the time grid: the objective of a table pq and its gradient per entry
 #include "jq_host_tl.h"      // what the drivers of the tangent-linear sweeps share: budgeting, stream generation, trace reduction, timing
 #include "jq_host_jvp.h"      // jq_traceobj_jvp: the tangent of the forward map along directions of coefficient space
 #include "jq_host_hvp.h"      // jq_traceobjgrad_hvp: the derivative of the gradient along directions of coefficient space
 #include "jq_host_ens_hvp.h"      // jq_eval_f_g_grad_hvp: the same over the nodes of a risk-neutral ensemble (lane / row-lane kernels: one launch per chunk)
+#include "jq_host_samples.h"      // controls given as samples on the time grid: the objective of a table pq, its gradient per entry, and (through the drivers above) Hessian-vector products along direction tables
 #include "jq_host_multi.h"      // multi-device handles: one process, N GPUs, one RCCL all-reduce
 #include "jq_host_info.h"      // options of a live handle, plan and timing introspection
 #ifdef JQ_DUMP_SELECTION

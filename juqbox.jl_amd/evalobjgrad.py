@@ -32,6 +32,9 @@
                                         traceobjgrad for controls given as values on the time grid (jq_traceobjgrad_samples): the
                                         objective of a 2 Ncoupled x (2 nsteps + 1) table and its gradient per entry -- any
                                         parameterisation is then a chain rule on the host.
+  traceobjgrad_samples_hvp(pq, dirs, params, wa)
+                                        its gradient and the derivative of that gradient along direction tables
+                                        (jq_eval_f_g_grad_samples_hvp, one node): Hessian-vector products in sample space.
   control_sample_times(params, wa), control_samples(pcof, params, wa), spline_sample_matrix(params, ncoeff, times)
                                         the grid, the library's own controls on it, and their dense derivative d pq / d pcof.
 """
@@ -779,6 +782,39 @@ def traceobjgrad_samples(pq, params: objparams, wa: Working_Arrays_HIP, evaladjo
     _lib.check(L.jq_traceobjgrad_samples(h, _ptr(tab), shape[1], 1, _ptr(out4), _ptr(tg), _ptr(ig), _ptr(lg)), h)
     leak = np.zeros((0, 0)) if params.objFuncType == 1 else lg.reshape(shape, order="F")
     return out4[0], tg.reshape(shape, order="F"), out4[1], out4[2], out4[3], ig.reshape(shape, order="F"), leak
+
+
+def _direction_tables(dirs, params, who):
+    """dirs -> the flat [ndir][2 Nc x nt] stack of column-major tables of the C ABI and ndir.  One table (the shape of pq) or a stack
+    (2 Ncoupled, 2 nsteps + 1, ndir); ValueError for another shape or entries that are not finite"""
+    shape = (2 * int(params.Ncoupled), 2 * int(params.nsteps) + 1)
+    try:
+        d = np.asarray(dirs, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("%s: dirs must be a table like pq or a stack of tables (%s)" % (who, e))
+    if d.ndim == 2:
+        d = d[:, :, None]
+    if d.ndim != 3 or d.shape[:2] != shape or d.shape[2] < 1:
+        raise ValueError("%s: dirs has shape %r, expected %r or %r with ndir >= 1" % (who, np.shape(dirs), shape, shape + ("ndir",)))
+    if not np.all(np.isfinite(d)):
+        raise ValueError("%s: dirs has an entry that is not finite" % who)
+    return _f64(d), d.shape[2]
+
+
+def traceobjgrad_samples_hvp(pq, dirs, params: objparams, wa: Working_Arrays_HIP):
+    """The gradient of traceobjgrad_samples at the table pq and its derivative along direction tables (Hessian-vector products in
+    sample space) in one library call: the one-node form of eval_f_g_grad_samples_hvp (jq_eval_f_g_grad_samples_hvp with node 0, weight
+    1).  hv[:, :, j] = d/d eps totalgrad(pq + eps dirs[:, :, j]) at eps = 0, the exact derivative of the gradient the library returns,
+    truncated Neumann series included -- not symmetric at truncation level and never symmetrised (traceobjgrad_hvp).
+
+    dirs: one table in the shape of pq or a stack (2 Ncoupled, 2 nsteps + 1, ndir).  Returns a dict: objfv, primaryobjf, secondaryobjf,
+    totalgrad in the shape of pq, hv and hv_infid (the same for infidelgrad; objFuncType == 1: equal to hv) of shape
+    (2 Ncoupled, 2 nsteps + 1, ndir).  No Tikhonov term.  Shape errors and entries that are not finite raise ValueError before any
+    library call."""
+    from .ipopt_interface import eval_f_g_grad_samples_hvp
+    r = eval_f_g_grad_samples_hvp(pq, dirs, params, wa, _who="traceobjgrad_samples_hvp")
+    return {"objfv": r["infidelity"] + r["leak"], "primaryobjf": r["infidelity"], "secondaryobjf": r["leak"],
+            "totalgrad": r["infid_grad"] + r["leak_grad"], "hv": r["hv_infid"] + r["hv_leak"], "hv_infid": r["hv_infid"]}
 
 
 def spline_sample_matrix(params: objparams, ncoeff: int, times):

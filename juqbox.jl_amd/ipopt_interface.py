@@ -5,7 +5,7 @@ signatures, so any L-BFGS driver can call them)."""
 import numpy as np
 
 from . import _lib
-from .evalobjgrad import Working_Arrays_HIP, _directions, _drift_members, _f64, _members, _pcof_columns, _ptr, _sample_table
+from .evalobjgrad import Working_Arrays_HIP, _directions, _drift_members, _f64, _direction_tables, _members, _pcof_columns, _ptr, _sample_table
 from .setup_utils import tikhonov_grad, tikhonov_pen
 
 
@@ -287,6 +287,51 @@ def eval_f_g_grad_samples(pq, params, wa, nodes=(0.0,), weights=(1.0,), shift=No
     if compute_adjoint:
         r["infid_grad"], r["leak_grad"] = ig.reshape(shape, order="F"), lg.reshape(shape, order="F")
     return r
+
+
+def eval_f_g_grad_samples_hvp(pq, dirs, params, wa, nodes=(0.0,), weights=(1.0,), shift=None, _who="eval_f_g_grad_samples_hvp"):
+    """eval_f_g_grad_samples over the quadrature nodes and the derivative of its two gradients along direction tables in one library call
+    (jq_eval_f_g_grad_samples_hvp): Hessian-vector products in sample space, sum_i w_i d/d eps grad_i(pq + eps dirs[:, :, j]) at eps = 0
+    -- eval_f_g_grad_hvp with "coefficient" read as "sample".  The products are exact derivatives of the gradients eval_f_g_grad_samples
+    returns, truncated Neumann series included: not symmetric at truncation level, and never symmetrised.  The routes are those of
+    eval_f_g_grad_hvp -- a table never changes the route (wa.plan_info()["sampled_hvp"]["route"]: "lane", "rowlane", "quad" or
+    "sequential") -- on the same tangent-linear kernels.  With a parameterisation pq = fn(theta) the second derivative along v is
+    Jfn' Hs (Jfn v) plus the curvature of fn against the sample gradient (torch_controls.sampled_hessvec).
+
+    pq: the 2 Ncoupled x (2 nsteps + 1) table of traceobjgrad_samples; dirs: one such table or a stack (2 Ncoupled, 2 nsteps + 1, ndir).
+    Returns a dict: infidelity, leak, infid_grad, leak_grad in the shape of pq (objFuncType == 1: infid_grad is the total gradient,
+    leak_grad zeros), hv_infid, hv_leak of shape (2 Ncoupled, 2 nsteps + 1, ndir) (objFuncType == 1: hv_infid is the derivative of the
+    total gradient, hv_leak zeros).  No Tikhonov term; params.last_* are left alone.  Shape errors and entries that are not finite raise
+    ValueError before any library call; the library refuses what eval_f_g_grad_hvp refuses, uncoupled controls among it."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("%s: wa must be a Working_Arrays_HIP" % _who)
+    if wa.params is not params:
+        raise ValueError("%s: wa was allocated for a different objparams" % _who)
+    tab, shape = _sample_table(pq, params, _who)
+    D, nd = _direction_tables(dirs, params, _who)
+    try:
+        nodes, weights = np.asarray(nodes, dtype=np.float64), np.asarray(weights, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("%s: nodes and weights must be vectors of numbers (%s)" % (_who, e))
+    if nodes.ndim != 1 or weights.ndim != 1 or nodes.size != weights.size:
+        raise ValueError("%s: nodes and weights must be vectors of the same length, not %r and %r" % (_who, nodes.shape, weights.shape))
+    if nodes.size < 1:
+        raise ValueError("%s: need at least one node" % _who)
+    sh = None
+    if shift is not None:
+        if np.shape(shift) != (int(params.Ntot),):
+            raise ValueError("%s: shift must have one entry per level, not shape %r" % (_who, np.shape(shift)))
+        sh = _f64(shift)
+    nodes, weights = _f64(nodes), _f64(weights)
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    out2 = np.zeros(2)
+    ig, lg = np.zeros(tab.size), np.zeros(tab.size)
+    hvi, hvl = np.zeros(tab.size * nd), np.zeros(tab.size * nd)
+    _lib.check(L.jq_eval_f_g_grad_samples_hvp(h, _ptr(tab), shape[1], _ptr(D), nd, _ptr(nodes), _ptr(weights), nodes.size, _ptr(sh), _ptr(out2),
+                                              _ptr(ig), _ptr(lg), _ptr(hvi), _ptr(hvl)), h)
+    return dict(infidelity=float(out2[0]), leak=float(out2[1]), infid_grad=ig.reshape(shape, order="F"), leak_grad=lg.reshape(shape, order="F"),
+                hv_infid=hvi.reshape(shape + (nd,), order="F"), hv_leak=hvl.reshape(shape + (nd,), order="F"))
 
 
 def tikhonov_hessvec(d, tik0):

@@ -6,12 +6,16 @@
       dJ/dpq as its backward.  Whatever produced pq -- a piecewise-constant pulse through repeat_interleave, an envelope, a filter, a
       torch.nn.Module -- is differentiated by torch; the time loops run in the library.
 
+  sampled_hessvec(fn, theta, v, params, wa, nodes=None, weights=None, shift=None)
+      the derivative along v of the gradient of J(fn(theta)): the library's Hessian-vector product in sample space
+      (eval_f_g_grad_samples_hvp) between torch.func.jvp and vjp of fn, plus the curvature of fn against the sample gradient.
+
 The samples go through host memory (the library's entry points take host pointers); a device-pointer variant is not offered."""
 import numpy as np
 import torch
 
 from .evalobjgrad import traceobjgrad_samples
-from .ipopt_interface import eval_f_g_grad_samples
+from .ipopt_interface import eval_f_g_grad_samples, eval_f_g_grad_samples_hvp
 
 
 class SampledObjective(torch.autograd.Function):
@@ -40,3 +44,42 @@ class SampledObjective(torch.autograd.Function):
     def backward(ctx, grad_output):
         (grad,) = ctx.saved_tensors
         return grad_output * grad, None, None, None, None, None
+
+
+def sampled_hessvec(fn, theta, v, params, wa, nodes=None, weights=None, shift=None):
+    """The derivative, along v, of the gradient of J(fn(theta)) with respect to theta, for a differentiable theta -> pq = fn(theta) (a
+    float64 tensor in the shape of a sample table) and J the objective of SampledObjective:
+
+        d/d eps grad_theta J(fn(theta + eps v)) at eps = 0  =  Jfn' (Hs (Jfn v))  +  d/d eps [ Jfn(theta + eps v)' G ] at eps = 0
+
+    with Jfn the Jacobian of fn at theta, G the library's sample gradient at fn(theta) held constant, and Hs u the library's exact
+    Hessian-vector product in sample space (eval_f_g_grad_samples_hvp).  Computed as
+        u = Jfn v                                  torch.func.jvp of fn,
+        G, Hs u                                    ONE library call,
+        Jfn' (Hs u)                                torch.func.vjp of fn,
+        the second term                            torch.func.jvp of theta -> vjp_fn(theta)(G): the curvature of fn, zero for a linear fn.
+    fn must be composed of torch operations torch.func can differentiate twice.  Returns a tensor in the shape of theta.
+
+    SampledObjective is deliberately NOT twice differentiable through autograd: double backward would need Hs' w, the library gives
+    Hs w, the two differ at truncation level of the Neumann series (traceobjgrad_hvp), and this package never symmetrises silently.
+    This function needs Hs w only, so it returns exactly the derivative of the gradient that SampledObjective's backward returns."""
+    if not isinstance(theta, torch.Tensor) or theta.dtype != torch.float64:
+        raise TypeError("sampled_hessvec: theta must be a float64 tensor")
+    if not isinstance(v, torch.Tensor) or v.dtype != torch.float64 or v.shape != theta.shape:
+        raise TypeError("sampled_hessvec: v must be a float64 tensor in the shape of theta")
+    if (nodes is None) != (weights is None):
+        raise ValueError("sampled_hessvec: give nodes and weights together")
+    theta, v = theta.detach(), v.detach()
+    pq, u = torch.func.jvp(fn, (theta,), (v,))
+    if nodes is None:
+        r = eval_f_g_grad_samples_hvp(pq.to("cpu").numpy(), u.to("cpu").numpy(), params, wa, _who="sampled_hessvec")
+    else:
+        r = eval_f_g_grad_samples_hvp(pq.to("cpu").numpy(), u.to("cpu").numpy(), params, wa, nodes, weights, shift, _who="sampled_hessvec")
+    G = torch.from_numpy(np.ascontiguousarray(r["infid_grad"] + r["leak_grad"])).to(theta.device)
+    Hu = torch.from_numpy(np.ascontiguousarray((r["hv_infid"] + r["hv_leak"])[:, :, 0])).to(theta.device)
+
+    def pullback(th, w):
+        return torch.func.vjp(fn, th)[1](w)[0]
+
+    curvature = torch.func.jvp(lambda th: pullback(th, G), (theta,), (v,))[1]
+    return pullback(theta, Hu) + curvature
