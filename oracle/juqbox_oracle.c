@@ -36,6 +36,18 @@ typedef struct {
     int *rowval;  /* nnz */
 } pattern_t;
 
+/* TEST-ONLY instrumentation of the iterative solvers (jqo_instrument; NULL = off, the default: nothing below changes a number then).
+ * Record: per call of jacobi / jacobi_midpoint, in call order, the iteration count, the exit (tolerance or cap) and the margin
+ * |norm / tol - 1| of every stopping comparison (both norms for jacobi_midpoint).  Bias: the solve with index bias_index (-1: every
+ * solve) performs one iteration more than its rule says (bias_mode +1) or one fewer where the rule's count is >= 2 (bias_mode -1);
+ * tests/test_stopping_matrix.py uses it to show that a comparison would notice such a solver.  The record is the RULE's in both cases. */
+typedef struct {
+    int record, bias_mode, bias_index;
+    int nsolves, cap_solves, nmargins, cap_margins, sample;
+    int *count, *by_cap, *first, *sample_of; /* per solve; first: index of its first margin */
+    double *margins;
+} instr_t;
+
 typedef struct {
     /* problem (objparams fields the path needs: src/evalobjgrad.jl:53-148) */
     int Ntot, N, Ncoupled, Nfreq, nsteps, objFuncType;
@@ -66,7 +78,45 @@ typedef struct {
     double dtknot;
     double *tcenter;
     const double *pcof;
+    instr_t *ins; /* test-only: iteration record and bias (NULL = off) */
 } oracle_t;
+
+static void ins_margin(instr_t *ins, double norm, double tol)
+{
+    if (!ins->record) return;
+    if (ins->nmargins == ins->cap_margins) {
+        ins->cap_margins = ins->cap_margins ? 2 * ins->cap_margins : 1024;
+        ins->margins = (double *)realloc(ins->margins, (size_t)ins->cap_margins * sizeof(double));
+    }
+    ins->margins[ins->nmargins++] = fabs(norm / tol - 1.0);
+}
+
+/* closes the record of a solve (solves are counted whether recording or not: the bias addresses them by their index) */
+static void ins_solve(instr_t *ins, int count, int by_cap, int first)
+{
+    if (ins->record) {
+        if (ins->nsolves == ins->cap_solves) {
+            size_t n = (size_t)(ins->cap_solves = ins->cap_solves ? 2 * ins->cap_solves : 256) * sizeof(int);
+            ins->count = (int *)realloc(ins->count, n);
+            ins->by_cap = (int *)realloc(ins->by_cap, n);
+            ins->first = (int *)realloc(ins->first, n);
+            ins->sample_of = (int *)realloc(ins->sample_of, n);
+        }
+        ins->count[ins->nsolves] = count;
+        ins->by_cap[ins->nsolves] = by_cap;
+        ins->first[ins->nsolves] = first;
+        ins->sample_of[ins->nsolves] = ins->sample;
+    }
+    ins->nsolves++;
+}
+
+/* iterations the biased solve performs where its rule performs `count` (-1: this solve is not biased) */
+static int ins_forced(const instr_t *ins, int count)
+{
+    if (!ins->bias_mode || (ins->bias_index >= 0 && ins->bias_index != ins->nsolves)) return -1;
+    if (ins->bias_mode > 0) return count + 1;
+    return count >= 2 ? count - 1 : -1;
+}
 
 /* ------------------------------------------------------------------------------------------ */
 static void pattern_from_dense(pattern_t *p, int n, const double *const *mats, int nmats, int full)
@@ -243,14 +293,15 @@ static void neumann(const oracle_t *o, double h, const double *S, double *B, dou
 }
 
 /* jacobi!: src/linear_solvers.jl:110-153 (S is scaled by -h/2 in place and restored there; here the
- * scaling is folded into the product).  B is left untouched, as in the reference. */
-static void jacobi(const oracle_t *o, double h, const double *S, const double *B, double *Tm, double *X, int max_iter,
-                   double tol)
+ * scaling is folded into the product).  B is left untouched, as in the reference.
+ * force < 0: the reference's loop.  force >= 0 (test-only bias): exactly `force` iterations, no stopping test.  Returns the count. */
+static int jacobi_loop(const oracle_t *o, double h, const double *S, const double *B, double *Tm, double *X, int max_iter,
+                       double tol, int force, int *by_cap)
 {
     int len = o->Ntot * o->N, j, i;
     double coeff = -0.5 * h;
     memcpy(X, B, (size_t)len * sizeof(double));
-    for (j = 1; j <= max_iter; j++) {
+    for (j = 1; j <= (force < 0 ? max_iter : force); j++) {
         double err = 0.0;
         mul(Tm, S, &o->patS, X, o->N, coeff, 0.0); /* T = (coeff*S)*X */
         for (i = 0; i < len; i++) {
@@ -259,7 +310,26 @@ static void jacobi(const oracle_t *o, double h, const double *S, const double *B
             err += d * d;
             X[i] = tnew; /* X .= T */
         }
-        if (sqrt(err) < tol) return;
+        if (force >= 0) continue;
+        if (o->ins) ins_margin(o->ins, sqrt(err), tol);
+        if (sqrt(err) < tol) {
+            *by_cap = 0;
+            return j;
+        }
+    }
+    *by_cap = 1;
+    return j - 1;
+}
+
+static void jacobi(const oracle_t *o, double h, const double *S, const double *B, double *Tm, double *X, int max_iter,
+                   double tol)
+{
+    int by_cap, first = o->ins ? o->ins->nmargins : 0;
+    int count = jacobi_loop(o, h, S, B, Tm, X, max_iter, tol, -1, &by_cap);
+    if (o->ins) {
+        int forced = ins_forced(o->ins, count);
+        if (forced >= 0) jacobi_loop(o, h, S, B, Tm, X, max_iter, tol, forced, &by_cap); /* (B is untouched: a clean restart) */
+        ins_solve(o->ins, count, by_cap, first);
     }
 }
 
@@ -528,6 +598,13 @@ void jqo_set_uncoupled(void *h, const double *rfreq)
     for (q = 0; q < o->Ncoupled; q++) o->Rfreq[q] = rfreq[q];
 }
 
+static void ins_free(instr_t *ins)
+{
+    if (!ins) return;
+    free(ins->count); free(ins->by_cap); free(ins->first); free(ins->sample_of); free(ins->margins);
+    free(ins);
+}
+
 void jqo_destroy(void *h)
 {
     oracle_t *o = (oracle_t *)h;
@@ -542,7 +619,40 @@ void jqo_destroy(void *h)
     free(o->patHsym); free(o->patHanti);
     free(o->Hconst); free(o->Hsym); free(o->Hanti); free(o->Uinit); free(o->Utr); free(o->Uti);
     free(o->wdiag); free(o->Cfreq); free(o->Rfreq); free(o->wreal); free(o->wimag);
+    ins_free(o->ins);
     free(o);
+}
+
+/* TEST-ONLY: (re)start the instrumentation.  record, bias_mode (0, +1, -1), bias_index (-1: every solve): all zero switches it off. */
+void jqo_instrument(void *h, int record, int bias_mode, int bias_index)
+{
+    oracle_t *o = (oracle_t *)h;
+    ins_free(o->ins);
+    o->ins = NULL;
+    if (!record && !bias_mode) return;
+    o->ins = (instr_t *)calloc(1, sizeof(instr_t));
+    o->ins->record = record; o->ins->bias_mode = bias_mode; o->ins->bias_index = bias_index;
+}
+
+/* sizes[0] = solves since jqo_instrument, sizes[1] = margins recorded */
+void jqo_record_sizes(void *h, int *sizes)
+{
+    oracle_t *o = (oracle_t *)h;
+    sizes[0] = o->ins ? o->ins->nsolves : 0;
+    sizes[1] = o->ins && o->ins->record ? o->ins->nmargins : 0;
+}
+
+/* per solve: count, by_cap, first (index of its first margin), sample (of jqo_eval_f_g_grad; 0 outside); then the margins */
+void jqo_record_get(void *h, int *count, int *by_cap, int *first, int *sample, double *margins)
+{
+    oracle_t *o = (oracle_t *)h;
+    instr_t *ins = o->ins;
+    if (!ins || !ins->record) return;
+    memcpy(count, ins->count, (size_t)ins->nsolves * sizeof(int));
+    memcpy(by_cap, ins->by_cap, (size_t)ins->nsolves * sizeof(int));
+    memcpy(first, ins->first, (size_t)ins->nsolves * sizeof(int));
+    memcpy(sample, ins->sample_of, (size_t)ins->nsolves * sizeof(int));
+    memcpy(margins, ins->margins, (size_t)ins->nmargins * sizeof(double));
 }
 
 void jqo_set_max_iter(void *h, int max_iter) { ((oracle_t *)h)->max_iter = max_iter; }
@@ -776,14 +886,15 @@ int jqo_traceobjgrad(void *h, const double *pcof, int ncoeff, int evaladjoint, d
 
 /* jacobi_midpoint: src/linear_solvers.jl:156-215 (sparse) / :218-270 (dense).  On exit x0_u, x0_v hold the
  * solution of (I - h/2 [S -K; K S]) x = rhs.  The caller copies them into u, v (ImplicitMidpoint.jl:142-143). */
-static void jacobi_midpoint(const oracle_t *o, double h, const double *rhs_u, const double *rhs_v, const double *S,
-                            const double *K, double *u_init, double *v_init, double *x0_u, double *x0_v, double *nu_,
-                            double *nv_, int max_iter, double tol)
+static int jacobi_midpoint_loop(const oracle_t *o, double h, const double *rhs_u, const double *rhs_v, const double *S,
+                                const double *K, double *u_init, double *v_init, double *x0_u, double *x0_v, double *nu_,
+                                double *nv_, int max_iter, double tol, int force, int *by_cap)
 {
     int len = o->Ntot * o->N, N = o->N, it, i;
     memcpy(x0_u, u_init, (size_t)len * sizeof(double));
     memcpy(x0_v, v_init, (size_t)len * sizeof(double));
-    for (it = 0; it < max_iter; it++) {
+    *by_cap = 1;
+    for (it = 0; it < (force < 0 ? max_iter : force); it++) {
         double nru = 0.0, nrv = 0.0;
         mul(u_init, S, &o->patS, x0_u, N, 0.5 * h, 0.0);
         axpy(len, 1.0, rhs_u, u_init);
@@ -793,6 +904,7 @@ static void jacobi_midpoint(const oracle_t *o, double h, const double *rhs_u, co
         mul(v_init, S, &o->patS, x0_v, N, 0.5 * h, 1.0);
         memcpy(x0_u, u_init, (size_t)len * sizeof(double));
         memcpy(x0_v, v_init, (size_t)len * sizeof(double));
+        if (force >= 0) continue; /* (test-only bias: a fixed count, no residual) */
         mul(nu_, K, &o->patK, x0_v, N, 0.5 * h, 0.0);
         mul(nu_, S, &o->patS, x0_u, N, -0.5 * h, 1.0);
         axpy(len, 1.0, x0_u, nu_);
@@ -805,8 +917,44 @@ static void jacobi_midpoint(const oracle_t *o, double h, const double *rhs_u, co
             nru += nu_[i] * nu_[i];
             nrv += nv_[i] * nv_[i];
         }
-        if (sqrt(nru) < tol && sqrt(nrv) < tol) break;
+        if (o->ins) {
+            ins_margin(o->ins, sqrt(nru), tol);
+            ins_margin(o->ins, sqrt(nrv), tol);
+        }
+        if (sqrt(nru) < tol && sqrt(nrv) < tol) {
+            *by_cap = 0;
+            it++; /* (iterations performed) */
+            break;
+        }
     }
+    return it;
+}
+
+static void jacobi_midpoint(const oracle_t *o, double h, const double *rhs_u, const double *rhs_v, const double *S,
+                            const double *K, double *u_init, double *v_init, double *x0_u, double *x0_v, double *nu_,
+                            double *nv_, int max_iter, double tol)
+{
+    int by_cap, count, forced, first, len = o->Ntot * o->N;
+    double *keep = NULL;
+    if (!o->ins) {
+        jacobi_midpoint_loop(o, h, rhs_u, rhs_v, S, K, u_init, v_init, x0_u, x0_v, nu_, nv_, max_iter, tol, -1, &by_cap);
+        return;
+    }
+    first = o->ins->nmargins;
+    if (o->ins->bias_mode) { /* the loop uses u_init, v_init as scratch: keep the initial guess for the biased restart */
+        keep = (double *)malloc(2 * (size_t)len * sizeof(double));
+        memcpy(keep, u_init, (size_t)len * sizeof(double));
+        memcpy(keep + len, v_init, (size_t)len * sizeof(double));
+    }
+    count = jacobi_midpoint_loop(o, h, rhs_u, rhs_v, S, K, u_init, v_init, x0_u, x0_v, nu_, nv_, max_iter, tol, -1, &by_cap);
+    forced = ins_forced(o->ins, count);
+    if (forced >= 0) {
+        memcpy(u_init, keep, (size_t)len * sizeof(double));
+        memcpy(v_init, keep + len, (size_t)len * sizeof(double));
+        jacobi_midpoint_loop(o, h, rhs_u, rhs_v, S, K, u_init, v_init, x0_u, x0_v, nu_, nv_, max_iter, tol, forced, &by_cap);
+    }
+    free(keep);
+    ins_solve(o->ins, count, by_cap, first);
 }
 
 typedef struct {
@@ -1035,6 +1183,7 @@ int jqo_eval_f_g_grad(void *h, const double *pcof, int ncoeff, const double *nod
     }
     for (i = 0; i < nquad && rc == 0; i++) {
         double ep = nodes[i];
+        if (o->ins) o->ins->sample = i;
         for (j = 1; j < n; j++) o->Hconst[j + (size_t)j * n] += ep * shift[j];
         rc = jqo_traceobjgrad(h, pcof, ncoeff, compute_adjoint, r, tg, ig, lg, NULL, NULL, NULL);
         if (rc == 0) {
@@ -1048,6 +1197,7 @@ int jqo_eval_f_g_grad(void *h, const double *pcof, int ncoeff, const double *nod
         }
         for (j = 1; j < n; j++) o->Hconst[j + (size_t)j * n] -= ep * shift[j];
     }
+    if (o->ins) o->ins->sample = 0;
     free(tg);
     return rc;
 }

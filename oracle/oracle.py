@@ -31,6 +31,10 @@ def lib():
             [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int]
         L.jqo_destroy.argtypes = [ctypes.c_void_p]
         L.jqo_set_max_iter.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        c_ip = ctypes.POINTER(ctypes.c_int)
+        L.jqo_instrument.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        L.jqo_record_sizes.argtypes = [ctypes.c_void_p, c_ip]
+        L.jqo_record_get.argtypes = [ctypes.c_void_p, c_ip, c_ip, c_ip, c_ip, c_dp]
         L.jqo_set_uncoupled.argtypes = [ctypes.c_void_p, c_dp]
         L.jqo_set_target.argtypes = [ctypes.c_void_p, c_dp, c_dp]
         L.jqo_set_wdiag.argtypes = [ctypes.c_void_p, c_dp]
@@ -102,6 +106,30 @@ class Oracle:
 
     def set_max_iter(self, m):
         lib().jqo_set_max_iter(self.h, int(m))
+
+    def instrument(self, record=False, bias=0, solve=-1):
+        """TEST-ONLY (both off by default; with both off no number changes).  record: keep, per call of jacobi / jacobi_midpoint from now on,
+        the iteration count, the exit and the margins of its stopping comparisons (iteration_record).  bias +1 / -1: solve number `solve`
+        (counted from this call on; -1: every solve) performs one iteration more than its rule says / one fewer where the rule's count
+        is >= 2.  The record stays the rule's."""
+        assert bias in (0, 1, -1)
+        lib().jqo_instrument(self.h, 1 if record else 0, int(bias), int(solve))
+
+    def iteration_record(self):
+        """-> dict of arrays, one entry per solve in call order: count, by_cap (left by the cap, not by the tolerance), sample (of
+        eval_f_g_grad; 0 outside an ensemble), margin (the smallest |norm / tol - 1| of its stopping comparisons, inf where it made none),
+        and margins: the list of every comparison's margin per solve (both norms per iteration for jacobi_midpoint)."""
+        c_ip = ctypes.POINTER(ctypes.c_int)
+        sizes = np.zeros(2, dtype=np.intc)
+        lib().jqo_record_sizes(self.h, sizes.ctypes.data_as(c_ip))
+        ns, nm = int(sizes[0]), int(sizes[1])
+        count, by_cap, first, sample = (np.zeros(ns, dtype=np.intc) for _ in range(4))
+        margins = np.zeros(nm)
+        if ns:
+            lib().jqo_record_get(self.h, *[a.ctypes.data_as(c_ip) for a in (count, by_cap, first, sample)], _p(margins))
+        per = np.split(margins, first[1:]) if ns else []
+        return dict(count=count, by_cap=by_cap.astype(bool), sample=sample, margins=per,
+                    margin=np.array([m.min() if m.size else np.inf for m in per]))
 
     def controls(self, pcof, t):
         pcof = _f(pcof)
