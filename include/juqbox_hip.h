@@ -681,8 +681,8 @@ int jq_traceobj_sweep(jq_handle *h, const double *pcof, int32_t ncoeff, const do
  * Errors: JQ_EINVAL for NULL required pointers, nt != 2 nsteps + 1, a sample that is not finite, nquad < 1.  JQ_EUNSUPPORTED for
  * uncoupled controls (their operators are driven by ft = 2 (p cos(2 pi Rfreq t) - q sin(2 pi Rfreq t)), a function of both slots: a
  * lab-frame sample interface is a later step), and whatever jq_traceobjgrad refuses for the handle's settings.  A refused call writes
- * nothing and leaves the handle as it was.  Multi-device handles run these calls on their first device.  Not served: batches of
- * sample tables, drift or mix members with samples, device pointers, sharding over devices.
+ * nothing and leaves the handle as it was.  Multi-device handles run these calls on their first device.  Not served: device pointers,
+ * sharding over devices (batches of tables and member ensembles: the three calls at the end of this section).
  *
  * jq_eval_f_g_grad_samples_hvp: jq_eval_f_g_grad_samples with its gradients, and Hessian-vector products in sample space -- the semantics
  * of jq_eval_f_g_grad_hvp with "coefficient" read as "sample":
@@ -712,6 +712,40 @@ int jq_eval_f_g_grad_samples(jq_handle *h, const double *pq, int32_t nt, const d
 int jq_eval_f_g_grad_samples_hvp(jq_handle *h, const double *pq, int32_t nt, const double *dirs, int32_t ndir, const double *nodes,
                                  const double *weights, int32_t nquad, const double *shift, double *out2, double *infid_grad,
                                  double *leak_grad, double *hv_infid, double *hv_leak);
+/*
+ * Sample tables in batches and over member ensembles, in one call -- jq_traceobjgrad_batch, jq_traceobjgrad_members and
+ * jq_eval_f_g_grad_members with "control vector" read as "sample table".  Where the spline calls share launches (row-lane and
+ * cooperative-quad kernels, Stormer-Verlet with the Neumann solver, the column counts of jq_traceobjgrad_batch; option pcof_batch_max
+ * applies, 0 forces the other route) the groups of these calls do: every workgroup reads the operator stream of its own table, or of the
+ * shared table under its member's drift and mix.  On every other route the groups run one after the other inside the call (member
+ * drifts become the handle's drift in turn; the handle's own is restored at the end).
+ * jq_traceobjgrad_samples_batch: pqs holds ntab tables [2 Nc x nt] one after the other; column i of every output (out4: [4 x ntab], the
+ * gradients: [2 Nc x nt x ntab]) is what jq_traceobjgrad_samples(pqs[i]) returns -- the record bit for bit at the same chunk length.
+ * jq_traceobjgrad_samples_members: ONE table; member g has the drift Hconsts[:, :, g] (NULL: the handle's) and the real mix
+ * ctrl_mix[:, :, g] (Nc x Nc column-major; NULL: identity): what reaches operator l of member g is sum_k C_g[l, k] (p_k, q_k)(t_J), as in
+ * jq_traceobjgrad_members.  Member g's gradients ([2 Nc x nt x nmember]) are those with respect to the SHARED table -- its mix is folded in
+ * by C_g'.  C = I writes the table's bits, a zero column k of C gives exactly zero rows 2 k, 2 k + 1 of that member's gradient.
+ * jq_eval_f_g_grad_samples_members: out2 = sum_g w_g (infidelity_g, leak_g), infid_grad / leak_grad ([2 Nc x nt]) the weighted sample
+ * gradients, summed ON THE DEVICE in member order from the members' finished tables (they are not fetched), so their bits do not depend
+ * on how many members share a launch; member_out (may be NULL): the 4 x nmember records, as jq_eval_f_g_grad_members.
+ * jq_plan_info reports "sampled_batch": {kind ("tables" | "members"), mode ("grouped" | "sequential"), why, family, per_launch, drifts,
+ * mixes, time_points, chunk_steps} after such a call (additive key; "pcof_batch", "drift_batch", "member_batch" keep describing the
+ * spline calls, "sampled_controls" is refreshed as by any sampled evaluation).
+ * Errors: the union of the sampled calls' and the member calls' -- JQ_EINVAL for NULL required pointers, nt != 2 nsteps + 1, a sample
+ * of ANY table that is not finite, ntab < 1, nmember < 1, Hconsts and ctrl_mix both NULL, a mix entry that is not finite; JQ_EUNSUPPORTED
+ * for uncoupled controls.  A refused call writes nothing and leaves the handle as it was.  Member drifts are tested against the plan
+ * like jq_traceobjgrad_members' (one re-plan for the union of all patterns, with that call's caveats).  Multi-device handles run these
+ * calls on their first device.  Not served: Hessian-vector products over members or batches in sample space, members x eps nodes,
+ * uncoupled controls, device pointers, sharding over devices.
+ */
+int jq_traceobjgrad_samples_batch(jq_handle *h, const double *pqs, int32_t nt, int32_t ntab, int32_t evaladjoint,
+                                  double *out4, double *totalgrad, double *infidelgrad, double *leakgrad);
+int jq_traceobjgrad_samples_members(jq_handle *h, const double *pq, int32_t nt, const double *Hconsts, const double *ctrl_mix,
+                                    int32_t nmember, int32_t evaladjoint,
+                                    double *out4, double *totalgrad, double *infidelgrad, double *leakgrad);
+int jq_eval_f_g_grad_samples_members(jq_handle *h, const double *pq, int32_t nt, const double *Hconsts, const double *ctrl_mix,
+                                     const double *weights, int32_t nmember, int32_t compute_adjoint,
+                                     double *out2, double *infid_grad, double *leak_grad, double *member_out);
 
 /* ---- introspection ---------------------------------------------------------------------------*/
 /*

@@ -490,6 +490,62 @@ function eval_f_g_grad_samples_hvp(pq::Matrix{Float64}, dirs::Union{Matrix{Float
                       wa.handle, pq, size(pq, 2), D, nd, nodes, weights, nq, shift === nothing ? C_NULL : pointer(shift), out2, ig, lg, hvi, hvl))
     return (infidelity = out2[1], leak = out2[2], infid_grad = ig, leak_grad = lg, hv_infid = hvi, hv_leak = hvl)
 end
+# Many sample tables in one call (jq_traceobjgrad_samples_batch): pqs is [2 Nc, nt, ntab]; slice i of every result is what
+# traceobjgrad_samples(pqs[:, :, i]) returns.  Where the spline batch shares launches the tables do (jq_plan_info "sampled_batch").
+function traceobjgrad_samples_batch(pqs::Array{Float64, 3}, params::objparams, wa::AbstractWorkingArraysHIP, evaladjoint::Bool = true)
+    (size(pqs, 1) == 2 * params.Ncoupled && size(pqs, 2) == 2 * params.nsteps + 1 && size(pqs, 3) >= 1) ||
+        throw(DimensionMismatch("traceobjgrad_samples_batch: pqs must be 2 Ncoupled x (2 nsteps + 1) x ntab, ntab >= 1"))
+    ntab = size(pqs, 3)
+    sync!(wa, params)
+    out4 = zeros(4, ntab)
+    tg = zeros(size(pqs)); ig = zeros(size(pqs)); lg = zeros(size(pqs))
+    jqcheck(wa, ccall((:jq_traceobjgrad_samples_batch, libjq), Cint,
+                      (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                      wa.handle, pqs, size(pqs, 2), ntab, evaladjoint ? 1 : 0, out4, tg, ig, lg))
+    evaladjoint || return out4[1, :], out4[2, :], out4[3, :]
+    return out4[1, :], tg, out4[2, :], out4[3, :], out4[4, :], ig, (params.objFuncType == 1 ? zeros(0, 0, 0) : lg)
+end
+# the shapes of a member ensemble over ONE sample table: (nmember); `nothing` for Hconsts / ctrl_mix means the handle's drift / the identity
+function samples_members_count(who::String, pq::Matrix{Float64}, params::objparams, Hconsts, ctrl_mix)
+    size(pq) == (2 * params.Ncoupled, 2 * params.nsteps + 1) || throw(DimensionMismatch("$who: pq must be 2 Ncoupled x (2 nsteps + 1)"))
+    (Hconsts === nothing && ctrl_mix === nothing) && throw(ArgumentError("$who: give Hconsts, ctrl_mix or both"))
+    Ntot = params.N + params.Nguard
+    nm = ctrl_mix === nothing ? size(Hconsts, 3) : size(ctrl_mix, 3)
+    nm >= 1 || throw(ArgumentError("$who: need at least one member"))
+    Hconsts === nothing || (size(Hconsts) == (Ntot, Ntot, nm)) || throw(DimensionMismatch("$who: Hconsts must be Ntot x Ntot x nmember"))
+    ctrl_mix === nothing || (size(ctrl_mix) == (params.Ncoupled, params.Ncoupled, nm)) || throw(DimensionMismatch("$who: ctrl_mix must be Nc x Nc x nmember"))
+    return nm
+end
+# ONE sample table under nmember members (jq_traceobjgrad_samples_members): member i has the drift Hconsts[:, :, i] and the real control
+# mix ctrl_mix[:, :, i] (operator l is driven by sum_k C[l, k] (p_k, q_k)); its gradients [2 Nc, nt, i] are those with respect to the
+# shared table.  The handle's drift and plan are left alone.
+function traceobjgrad_samples_members(pq::Matrix{Float64}, params::objparams, wa::AbstractWorkingArraysHIP,
+                                      Hconsts::Union{Nothing,Array{Float64,3}}, ctrl_mix::Union{Nothing,Array{Float64,3}}, evaladjoint::Bool = true)
+    nm = samples_members_count("traceobjgrad_samples_members", pq, params, Hconsts, ctrl_mix)
+    sync!(wa, params)
+    out4 = zeros(4, nm)
+    tg = zeros(size(pq)..., nm); ig = zeros(size(pq)..., nm); lg = zeros(size(pq)..., nm)
+    jqcheck(wa, ccall((:jq_traceobjgrad_samples_members, libjq), Cint,
+                      (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                      wa.handle, pq, size(pq, 2), Hconsts === nothing ? C_NULL : pointer(Hconsts), ctrl_mix === nothing ? C_NULL : pointer(ctrl_mix),
+                      nm, evaladjoint ? 1 : 0, out4, tg, ig, lg))
+    evaladjoint || return out4[1, :], out4[2, :], out4[3, :]
+    return out4[1, :], tg, out4[2, :], out4[3, :], out4[4, :], ig, (params.objFuncType == 1 ? zeros(0, 0, 0) : lg)
+end
+# the weighted ensemble of those members (jq_eval_f_g_grad_samples_members): sum_i w_i (infidelity_i, leak_i) and the two weighted sample
+# gradients [2 Nc, nt], summed on the device; members: the 4 x nmember records
+function eval_f_g_grad_samples_members(pq::Matrix{Float64}, params::objparams, wa::AbstractWorkingArraysHIP, weights::Vector{Float64},
+                                       Hconsts::Union{Nothing,Array{Float64,3}}, ctrl_mix::Union{Nothing,Array{Float64,3}}, compute_adjoint::Bool = true)
+    nm = samples_members_count("eval_f_g_grad_samples_members", pq, params, Hconsts, ctrl_mix)
+    length(weights) == nm || throw(ArgumentError("eval_f_g_grad_samples_members: need one weight per member"))
+    sync!(wa, params)
+    out2 = zeros(2); ig = zeros(size(pq)); lg = zeros(size(pq)); rec = zeros(4, nm)
+    jqcheck(wa, ccall((:jq_eval_f_g_grad_samples_members, libjq), Cint,
+                      (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                      wa.handle, pq, size(pq, 2), Hconsts === nothing ? C_NULL : pointer(Hconsts), ctrl_mix === nothing ? C_NULL : pointer(ctrl_mix),
+                      weights, nm, compute_adjoint ? 1 : 0, out2, ig, lg, rec))
+    return (infidelity = out2[1], leak = out2[2], infid_grad = ig, leak_grad = lg, members = rec)
+end
 
 # Many control vectors of ONE problem in one call (jq_traceobjgrad_batch): column i of every result is what
 # traceobjgrad(pcofs[:, i], params, wa, false, evaladjoint) returns.  On the latency kernels (row-lane, cooperative quad; Stormer-Verlet)

@@ -101,6 +101,9 @@ SYMBOLS = {
     "jq_traceobjgrad_samples": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_i32, c_i32, c_dp, c_dp, c_dp, c_dp]),
     "jq_eval_f_g_grad_samples": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_i32, c_dp, c_dp, c_i32, c_dp, c_i32, c_dp, c_dp, c_dp]),
     "jq_eval_f_g_grad_samples_hvp": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_i32, c_dp, c_i32, c_dp, c_dp, c_i32, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "jq_traceobjgrad_samples_batch": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_i32, c_i32, c_i32, c_dp, c_dp, c_dp, c_dp]),
+    "jq_traceobjgrad_samples_members": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_i32, c_dp, c_dp, c_i32, c_i32, c_dp, c_dp, c_dp, c_dp]),
+    "jq_eval_f_g_grad_samples_members": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_i32, c_dp, c_dp, c_dp, c_i32, c_i32, c_dp, c_dp, c_dp, c_dp]),
     "jq_last_timing": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(jq_timing)]),
     "jq_version": (ctypes.c_char_p, []),
     "jq_abi_version": (ctypes.c_int, []),

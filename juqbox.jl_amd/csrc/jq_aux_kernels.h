@@ -626,6 +626,56 @@ __global__ void k_gradsamples_grouped(const double* __restrict__ R, int nsteps_c
     G[(size_t)J * 2 * Nc + 2 * (q0 + c) + isq] += acc;
 }
 
+// Sample tables in a grouped batch of run_eval (jq_traceobjgrad_samples_batch / _members, jq_host_samples_batch.h): siblings again, so
+// that every launch above stays the code it was.
+
+// grid.y = groups: group g reads its table tstride doubles behind the one before (0: every group reads the ONE shared table of a member
+// ensemble) and writes the pq block g ([g][ntp][2 Nc], what k_stream reads for a grouped chunk); index map and bounds of k_ctrl_samples.
+// mix (nullptr: none): [groups][Nc x Nc] column-major mixing matrices, applied with the loop of k_ctrl -- zero entries of C are skipped
+// and the first term is the product alone, so C = I writes the table's bits.  The table IS the unmixed value: no `raw` area.
+__global__ void k_ctrl_samples_members(const double* __restrict__ S, long long tstride, int nt, int J0, int dir, int ntp, int Nc,
+                                       const double* __restrict__ mix, double* __restrict__ pq)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= ntp) return;
+    const int J = J0 + dir * j;
+    if (J < 0 || J >= nt) return;
+    const double* val = S + (size_t)blockIdx.y * (size_t)tstride + (size_t)J * 2 * Nc;
+    pq += ((size_t)blockIdx.y * ntp + j) * 2 * Nc;
+    if (!mix) {
+        for (int f = 0; f < 2 * Nc; ++f) pq[f] = val[f];
+        return;
+    }
+    const double* C = mix + (size_t)blockIdx.y * Nc * Nc;
+    for (int l = 0; l < Nc; ++l) {
+        double pm = 0.0, qm = 0.0;
+        bool first = true;
+        for (int k = 0; k < Nc; ++k) {
+            const double c = C[l + Nc * k];
+            if (c == 0.0) continue;
+            const double pk = c * val[2 * k], qk = c * val[2 * k + 1];
+            pm = first ? pk : pm + pk;
+            qm = first ? qk : qm + qk;
+            first = false;
+        }
+        pq[2 * l] = pm;
+        pq[2 * l + 1] = qm;
+    }
+}
+
+// The ensemble gradient of jq_eval_f_g_grad_samples_members on the device: A <- ((A + w_0 T_0) + w_1 T_1) + ... over the `groups`
+// finished sample gradients T_g of a launch ([g] tstride doubles apart, k_gradsamples_grouped's tables) in member order, one thread per
+// entry and ONE store.  The sum starts from A and runs in member order over whole gradients, so the bits of the ensemble gradient do not
+// depend on how many members share a launch, whatever the chunking; the members' tables stay on the device.
+__global__ void k_gradsamples_wsum(const double* __restrict__ T, long long tstride, int groups, const double* __restrict__ w, double* __restrict__ A, long long len)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= len) return;
+    double acc = A[e];
+    for (int g = 0; g < groups; ++g) acc = acc + w[g] * T[(size_t)g * (size_t)tstride + e];
+    A[e] = acc;
+}
+
 // Packed result of an ensemble evaluation, left on the device for the collective that sums it over GPUs (one all-reduce):
 //   out = [ sum_i w_i primaryobjf_i, sum_i w_i secondaryobjf_i, infidelity gradient [ncoeff], leak gradient [ncoeff] ]
 // (src/ipopt_interface.jl:48-59; grad = the weighted gradient sums of the forced [0] and unforced [1] backward sweeps:

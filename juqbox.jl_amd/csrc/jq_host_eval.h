@@ -25,6 +25,12 @@ struct EvalRequest {
     // (p_1, q_1, p_2, q_2, ...) at every time point of jq_sample_times.  It takes the place of the coefficients: pcof is not read, ncoeff
     // = 2 Nc nt is the length of the gradients, which are those with respect to the samples.  Only k_ctrl_samples and k_gradsamples see it.
     const double* samples = nullptr;
+    // ... in a grouped batch (jq_host_samples_batch.h): `groups` tables one after the other (jq_traceobjgrad_samples_batch), or -- with
+    // drifts / mix -- the ONE table the members share, uploaded once.  Only k_ctrl_samples_members and k_gradsamples_grouped see those.
+    // ens_w (jq_eval_f_g_grad_samples_members; NULL: none): HOST weights [max(groups, 1)] of the launch's members.  The gradients of the
+    // EvalOut are then ONE pair of tables, ens_acc0 / ens_acc1 (HOST [ncoeff]; NULL: zeros) plus the members' weighted gradients in member
+    // order (k_gradsamples_wsum) -- the members' own tables are not fetched.
+    const double *ens_w = nullptr, *ens_acc0 = nullptr, *ens_acc1 = nullptr;
     bool split_part = false;        // one part of a split batch: not split again
 };
 struct EvalOut {
@@ -172,9 +178,11 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     const int nt = 2 * h->nsteps + 1;
     if (sampled) {
         if (int rc = samples_refuse(h, "run_eval")) return rc;
-        if (rq.groups > 0 || rq.drifts || rq.mix) return fail(h, JQ_EUNSUPPORTED, "sampled controls together with a batch of control vectors, member drifts or control mixes are not served");
+        if ((rq.groups > 0 || rq.drifts || rq.mix) && (rq.eps || rq.wgt || rq.nodes != 1 || rq.hist_r || rq.d_packed))
+            return fail(h, JQ_EUNSUPPORTED, "sampled controls in a batch of tables or a member ensemble together with eps nodes, a state history or a packed result are not served");
         if (ncoeff != 2 * h->Nc * nt) return fail(h, JQ_EHIP, "internal error: sampled controls with a gradient length other than 2 Nc nt");
     }
+    if (rq.ens_w && !sampled) return fail(h, JQ_EHIP, "internal error: ensemble weights without sampled controls");
     const bool adjoint = rq.adjoint;
     double *const hist_r = rq.hist_r, *const hist_i = rq.hist_i, *const d_packed = rq.d_packed;
     HIPCHK(h, hipSetDevice(h->device));
@@ -244,6 +252,11 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     if (G > 0 && (nsamples != G * spg || Q < 1 || Q > spg || hist_r || d_packed)) return fail(h, JQ_EHIP, "internal error: grouped batch with a state history or a packed result");
     if (rq.drifts && G == 0) return fail(h, JQ_EHIP, "internal error: member drifts outside a grouped batch");
     const int nvec = G > 0 ? G : 1;      // (coefficient blocks, tile streams, gradients of the launch)
+    // sample tables per group, or one table under a mix: the grouped sample kernels take the place of k_ctrl_samples / k_gradsamples
+    const bool sampled_grp = sampled && (G > 0 || rq.mix);
+    const bool shared_table = sampled && (rq.drifts || rq.mix);      // (an ensemble's members share ONE table: no copies)
+    const int ntab = (sampled && !shared_table) ? nvec : 1;
+    const bool ens = rq.ens_w != nullptr && adjoint;
     // Structure embedding (try_embed): batches that would run on the dense / band MFMA families go to the embedded twin,
     // whose operators have the JQ_BW_T4 structure (quad-layout / JQ_BW_T4 slab kernels).  State histories stay here (their
     // rows are the user's), the implicit-midpoint path too.
@@ -294,7 +307,7 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     const bool two_pass = adjoint && h->objFuncType != 1;
 
     // ---- capacity ------------------------------------------------------------------------------
-    if ((rc = dev_grow(h, &h->d_pcof, &h->cap_pcof, (size_t)nvec * ncoeff))) return rc;
+    if ((rc = dev_grow(h, &h->d_pcof, &h->cap_pcof, (size_t)(sampled ? ntab : nvec) * ncoeff))) return rc;
     const size_t gstride = G > 0 ? (size_t)(2 * p.cs + 1) * 2 * (size_t)p.stride : 0;      // doubles between the tile streams of two vectors
     if (G > 0) {      // (sized by jq_create for ONE vector and the handle's chunk length)
         if ((rc = dev_grow(h, &h->d_stream, &h->cap_stream, (size_t)G * gstride))) return rc;
@@ -319,7 +332,8 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
         h->cap_slabs = p.park_slabs;
     }
     if (adjoint && (rc = dev_grow(h, &h->d_traces, &h->cap_traces, (size_t)p.trace_rows * p.cs * ntr))) return rc;
-    if ((rc = dev_grow(h, &h->d_grad, &h->cap_grad, (size_t)nvec * 2 * ncoeff))) return rc;      // [vector][forced | unforced][ncoeff]
+    if ((rc = dev_grow(h, &h->d_grad, &h->cap_grad, (size_t)(nvec + (ens ? 1 : 0)) * 2 * ncoeff))) return rc;      // [vector][forced | unforced][ncoeff] (+ the ensemble's pair)
+    if (ens && (rc = dev_grow(h, &h->d_wq, &h->cap_wq, (size_t)nvec))) return rc;
     if ((rc = dev_grow(h, &h->d_res, &h->cap_res, (size_t)nsamples * 4))) return rc;
     const size_t cq3_quad = 64 + (size_t)8 * 8 * h->NT * 64 + 64;      // doubles per quad: JQ_CQ3_HEAD + JQ_CQ3_SLOTS * JQ_CQ3_ARRAYS * NT * 64 + JQ_CQ3_TAIL
     if (cq3) {
@@ -333,7 +347,7 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     std::vector<double> gpcof, dimg;
     const bool one_vector = G > 0 && (rq.drifts || rq.mix);      // (an ensemble's members share ONE control vector)
     // one control vector for every group: its block replicated (k_ctrl, k_gradacc stay the launches of a control-vector batch)
-    if (one_vector)
+    if (one_vector && !sampled)
         for (int g = 0; g < G; ++g) gpcof.insert(gpcof.end(), pcof, pcof + ncoeff);
     if (rq.drifts) {
         // the members' drift images in the planned family's layout -- the builders and the bits of upload_operators' image 0
@@ -352,7 +366,10 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     }
     const double* const h0img = rq.drifts ? h->d_drift : p.himg;      // image 0 of group 0 and the stride to the next group's
     const long long h0_gstride = rq.drifts ? p.stride : 0;
-    HIPCHK(h, hipMemcpyAsync(h->d_pcof, one_vector ? gpcof.data() : pcof, (size_t)nvec * ncoeff * sizeof(double), hipMemcpyHostToDevice, s));
+    if (sampled)
+        HIPCHK(h, hipMemcpyAsync(h->d_pcof, pcof, (size_t)ntab * ncoeff * sizeof(double), hipMemcpyHostToDevice, s));
+    else
+        HIPCHK(h, hipMemcpyAsync(h->d_pcof, one_vector ? gpcof.data() : pcof, (size_t)nvec * ncoeff * sizeof(double), hipMemcpyHostToDevice, s));
     if (rq.mix) HIPCHK(h, hipMemcpyAsync(h->d_mix, rq.mix, (size_t)nvec * ncnc * sizeof(double), hipMemcpyHostToDevice, s));
     const double* const d_mix = rq.mix ? h->d_mix : nullptr;
     double* const d_pqraw = rq.mix ? h->d_mix + (size_t)nvec * ncnc : nullptr;
@@ -385,7 +402,14 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
         tabs[p.ws_off + i] = shift ? shift[i] : (i >= 1 ? 0.01 * pow(10.0, (double)(i - 1)) : 0.0);
     }
     HIPCHK(h, hipMemcpyAsync(h->d_tabs, tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemsetAsync(h->d_grad, 0, (size_t)nvec * 2 * ncoeff * sizeof(double), s));
+    HIPCHK(h, hipMemsetAsync(h->d_grad, 0, (size_t)(nvec + (ens ? 1 : 0)) * 2 * ncoeff * sizeof(double), s));
+    double* const d_ens = h->d_grad + (size_t)nvec * 2 * ncoeff;      // (the ensemble's pair of tables, behind the members')
+    if (ens) {
+        if (rq.ens_acc0) HIPCHK(h, hipMemcpyAsync(d_ens, rq.ens_acc0, (size_t)ncoeff * sizeof(double), hipMemcpyHostToDevice, s));
+        if (rq.ens_acc1 && two_pass) HIPCHK(h, hipMemcpyAsync(d_ens + ncoeff, rq.ens_acc1, (size_t)ncoeff * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(h->d_wq, rq.ens_w, (size_t)nvec * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    const long long tstride = shared_table ? 0 : ncoeff;      // doubles between the tables of two groups
 
     SplineArgs sp;
     sp.pcof = h->d_pcof; sp.cfreq = h->d_cfreq; sp.D1 = D1; sp.Nfreq = h->Nfreq; sp.Ncoupled = h->Nc; sp.nCoeff = ncoeff;
@@ -438,7 +462,9 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     for (int n0 = 0; n0 < h->nsteps; n0 += p.cs) {
         const int nc = std::min(p.cs, h->nsteps - n0);
         const int ntp = 2 * nc + 1;
-        if (sampled)
+        if (sampled_grp)
+            hipLaunchKernelGGL(k_ctrl_samples_members, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, h->d_pcof, tstride, nt, 2 * n0, 1, ntp, h->Nc, d_mix, h->d_pq);
+        else if (sampled)
             hipLaunchKernelGGL(k_ctrl_samples, dim3((ntp + 127) / 128), dim3(128), 0, s, h->d_pcof, nt, 2 * n0, 1, ntp, h->Nc, h->d_pq);
         else
             hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, sp, h->d_tf, n0, ntp, dt, h->d_pq, d_mix, d_pqraw);
@@ -508,7 +534,10 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
             for (int n0 = 0; n0 < h->nsteps; n0 += p.cs) {
                 const int nc = std::min(p.cs, h->nsteps - n0);
                 const int ntp = 2 * nc + 1;
-                if (sampled)
+                if (sampled_grp)
+                    hipLaunchKernelGGL(k_ctrl_samples_members, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, h->d_pcof, tstride, nt, 2 * (h->nsteps - n0), -1, ntp,
+                                       h->Nc, d_mix, h->d_pq);
+                else if (sampled)
                     hipLaunchKernelGGL(k_ctrl_samples, dim3((ntp + 127) / 128), dim3(128), 0, s, h->d_pcof, nt, 2 * (h->nsteps - n0), -1, ntp, h->Nc, h->d_pq);
                 else
                     hipLaunchKernelGGL(k_ctrl, dim3((ntp + 127) / 128, nvec), dim3(128), 0, s, sp, h->d_tb, n0, ntp, -dt, h->d_pq, d_mix, d_pqraw);
@@ -560,7 +589,11 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
                 const int ntr_R = d_mix ? h->Nc * JQ_NTR : ntr_g;
                 hipLaunchKernelGGL(k_trace_reduce, dim3((unsigned)(((long long)nc * ntr_R + 255) / 256), nvec), dim3(256), 0, s,
                                    h->d_traces, G > 0 ? p.upg : p.trace_rows, nc, ntr_g, h->d_R, d_mix, h->Nc, q0);
-                if (sampled)      // the same records without the basis: one thread per (time point of the chunk, control of the group, p | q)
+                if (sampled_grp) {      // per group its record into its own table; with a mix the records are the rows of ALL controls
+                    const int gq0 = d_mix ? 0 : q0, gng = d_mix ? h->Nc : ng;
+                    hipLaunchKernelGGL(k_gradsamples_grouped, dim3((unsigned)(((long long)ntp * gng * 2 + 255) / 256), nvec), dim3(256), 0, s, h->d_R, nc, -dt,
+                                       h->d_grad + (size_t)pass * ncoeff, (long long)2 * ncoeff, nt, 2 * (h->nsteps - n0), h->Nc, gq0, gng);
+                } else if (sampled)      // the same records without the basis: one thread per (time point of the chunk, control of the group, p | q)
                     hipLaunchKernelGGL(k_gradsamples, dim3((unsigned)(((long long)ntp * ng * 2 + 255) / 256)), dim3(256), 0, s, h->d_R, nc, -dt,
                                        h->d_grad + (size_t)pass * ncoeff, nt, 2 * (h->nsteps - n0), h->Nc, q0, ng);
                 else      // gradbcarrier2! as a scatter: one workgroup per coefficient of the group's controls
@@ -573,6 +606,10 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
         }
     }
     HIPCHK(h, hipGetLastError());
+    if (ens && !cq3_fault)      // the members' finished tables, weighted, onto the ensemble's pair in member order
+        for (int pass = 0; pass < (two_pass ? 2 : 1); ++pass)
+            hipLaunchKernelGGL(k_gradsamples_wsum, dim3((unsigned)((ncoeff + 255) / 256)), dim3(256), 0, s, h->d_grad + (size_t)pass * ncoeff, (long long)2 * ncoeff, nvec,
+                               h->d_wq, d_ens + (size_t)pass * ncoeff, (long long)ncoeff);
     if (d_packed) {
         if (wgt) {
             if ((rc = dev_grow(h, &h->d_wq, &h->cap_wq, (size_t)nsamples))) return rc;
@@ -587,7 +624,14 @@ static int run_eval_impl(jq_handle* h, const EvalRequest& rq, EvalOut* out)
     // ---- outputs -------------------------------------------------------------------------------
     out->res.resize((size_t)nsamples * 4);
     HIPCHK(h, hipMemcpyAsync(out->res.data(), h->d_res, out->res.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (adjoint) {      // (grouped batch: [vector][ncoeff] each)
+    if (ens) {      // (the ensemble's pair alone)
+        out->grad0.resize((size_t)ncoeff);
+        HIPCHK(h, hipMemcpyAsync(out->grad0.data(), d_ens, (size_t)ncoeff * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (two_pass) {
+            out->grad1.resize((size_t)ncoeff);
+            HIPCHK(h, hipMemcpyAsync(out->grad1.data(), d_ens + ncoeff, (size_t)ncoeff * sizeof(double), hipMemcpyDeviceToHost, s));
+        }
+    } else if (adjoint) {      // (grouped batch: [vector][ncoeff] each)
         out->grad0.resize((size_t)nvec * ncoeff);
         if (two_pass) out->grad1.resize((size_t)nvec * ncoeff);
         for (int g = 0; g < nvec; ++g) {

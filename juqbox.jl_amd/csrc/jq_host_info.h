@@ -222,6 +222,14 @@ extern "C" int jq_plan_info(const jq_handle* hh, char* buf, int32_t buflen)
         kv("sampled_hvp", std::string("{\"route\": \"") + (m.route == 1 ? "lane" : m.route == 3 ? "rowlane" : m.route == 4 ? "quad" : "sequential") + "\", \"directions_per_launch\": " + num(m.per_launch) +
                             ", \"chunk_steps\": " + num(m.chunk) + ", \"rounds\": " + num(m.rounds) + ", \"time_points\": " + num(m.nt) + ", \"nodes\": " + num(m.nodes) + "}");
     }
+    // jq_traceobjgrad_samples_batch / jq_traceobjgrad_samples_members / jq_eval_f_g_grad_samples_members (after a call): what the groups
+    // were, the route ("grouped": the groups share launches; "sequential": one after the other inside the call) and why, the kernel family
+    // that ran, groups per launch, what differed between the members, time points of the tables, steps per chunk
+    if (!h->sampled_batch.kind.empty()) {
+        const jq_handle::SampledBatch& m = h->sampled_batch;
+        kv("sampled_batch", std::string("{\"kind\": \"") + m.kind + "\", \"mode\": \"" + m.mode + "\", \"why\": \"" + m.why + "\", \"family\": " + num(m.family) + ", \"per_launch\": " + num(m.per_launch) +
+                              ", \"drifts\": " + (m.drifts ? "true" : "false") + ", \"mixes\": " + (m.mix ? "true" : "false") + ", \"time_points\": " + num(m.nt) + ", \"chunk_steps\": " + num(m.chunk) + "}");
+    }
     o += "}";
     if (buflen > 0) {
         const size_t n = std::min(o.size(), (size_t)buflen - 1);

@@ -211,6 +211,14 @@ struct jq_handle {
     struct SampledHvp {
         int route = 0, per_launch = 0, chunk = 0, rounds = 0, nt = 0, nodes = 0;
     } sampled_hvp;
+    // ... and the last jq_traceobjgrad_samples_batch / jq_traceobjgrad_samples_members / jq_eval_f_g_grad_samples_members: what its groups were
+    // ("tables" | "members"), the route with its reason, the kernel family that ran, groups per launch, what differed between the members,
+    // time points of the tables, chunk length (jq_plan_info "sampled_batch"; kind empty: no call yet)
+    struct SampledBatch {
+        std::string kind, mode, why;
+        int family = -1, per_launch = 0, nt = 0, chunk = 0;
+        bool drifts = false, mix = false;
+    } sampled_batch;
     // Structure embedding (try_embed): a second handle of the SAME problem with its two fastest Kronecker factors zero-padded
     // to 4 levels each (row i1 + d1 i2 + d1 d2 i3 -> i1 + 4 i2 + 16 i3), under which the operators have the JQ_BW_T4 structure;
     // batches that would otherwise run on the dense / band MFMA kernels go there (quad-layout / JQ_BW_T4 slab kernels).
@@ -730,6 +738,7 @@ extern "C" int jq_eval_f_g_grad_batch(jq_handle* h, const double* pcofs, int32_t
 #include "jq_host_hvp.h"      // jq_traceobjgrad_hvp: the derivative of the gradient along directions of coefficient space
 #include "jq_host_ens_hvp.h"      // jq_eval_f_g_grad_hvp: the same over the nodes of a risk-neutral ensemble (lane / row-lane kernels: one launch per chunk)
 #include "jq_host_samples.h"      // controls given as samples on the time grid: the objective of a table pq, its gradient per entry, and (through the drivers above) Hessian-vector products along direction tables
+#include "jq_host_samples_batch.h"      // ... in batches of tables and over member ensembles (drifts, control mixes) in one call
 #include "jq_host_multi.h"      // multi-device handles: one process, N GPUs, one RCCL all-reduce
 #include "jq_host_info.h"      // options of a live handle, plan and timing introspection
 #ifdef JQ_DUMP_SELECTION

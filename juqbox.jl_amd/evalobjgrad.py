@@ -32,6 +32,11 @@
                                         traceobjgrad for controls given as values on the time grid (jq_traceobjgrad_samples): the
                                         objective of a 2 Ncoupled x (2 nsteps + 1) table and its gradient per entry -- any
                                         parameterisation is then a chain rule on the host.
+  traceobjgrad_samples_batch(pqs, params, wa, evaladjoint=True)
+  traceobjgrad_samples_members(pq, params, wa, Hconsts=None, ctrl_mix=None, evaladjoint=True)
+                                        traceobjgrad_samples for many tables, or for ONE table under members that differ in their drift
+                                        and in a real mix of the controls, in one library call (jq_traceobjgrad_samples_batch,
+                                        jq_traceobjgrad_samples_members): the groups share launches where the spline batch does.
   traceobjgrad_samples_hvp(pq, dirs, params, wa)
                                         its gradient and the derivative of that gradient along direction tables
                                         (jq_eval_f_g_grad_samples_hvp, one node): Hessian-vector products in sample space.
@@ -782,6 +787,87 @@ def traceobjgrad_samples(pq, params: objparams, wa: Working_Arrays_HIP, evaladjo
     _lib.check(L.jq_traceobjgrad_samples(h, _ptr(tab), shape[1], 1, _ptr(out4), _ptr(tg), _ptr(ig), _ptr(lg)), h)
     leak = np.zeros((0, 0)) if params.objFuncType == 1 else lg.reshape(shape, order="F")
     return out4[0], tg.reshape(shape, order="F"), out4[1], out4[2], out4[3], ig.reshape(shape, order="F"), leak
+
+
+def _sample_tables(pqs, params, who):
+    """pqs -> ([ntab, 2 Nc * nt] array, table i column-major in row i, and the shape of one table).  An [ntab, 2 Ncoupled, 2 nsteps + 1]
+    array or a sequence of tables; ValueError for anything else, through _sample_table per table"""
+    try:
+        tabs = list(pqs)
+    except TypeError as e:
+        raise ValueError("%s: pqs must be an [ntab, 2 Ncoupled, 2 nsteps + 1] array or a sequence of tables (%s)" % (who, e))
+    if len(tabs) == 0:
+        raise ValueError("%s: need at least one table" % who)
+    flat, shape = [], None
+    for t in tabs:
+        f, shape = _sample_table(t, params, who)
+        flat.append(f)
+    return np.ascontiguousarray(np.stack(flat)), shape
+
+
+def _sample_columns(params, out4, tg, ig, lg, shape, evaladjoint):
+    """the return tuple of traceobjgrad_batch for n groups over sample tables: gradients [n, 2 Nc, nt]"""
+    if not evaladjoint:
+        return out4[:, 0].copy(), out4[:, 1].copy(), out4[:, 2].copy()
+    n = out4.shape[0]
+
+    def tables(g):
+        return np.ascontiguousarray(g.reshape((n, shape[1], shape[0])).transpose(0, 2, 1))
+
+    leak = np.zeros((n, 0, 0)) if params.objFuncType == 1 else tables(lg)
+    return out4[:, 0].copy(), tables(tg), out4[:, 1].copy(), out4[:, 2].copy(), out4[:, 3].copy(), tables(ig), leak
+
+
+def traceobjgrad_samples_batch(pqs, params: objparams, wa: Working_Arrays_HIP, evaladjoint: bool = True):
+    """ntab evaluations traceobjgrad_samples(pqs[i], params, wa) in one library call (jq_traceobjgrad_samples_batch).  On the row-lane and
+    cooperative-quad (latency) kernels with the Stormer-Verlet integrator and the Neumann solver the tables share launches -- every
+    workgroup reads the operator stream of its own table --, everywhere else they run one after the other inside the call
+    (wa.plan_info()["sampled_batch"] says which).  Entry i equals the single call's at the same chunk length.
+
+    pqs: an [ntab, 2 Ncoupled, 2 nsteps + 1] array or a sequence of tables.
+    Returns the tuple of traceobjgrad_samples with a leading axis of length ntab on every element (gradients [ntab, 2 Ncoupled, nt];
+    leakgrad empty for objFuncType == 1).  Shape errors and entries that are not finite raise ValueError before any library call."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("traceobjgrad_samples_batch: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("traceobjgrad_samples_batch: wa was allocated for a different objparams")
+    T, shape = _sample_tables(pqs, params, "traceobjgrad_samples_batch")
+    n, ln = T.shape
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    out4 = np.zeros((n, 4))
+    if not evaladjoint:
+        _lib.check(L.jq_traceobjgrad_samples_batch(h, _ptr(T), shape[1], n, 0, _ptr(out4), None, None, None), h)
+        return _sample_columns(params, out4, None, None, None, shape, False)
+    tg, ig, lg = np.zeros((n, ln)), np.zeros((n, ln)), np.zeros((n, ln))
+    _lib.check(L.jq_traceobjgrad_samples_batch(h, _ptr(T), shape[1], n, 1, _ptr(out4), _ptr(tg), _ptr(ig), _ptr(lg)), h)
+    return _sample_columns(params, out4, tg, ig, lg, shape, True)
+
+
+def traceobjgrad_samples_members(pq, params: objparams, wa: Working_Arrays_HIP, Hconsts=None, ctrl_mix=None, evaladjoint: bool = True):
+    """ONE sample table under nmember members in one library call (jq_traceobjgrad_samples_members): member i has the drift
+    Hconsts[:, :, i] (None: the drift of params) and the real Nc x Nc control mix C_i = ctrl_mix[:, :, i] (None: identity) -- operator l is
+    driven by sum_k C_i[l, k] (p_k, q_k)(t_J), as in traceobjgrad_members.  Member i's gradients are those with respect to the SHARED
+    table (its mix folded in by C_i').  Routing as traceobjgrad_samples_batch (wa.plan_info()["sampled_batch"]); params.Hconst and the
+    handle's drift are what they were afterwards.
+
+    Returns the tuple of traceobjgrad_samples_batch, one entry per member.  Shape errors and entries that are not finite raise ValueError
+    before any library call."""
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("traceobjgrad_samples_members: wa must be a Working_Arrays_HIP")
+    if wa.params is not params:
+        raise ValueError("traceobjgrad_samples_members: wa was allocated for a different objparams")
+    tab, shape = _sample_table(pq, params, "traceobjgrad_samples_members")
+    H, C, n = _members(params, Hconsts, ctrl_mix, "traceobjgrad_samples_members")
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    out4 = np.zeros((n, 4))
+    if not evaladjoint:
+        _lib.check(L.jq_traceobjgrad_samples_members(h, _ptr(tab), shape[1], _ptr(H), _ptr(C), n, 0, _ptr(out4), None, None, None), h)
+        return _sample_columns(params, out4, None, None, None, shape, False)
+    tg, ig, lg = np.zeros((n, tab.size)), np.zeros((n, tab.size)), np.zeros((n, tab.size))
+    _lib.check(L.jq_traceobjgrad_samples_members(h, _ptr(tab), shape[1], _ptr(H), _ptr(C), n, 1, _ptr(out4), _ptr(tg), _ptr(ig), _ptr(lg)), h)
+    return _sample_columns(params, out4, tg, ig, lg, shape, True)
 
 
 def _direction_tables(dirs, params, who):

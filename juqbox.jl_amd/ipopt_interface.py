@@ -566,6 +566,46 @@ def eval_f_g_grad_members(pcof, params, wa, weights, Hconsts=None, ctrl_mix=None
     return params.last_infidelity, params.last_leak
 
 
+def eval_f_g_grad_samples_members(pq, params, wa, weights, Hconsts=None, ctrl_mix=None, compute_adjoint=True, per_member=False):
+    """eval_f_g_grad_members for controls given as VALUES on the time grid (jq_eval_f_g_grad_samples_members): the weighted sums over
+    members that share ONE sample table and differ in a real mixing matrix of the controls (ctrl_mix), in their drift (Hconsts), or in
+    both -- the robust objective of a piecewise-constant, filtered or network-generated pulse.  The two gradients are summed on the device
+    in member order; the members' own gradient tables are never fetched.  Routing: wa.plan_info()["sampled_batch"].
+
+    weights: one per member.  Returns the dict of eval_f_g_grad_samples (infidelity, leak, and with compute_adjoint infid_grad, leak_grad in
+    the shape of pq), with per_member=True also members: the array [4, nmember] of the members' records -- the bits of
+    traceobjgrad_samples_members.  No Tikhonov term; params.last_* are left alone.  Shape errors and entries that are not finite raise
+    ValueError before any library call."""
+    who = "eval_f_g_grad_samples_members"
+    if not isinstance(wa, Working_Arrays_HIP):
+        raise TypeError("%s: wa must be a Working_Arrays_HIP" % who)
+    if wa.params is not params:
+        raise ValueError("%s: wa was allocated for a different objparams" % who)
+    tab, shape = _sample_table(pq, params, who)
+    H, C, nm = _members(params, Hconsts, ctrl_mix, who)
+    try:
+        w = np.asarray(weights, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("%s: weights must be a vector of numbers (%s)" % (who, e))
+    if w.ndim != 1 or w.size != nm:
+        raise ValueError("%s: need one weight per member (%d), not shape %r" % (who, nm, w.shape))
+    w = _f64(w)
+    L, h = _lib.load(), wa.handle
+    wa.sync_params()
+    out2 = np.zeros(2)
+    ig = np.zeros(tab.size) if compute_adjoint else None
+    lg = np.zeros(tab.size) if compute_adjoint else None
+    member_out = np.zeros((nm, 4)) if per_member else None
+    _lib.check(L.jq_eval_f_g_grad_samples_members(h, _ptr(tab), shape[1], _ptr(H), _ptr(C), _ptr(w), nm, 1 if compute_adjoint else 0, _ptr(out2),
+                                                  _ptr(ig), _ptr(lg), _ptr(member_out)), h)
+    r = dict(infidelity=float(out2[0]), leak=float(out2[1]))
+    if compute_adjoint:
+        r["infid_grad"], r["leak_grad"] = ig.reshape(shape, order="F"), lg.reshape(shape, order="F")
+    if per_member:
+        r["members"] = np.ascontiguousarray(member_out.T)
+    return r
+
+
 def _stale(pcof, params):
     # memoisation on ||pcof - last_pcof|| > 1e-15 (src/ipopt_interface.jl:83-84)
     last = params.last_pcof

@@ -6,6 +6,14 @@
       dJ/dpq as its backward.  Whatever produced pq -- a piecewise-constant pulse through repeat_interleave, an envelope, a filter, a
       torch.nn.Module -- is differentiated by torch; the time loops run in the library.
 
+  SampledMembersObjective.apply(pq, params, wa, weights, Hconsts, ctrl_mix)
+      the weighted infidelity + leak of a member ensemble under ONE table (eval_f_g_grad_samples_members: members that differ in their
+      drift, in a real mix of the controls, or in both) as a 0-dimensional tensor with dJ/dpq -- the robust objective of such a pulse.
+
+  SampledBatchObjective.apply(pqs, params, wa)
+      the objectives of ntab tables pqs[ntab, 2 Ncoupled, 2 nsteps + 1] in one library call (traceobjgrad_samples_batch) as a tensor of
+      ntab values; its backward contracts grad_output with the per-table gradients.
+
   sampled_hessvec(fn, theta, v, params, wa, nodes=None, weights=None, shift=None)
       the derivative along v of the gradient of J(fn(theta)): the library's Hessian-vector product in sample space
       (eval_f_g_grad_samples_hvp) between torch.func.jvp and vjp of fn, plus the curvature of fn against the sample gradient.
@@ -14,8 +22,8 @@ The samples go through host memory (the library's entry points take host pointer
 import numpy as np
 import torch
 
-from .evalobjgrad import traceobjgrad_samples
-from .ipopt_interface import eval_f_g_grad_samples, eval_f_g_grad_samples_hvp
+from .evalobjgrad import traceobjgrad_samples, traceobjgrad_samples_batch
+from .ipopt_interface import eval_f_g_grad_samples, eval_f_g_grad_samples_hvp, eval_f_g_grad_samples_members
 
 
 class SampledObjective(torch.autograd.Function):
@@ -44,6 +52,46 @@ class SampledObjective(torch.autograd.Function):
     def backward(ctx, grad_output):
         (grad,) = ctx.saved_tensors
         return grad_output * grad, None, None, None, None, None
+
+
+class SampledMembersObjective(torch.autograd.Function):
+    """J(pq) = sum_g w_g (infidelity_g + leak_g) over the members of eval_f_g_grad_samples_members (Hconsts or ctrl_mix may be None)."""
+
+    @staticmethod
+    def forward(ctx, pq, params, wa, weights, Hconsts=None, ctrl_mix=None):
+        if not isinstance(pq, torch.Tensor) or pq.dtype != torch.float64:
+            raise TypeError("SampledMembersObjective: pq must be a float64 tensor")
+        table = pq.detach().to("cpu").numpy()
+        want_grad = bool(ctx.needs_input_grad[0])
+        r = eval_f_g_grad_samples_members(table, params, wa, weights, Hconsts=Hconsts, ctrl_mix=ctrl_mix, compute_adjoint=want_grad)
+        if want_grad:
+            ctx.save_for_backward(torch.from_numpy(np.ascontiguousarray(r["infid_grad"] + r["leak_grad"])).to(pq.device))
+        return torch.tensor(float(r["infidelity"] + r["leak"]), dtype=torch.float64, device=pq.device)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (grad,) = ctx.saved_tensors
+        return grad_output * grad, None, None, None, None, None
+
+
+class SampledBatchObjective(torch.autograd.Function):
+    """J_i = objfv of traceobjgrad_samples(pqs[i]) for the ntab tables of pqs[ntab, 2 Ncoupled, 2 nsteps + 1], in one library call."""
+
+    @staticmethod
+    def forward(ctx, pqs, params, wa):
+        if not isinstance(pqs, torch.Tensor) or pqs.dtype != torch.float64 or pqs.dim() != 3:
+            raise TypeError("SampledBatchObjective: pqs must be a float64 tensor [ntab, 2 Ncoupled, 2 nsteps + 1]")
+        tables = pqs.detach().to("cpu").numpy()
+        want_grad = bool(ctx.needs_input_grad[0])
+        r = traceobjgrad_samples_batch(tables, params, wa, want_grad)
+        if want_grad:
+            ctx.save_for_backward(torch.from_numpy(np.ascontiguousarray(r[1])).to(pqs.device))
+        return torch.from_numpy(np.ascontiguousarray(r[0])).to(pqs.device)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (grads,) = ctx.saved_tensors
+        return grad_output[:, None, None] * grads, None, None
 
 
 def sampled_hessvec(fn, theta, v, params, wa, nodes=None, weights=None, shift=None):
